@@ -21,20 +21,25 @@ chunk buffer.
 The pass itself lives in roadsurf_amd/workload.py (SyntheticRun) and is the code the
 parity tests step at the same size (tests/test_hip_golden_and_scale.py).  Outputs stay
 attributable to points: with plan order on, the order row of every launch is kept
-(inside the timed region).  A second timed leg runs the same passes in natural order and
-is reported as `natural_order_value`.
+(inside the timed region).
+
+A plain run does only what the headline needs: set up, W untimed passes, K timed passes,
+the outputs of the last timed pass if `--dump-outputs DIR` is given, one JSON line.
+Everything else the benchmark measures runs only with `--full` (below).
 
 Multi-GPU: one process per GPU (torch.distributed.run), points sharded with no
 data-path collective; the only collectives are the timing barrier and the MAX
 over ranks.  Default is STRONG scaling (BASELINE config 4: --total-points 1 000 000
 sharded over the GPUs); `--points N` gives every GPU N points (weak scaling).
 
-The default run (N = 1) adds short extra legs under the same clock, reported as extra keys of the
-one JSON line: `full_feature_value` (the FULL feature set on the same points) and
+`--full` adds, under the same clock: a second timed leg of the same passes in natural order
+(`natural_order_value`), the CPU baseline (`cpu_baseline`), and with N = 1 short extra legs, reported
+as extra keys of the one JSON line: `full_feature_value` (the FULL feature set on the same points) and
 `driver_path_{relax,coupling,sky}_value` (rs_driver_run from raw series in host arrays, PCIe
 inclusive), `driver_path_relax_holes_value` (the same on observation series with missing sensors,
 gaps and early ends), `driver_path_relax_bench_weather_value` (the same on the headline's weather), `host_batch_value` (runsimulation_batch from step-resolution host arrays);
-`--no-extra-legs` skips them.
+`--no-natural-leg`, `--no-cpu-baseline` and `--no-extra-legs` leave the parts out again.
+(`--full-features` is something else: the FULL feature set as the headline's workload.)
 
 Prints ONE JSON line on rank 0.
 """
@@ -245,6 +250,82 @@ class ClockProbe:
         return None if abs(m - 100.0) < 1.0 else m
 
 
+class OutputSample:
+    """--dump-outputs: what the timed path hands its caller in the last timed pass.  A caller receives every
+    launch's output window [index][slot] and the launch's order row (slot -> point); here the windows are read
+    back into points on each plan's stream as the pass runs (so the last timed pass carries this work) and
+    written after it, for rank 0's shard:
+
+      <field>.npy        [S, SimLen]  every time index of a fixed sample of S points (seeded by --seed), whose
+                                      global point indices are points.npy
+      final_<field>.npy  [n]          every point of the shard at the last time index (above FINAL_MAX points a
+                                      seeded sample, whose global indices are final_points.npy)
+
+    Six fields each, float64 (float32 with --f32), at most BUDGET bytes in all; same arguments, same files."""
+
+    BUDGET = 60_000_000
+    FINAL_MAX = 1 << 20
+    SERIES_MAX = 32
+
+    def __init__(self, torch, dev, plans, offsets, offset: int, n: int, simlen: int, seed: int, f32: bool):
+        import numpy as np
+
+        from roadsurf_amd import device
+
+        self.torch, self.fields = torch, device.OUT_FIELDS
+        dtype = torch.float32 if f32 else torch.float64
+        item = 4 if f32 else 8
+        rng = np.random.default_rng(seed)
+        nf = min(n, self.FINAL_MAX)
+        final = np.arange(n) if nf == n else np.sort(rng.choice(n, nf, replace=False))
+        room = self.BUDGET - nf * (6 * item + (8 if nf < n else 0))
+        ns = max(0, min(self.SERIES_MAX, n, room // (6 * item * simlen + 8)))
+        series = np.sort(rng.choice(n, ns, replace=False))
+        self.points = {"points": series + offset} if ns else {}
+        if nf < n:
+            self.points["final_points"] = final + offset
+        self.series = {k: torch.full((ns, simlen), float("nan"), dtype=dtype, device=dev) for k in self.fields}
+        self.final = {k: torch.full((nf,), float("nan"), dtype=dtype, device=dev) for k in self.fields}
+        self.parts = []  # per plan: (plan, [(local points, destination rows) for the series and the final index])
+        for pl, off in zip(plans, offsets):
+            lo = off - offset
+            sel = []
+            for pts in (series, final):
+                rows = np.nonzero((pts >= lo) & (pts < lo + pl.npoints))[0]
+                sel.append((torch.as_tensor(pts[rows] - lo, dtype=torch.long, device=dev),
+                            torch.as_tensor(rows, dtype=torch.long, device=dev)) if len(rows) else None)
+            self.parts.append((pl, sel))
+
+    def on_launch(self, j: int, run):
+        """on_launch hook for plan j's SyntheticRun (workload.SyntheticRun.iter_pass)."""
+        pl, (ser, fin) = self.parts[j]
+        last = len(run.starts) - 1
+
+        def hook(c, t0, nsteps):
+            with self.torch.cuda.stream(pl.stream):  # before the next launch of this plan overwrites the window
+                if ser is not None:
+                    slots = run.slots_of(c, ser[0])
+                    for k in self.fields:
+                        self.series[k][ser[1], t0 - 1:t0 - 1 + nsteps] = run.out.tensors[k][:nsteps, slots].T
+                if fin is not None and c == last:
+                    slots = run.slots_of(c, fin[0])
+                    for k in self.fields:
+                        self.final[k][fin[1]] = run.out.tensors[k][nsteps - 1, slots]
+        return hook
+
+    def write(self, path: str) -> None:
+        """After the pass has finished on every stream."""
+        import numpy as np
+
+        os.makedirs(path, exist_ok=True)
+        for k in self.fields:
+            if self.series[k].shape[0]:
+                np.save(os.path.join(path, k + ".npy"), self.series[k].cpu().numpy())
+            np.save(os.path.join(path, "final_" + k + ".npy"), self.final[k].cpu().numpy())
+        for name, idx in self.points.items():
+            np.save(os.path.join(path, name + ".npy"), idx.astype(np.float64))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -284,9 +365,12 @@ def main() -> None:
                          "one plan's HBM-bound window expansion and re-sort run beside another's "
                          "VALU-bound step kernel, and the tail of one launch under the head of the next. "
                          "0 = auto by flavour and shard size")
-    ap.add_argument("--no-natural-leg", action="store_true",
-                    help="skip the second timed leg (natural order) that gives natural_order_value")
     ap.add_argument("--full", action="store_true",
+                    help="measure everything, not only the headline: the natural-order leg (natural_order_value), "
+                         "the CPU baseline (cpu_baseline) and, with one GPU, the extra legs (see --no-extra-legs)")
+    ap.add_argument("--no-natural-leg", action="store_true",
+                    help="with --full: skip the second timed leg (natural order) that gives natural_order_value")
+    ap.add_argument("--full-features", action="store_true",
                     help="the FULL feature set instead of the BASELINE workload's LEAN one: Tdew / TsurfObs / "
                          "depth streams present, a 6-hour initialization phase and relaxation behind it (what "
                          "an operational run uses; reported as config.feature_set)")
@@ -296,7 +380,7 @@ def main() -> None:
                          "point and index, summed over the ranks (what tests/test_hip_config4.py compares "
                          "between a one-rank and a two-rank launch)")
     ap.add_argument("--no-extra-legs", action="store_true",
-                    help="skip the short extra legs of the default run (N = 1, fp64, LEAN headline only): the FULL "
+                    help="with --full: skip its short extra legs (N = 1, fp64, LEAN headline only): the FULL "
                          "feature set on the same synthetic points (full_feature_value) and the driver data path "
                          "rs_driver_run with relaxation / coupling / sky view (driver_path_*_value), and runsimulation_batch "
                          "from step-resolution host arrays (host_batch_value)")
@@ -304,9 +388,14 @@ def main() -> None:
                     help="points of the driver-path legs (host arrays in, hourly outputs back: PCIe inclusive)")
     ap.add_argument("--host-batch-points", type=int, default=32768,
                     help="points of the runsimulation_batch leg (step-resolution host arrays in and out)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-sample", type=int, default=16384)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed passes write what the last one computed as DIR/<name>.npy (rank 0's "
+                         "shard; see OutputSample)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import torch.distributed as dist
@@ -346,7 +435,7 @@ def main() -> None:
         offset, n = sharding.strong_shard(total_points, world, rank)
     simlen = args.hours * workload.SPK + 1  # examples/example1/src/InputSettings.cpp:98
     settings = abi.default_settings(simlen)
-    if args.full:
+    if args.full_features:
         settings.use_relaxation = 1
     params = abi.default_parameters()
     if args.variant == 0 and not args.f32:
@@ -377,7 +466,7 @@ def main() -> None:
     chunk_auto = args.chunk <= 0
     if chunk_auto:
         args.chunk = ch
-    if args.full and n >= 400_000:
+    if args.full_features and n >= 400_000:
         # measured: three plans; launches of 120 indices with the knot-reading flavour (tools/experiments/
         # r4_full_duo.sh: 2.01e10 for 3 x 120, 2.00e10 for 3 x 240, 1.97e10 for 3 x 90 and 2 x 120), of 240
         # with a forcing window (tools/experiments/r3_full3.sh)
@@ -408,12 +497,13 @@ def main() -> None:
         torch.cuda.synchronize(dev)
 
     def timed_leg(plan_order: bool, plans=None, offsets=None, chunk_steps=None, full=None, steps=None,
-                  warmup=None, hours=None, f32=None):
-        """W untimed + exactly K timed passes, barrier + synchronize on both sides, MAX over ranks."""
+                  warmup=None, hours=None, f32=None, sample=None):
+        """W untimed + exactly K timed passes, barrier + synchronize on both sides, MAX over ranks.
+        `sample` (an OutputSample) reads the outputs of the last timed pass."""
         plans = plans_main if plans is None else plans
         offsets = offsets_main if offsets is None else offsets
         chunk_steps = args.chunk if chunk_steps is None else chunk_steps
-        full = args.full if full is None else full
+        full = args.full_features if full is None else full
         steps = args.steps if steps is None else steps
         warmup = args.warmup if warmup is None else warmup
         runs = [workload.SyntheticRun(pl, args.seed, args.hours if hours is None else hours, chunk_steps, point_offset=o,
@@ -424,8 +514,8 @@ def main() -> None:
                 for pl, o in zip(plans, offsets)]
         run = runs[0]
 
-        def one_pass():
-            its = [r.iter_pass() for r in runs]
+        def one_pass(sample=None):
+            its = [r.iter_pass(sample.on_launch(j, r) if sample else None) for j, r in enumerate(runs)]
             while its:  # launch c of every plan, then launch c+1 ...
                 its = [it for it in its if next(it, None) is not None]
 
@@ -439,8 +529,8 @@ def main() -> None:
         torch.cuda.synchronize(dev)
         clk = ClockProbe(torch, dev, dev_index, steps)
         t_start = time.perf_counter()
-        for _ in range(steps):
-            one_pass()
+        for i in range(steps):
+            one_pass(sample if i == steps - 1 else None)
             clk.probe()  # runs beside the launches still in flight
         fence()
         elapsed = time.perf_counter() - t_start
@@ -467,9 +557,15 @@ def main() -> None:
 
     cluster = bool(args.cluster)
     sclk = []  # mean engine clock of each timed leg (MHz), None where not readable
-    elapsed, step_ms, nlaunch, chunk, busy_ms = timed_leg(cluster)
+    sample = None
+    if args.dump_outputs and rank == 0:
+        sample = OutputSample(torch, dev, plans, offsets, offset, n, simlen, args.seed, args.f32)
+    elapsed, step_ms, nlaunch, chunk, busy_ms = timed_leg(cluster, sample=sample)
+    if sample is not None:
+        sample.write(args.dump_outputs)
+        del sample
     natural = None
-    if cluster and not args.no_natural_leg:
+    if args.full and cluster and not args.no_natural_leg:
         if fused:
             # natural order has no knot-reading flavour (nothing to gather through): its best shape is the
             # round-3 one - one point per lane, expansion kernel + forcing window, 4 x 120 / 4 x 240 / 2 x 240
@@ -491,7 +587,7 @@ def main() -> None:
             run = workload.SyntheticRun(pl, args.seed, args.hours, args.chunk, point_offset=o,
                                         plan_order=cluster, f32=args.f32, forecast=args.sort_key == "forecast",
                                         forecast_alpha=args.forecast_alpha, forecast_mode=args.forecast_mode,
-                                        full=args.full)
+                                        full=args.full_features)
 
             def on_launch(c, t0, ns, run=run, pl=pl):
                 with torch.cuda.stream(pl.stream):
@@ -515,17 +611,17 @@ def main() -> None:
     units_per_pass_rank = n * simlen
     value = units_per_pass_job * args.steps / elapsed
 
-    # ---- extra legs of the default run: the rows behind the headline, under the same clock ----------
+    # ---- extra legs of --full: the rows behind the headline, under the same clock -------------------
     # (N = 1, fp64, LEAN headline only; each a few seconds; --no-extra-legs skips them)
     extra = {}
-    if world == 1 and not (args.no_extra_legs or args.f32 or args.full) and cluster:
+    if args.full and world == 1 and not (args.no_extra_legs or args.f32 or args.full_features) and cluster:
         t_x = time.perf_counter()
         # the headline's plans are done (its timing events and failure counts are read): every leg below has the
         # GPU to itself, as the headline had (the library counts a device's live plans: rs_api.hip `underfilled`)
         for pl in plans:
             pl.close()
         # (1) the FULL feature set (Tdew / TsurfObs / depth streams, 6 h initialization phase, relaxation
-        # behind it) on the same synthetic points: what `bench.py --full` reports as its headline
+        # behind it) on the same synthetic points: what `bench.py --full-features` reports as its headline
         s_full = abi.default_settings(simlen)
         s_full.use_relaxation = 1
         Kf, chunk_f = (3, 120) if n >= 400_000 else (K, args.chunk)  # measured: tools/experiments/r4_full_duo.sh
@@ -658,7 +754,7 @@ def main() -> None:
     concurrency = step_ms / busy_ms
 
     traffic, valu, traffic_file, traffic_note = measured_traffic(n, chunk, K, args.f32)
-    if args.full:
+    if args.full_features:
         traffic, valu, traffic_note = None, None, "counter summaries are kept for the LEAN feature set only"
 
     # the binding roofline, from this run: vector-issue time of one pass (SQ_ACTIVE_INST_VALU of the
@@ -687,13 +783,13 @@ def main() -> None:
             "data": "synthetic",
             "config": {
                 "workload": f"{total_points} synthetic points x {args.hours} h (SimLen {simlen}, DTSecs 30, "
-                            f"NLayers 15), {'fp32' if args.f32 else 'fp64'}, {'FULL' if args.full else 'LEAN'} feature set, outputs every time index, "
+                            f"NLayers 15), {'fp32' if args.f32 else 'fp64'}, {'FULL' if args.full_features else 'LEAN'} feature set, outputs every time index, "
                             f"attributable to points"
                             + (" (per-launch order rows kept inside the timed region)" if cluster else ""),
                 "total_points": total_points,
                 "points_per_gpu": n,
                 "plans_per_gpu": K,
-                "feature_set": "FULL (dew point and observation streams, 6 h initialization phase, relaxation)" if args.full else "LEAN",
+                "feature_set": "FULL (dew point and observation streams, 6 h initialization phase, relaxation)" if args.full_features else "LEAN",
 
                 "simlen": simlen,
                 "chunk_steps": chunk,
@@ -768,7 +864,7 @@ def main() -> None:
                 "note": "second timed leg, same W/K and fences: points in natural order, no re-sort"
                         + (", expansion kernel + forcing window, one point per lane" if fused else ""),
             }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.cpu_sample, simlen, args.seed)
         print(json.dumps(line), flush=True)
     for pl in plans:

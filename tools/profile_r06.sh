@@ -5,7 +5,7 @@
 #   f32    BASELINE config 5 shape (1.25 M points x 7 d, fp32: two points per lane, 2 plans x 360) -> profiles/r06_f32_*
 #   small  125 000 points (config 4's per-GPU shard), one point per lane
 #          against two wavefronts per 64 points                          -> profiles/r06_small_shard_*
-#   full   FULL feature set (bench.py --full)                            -> profiles/r06_full_*
+#   full   FULL feature set (bench.py --full-features)                   -> profiles/r06_full_*
 # usage: profile_r06.sh [lean] [f32] [small] [full]   (default: all)
 set -e
 export TMPDIR=/tmp
@@ -16,6 +16,7 @@ B1="--steps 1 --warmup 0 --no-cpu-baseline --no-natural-leg --no-extra-legs"
 profile() { # tag, bench flags...
   local TAG=$1; shift
   local OUT=gpurun_out/prof_$TAG
+  PDIR=$OUT  # the bench runs after a profile call write beside its results
   rm -rf $OUT; mkdir -p $OUT
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-natural-leg --no-extra-legs "$@" > $OUT/bench_under_rocprof.json 2> $OUT/trace.err || { tail -20 $OUT/trace.err; exit 1; }
   find $OUT/trace -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/kernel_stats.csv
@@ -33,11 +34,11 @@ profile() { # tag, bench flags...
 for W in $WHAT; do case $W in
 lean)
   profile r06
-  python3 bench.py --steps 20 --warmup 5 > gpurun_out/prof_r06/bench.json 2> gpurun_out/prof_r06/bench.err
+  python3 bench.py --full --steps 20 --warmup 5 > $PDIR/bench.json 2> $PDIR/bench.err
   ;;
 f32)
   profile r06_f32 --f32 --points 1250000 --hours 168
-  python3 bench.py --f32 --points 1250000 --hours 168 --steps 3 --warmup 1 --no-cpu-baseline > gpurun_out/prof_r06_f32/bench.json 2> gpurun_out/prof_r06_f32/bench.err
+  python3 bench.py --full --f32 --points 1250000 --hours 168 --steps 3 --warmup 1 --no-cpu-baseline > $PDIR/bench.json 2> $PDIR/bench.err
   ;;
 small)
   for V in 1 3; do
@@ -53,7 +54,7 @@ small)
   python3 bench.py --total-points 250000 --steps 10 --warmup 2 --no-cpu-baseline --no-natural-leg --no-extra-legs > gpurun_out/prof_r06_small_v1/bench_250k.json 2>/dev/null
   ;;
 full)
-  profile r06_full --full
-  python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-natural-leg --no-extra-legs > gpurun_out/prof_r06_full/bench.json 2> gpurun_out/prof_r06_full/bench.err
+  profile r06_full --full-features
+  python3 bench.py --full-features --steps 5 --warmup 2 > $PDIR/bench.json 2> $PDIR/bench.err
   ;;
 esac; done

@@ -16,7 +16,7 @@ hours = int(sys.argv[3]) if len(sys.argv) > 3 else 48
 simlen = hours * 120 + 1
 s = abi.default_settings(simlen); p = abi.default_parameters()
 if what == "bench-full":
-    s.use_relaxation = 1  # (as bench.py --full)
+    s.use_relaxation = 1  # (as bench.py --full-features)
 if what.startswith("driver"):
     from roadsurf_amd import driver_workload
     w = driver_workload.DriverWorkload(n, hours)

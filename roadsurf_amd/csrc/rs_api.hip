@@ -618,15 +618,65 @@ int rs_hip_init_state(RsPlan *pl, const RsForcing *f, const RsPointParams *pp) {
   return 0;
 }
 
+/* 32-bit window offsets (WinOff) where every stream of the launch's windows spans fewer elements than rs_a32_limit:
+ * the forcing window (f_stride; 0: the launch reads none), the output rows from row0 to the launch's last, the
+ * sky-view write-back (wb_stride; 0: none) */
+static bool window_a32(const RsOutputs *o, int32_t t0, int32_t nsteps, int64_t f_stride, int64_t wb_stride) {
+  const uint64_t lim = rs_a32_limit();
+  const int64_t out_rows = ((int64_t)t0 + nsteps - 2) / o->decimate - o->row0 + 1;
+  return (uint64_t)f_stride * (uint64_t)nsteps < lim && (uint64_t)wb_stride * (uint64_t)nsteps < lim &&
+         (uint64_t)o->t_stride * (uint64_t)(out_rows > 0 ? out_rows : 1) < lim;
+}
+
+/* what every step launch of the plan reads; the rest of StepArgs is the entry point's */
+static void step_args(const RsPlan *pl, const RsOutputs *o, const RsPointParams *pp, int32_t t0, int32_t nsteps,
+                      rs::StepArgs &a) {
+  a.consts = pl->f32 ? pl->consts32_dev : pl->consts_dev;
+  a.o = *o;
+  a.pp = *pp;
+  a.state = pl->state;
+  a.npoints = pl->npoints;
+  a.np_pad = pl->np_pad;
+  a.t0 = t0;
+  a.nsteps = nsteps;
+}
+
+/* the two-wavefront flavour's wave table (valid for the slot order the last forecast re-sort left) and surface
+ * priority */
+static void wave_args(const RsPlan *pl, rs::StepArgs &a) {
+  a.wave_start = pl->wave_tab_valid ? pl->wave_tab : nullptr;
+  a.wave_cnt = pl->wave_tab_valid ? pl->wave_tab + pl->wave_n : nullptr;
+  a.wave_n = pl->wave_n;
+  a.surface_prio = underfilled(pl);
+}
+
+/* One step launch: the entry point's part of the shape (forcing source, feature set, sky view, output depth,
+ * coupling phase, 32-bit offsets) completed from the plan and `a`, the instance rs::select_step picks for it. */
+static hipError_t launch_step(const RsPlan *pl, const rs::StepArgs &a, rs::StepShape s) {
+  s.f32 = pl->f32;
+  s.nlayers = pl->c.NLayers;
+  s.score = pl->history_score;
+  s.variant = pl->variant;
+  s.npoints = pl->npoints;
+  s.diag = a.diag != nullptr;
+  s.wave_n = a.wave_start ? a.wave_n : 0;
+  s.cpl_list = a.cpl_list != nullptr;
+  s.cpl_nlist = a.cpl_nlist;
+  const rs::StepLaunch l = rs::select_step(s);
+  if (l.kernel == rs::StepKernel::NONE) return hipErrorInvalidValue;
+  if (l.grid == 0) return hipSuccess; /* an empty list */
+  return s.f32 ? rs32_launch_step(a, l, pl->stream) : rs_launch_step(a, l, pl->stream);
+}
+
 /* The replay rounds of a coupled run: while some points ask for another replay of their coupling
  * window (start_coupling_again), those points - compacted into full wavefronts - rewind, replay
  * the window and park again (step_kernel_coupled with cpl_stop).  `a` describes a window that
  * covers every such point's [couplingStartI, couplingEndI]. */
-/* lockstep: the window is compact (every point's coupling window fills most of it) and ends before
+/* s.cpl = REPLAY (lock step): the window is compact (every point's coupling window fills most of it) and ends before
  * the final index, no sky view: the rounds run the lock-step loop over the list (time_loop<REPLAY>:
  * scalar row arithmetic, coalesced outputs of the first pass' quality) instead of the general
- * kernel, which carries a time index per lane. */
-static int cpl_replay_rounds(RsPlan *pl, rs::StepArgs a, bool lockstep = false, bool raw = false) {
+ * kernel (s.cpl = GENERAL), which carries a time index per lane.  s.src = RAW: the forcing from the raw series. */
+static int cpl_replay_rounds(RsPlan *pl, rs::StepArgs a, const rs::StepShape &s) {
   if (!pl->cpl_list) {
     HIP_OK(plan_malloc(pl, &pl->cpl_flags, (size_t)2 * pl->np_pad * sizeof(int32_t)));
     HIP_OK(plan_malloc(pl, &pl->cpl_list, (size_t)pl->np_pad * sizeof(int32_t)));
@@ -657,17 +707,13 @@ static int cpl_replay_rounds(RsPlan *pl, rs::StepArgs a, bool lockstep = false, 
      * take issue slots from the other blocks' launches).  So it is done only for the tail of the tail:
      * once the list is down to 1/64 of the plan's points.  ROADSURF_HIP_CPL_COLLAPSE=r collapses from
      * round r on instead (tests; 0 = never). */
-    bool collapse = lockstep && !raw && (int64_t)n_again * 64 <= pl->npoints;
+    const bool lockstep = s.cpl == rs::StepCoupling::REPLAY && s.src == rs::StepSource::WINDOW;
+    bool collapse = lockstep && (int64_t)n_again * 64 <= pl->npoints;
     if (const char *e = getenv("ROADSURF_HIP_CPL_COLLAPSE"))
-      collapse = lockstep && !raw && atoi(e) > 0 && round + 1 >= atoi(e);
+      collapse = lockstep && atoi(e) > 0 && round + 1 >= atoi(e);
     a.cpl_inner = collapse ? 64 : 1;
     a.cpl_prio = ((int64_t)n_again * 4 <= pl->npoints) ? 1 : 0;
-    if (raw) /* two wavefronts per 64 listed points, forcing from the raw series (one replay per round) */
-      HIP_OK(rs_launch_step_duo_raw_replay(a, pl->stream));
-    else if (lockstep)
-      HIP_OK(rs_launch_step_cpl_replay(a, pl->c.NLayers, pl->stream));
-    else
-      HIP_OK(rs_launch_step_coupled(a, pl->c.NLayers, pl->stream));
+    HIP_OK(launch_step(pl, a, s));
     pl->cpl_rounds_last = round + 1;
     if (round == 63) { /* Coupling_control gives up after 25 passes: a point still listed now never will */
       HIP_OK(rs_cpl_select_again(pl->state, pl->np_pad, pl->npoints, pl->cpl_flags, pl->cpl_list,
@@ -731,42 +777,17 @@ int rs_hip_step(RsPlan *pl, const RsForcing *f, const RsOutputs *o, const RsPoin
   if (pl->f32 && (skyview || coupled) && pl->wb.sw_dir)
     return set_err("rs_hip_step: the fp32 flavour does not write the in-place input edits back (fp64 arrays)");
   rs::StepArgs a;
-  a.consts = pl->f32 ? pl->consts32_dev : pl->consts_dev;
+  step_args(pl, o, pp, t0, nsteps, a);
   a.f = *f;
-  a.o = *o;
-  a.pp = *pp;
-  a.state = pl->state;
-  a.npoints = pl->npoints;
-  a.np_pad = pl->np_pad;
-  a.t0 = t0;
-  a.nsteps = nsteps;
-  a.wb = pl->wb;
-  if (a.wb.sw_dir && !skyview) a.wb = rs::Writeback{nullptr, nullptr, nullptr, 0};
-  a.cpl_list = nullptr;
-  a.cpl_nlist = 0;
-  a.cpl_stop = 0;
-  a.cpl_inner = a.cpl_prio = 0;
-  a.out_index = nullptr;
-  a.wave_start = pl->wave_tab_valid ? pl->wave_tab : nullptr;
-  a.wave_cnt = pl->wave_tab_valid ? pl->wave_tab + pl->wave_n : nullptr;
-  a.wave_n = pl->wave_n;
-  a.duo_full_ok = (full && !skyview && !coupled && !f->depth && !(pl->c.tsurfOutputDepth >= 0.0)) ? 1 : 0;
-  {
-    /* bit 2: a sky-view launch the two-wavefront flavour can take (rs_launch_step_sky): no output depth, and
-     * every stream of the windows within 32-bit offsets */
-    const int64_t orows = ((int64_t)t0 + nsteps - 2) / o->decimate - o->row0 + 1;
-    const bool a32 = (uint64_t)f->t_stride * (uint64_t)nsteps < rs_a32_limit() &&
-                     (uint64_t)o->t_stride * (uint64_t)(orows > 0 ? orows : 1) < rs_a32_limit() &&
-                     (!pl->wb.sw_dir || (uint64_t)pl->wb.t_stride * (uint64_t)nsteps < rs_a32_limit());
-    if (skyview && !coupled && !f->depth && !(pl->c.tsurfOutputDepth >= 0.0) && a32) a.duo_full_ok |= 4;
-  }
-  a.surface_prio = underfilled(pl);
-  a.knots = nullptr;
-  a.knot_gather = nullptr;
-  a.knot_k0 = a.knot_n = a.spk = a.start_hour = 0;
-  a.r_spk = 0.0;
-  std::memset(&a.raw, 0, sizeof(a.raw));
+  if (skyview) a.wb = pl->wb;
+  wave_args(pl, a);
   a.diag = pl->diag_on ? pl->diag : nullptr;
+  rs::StepShape s;
+  s.full = full;
+  s.sky = skyview;
+  s.depth = f->depth || pl->c.tsurfOutputDepth >= 0.0;
+  s.cpl = coupled ? rs::StepCoupling::GENERAL : rs::StepCoupling::NONE;
+  s.a32 = window_a32(o, t0, nsteps, f->t_stride, a.wb.sw_dir ? a.wb.t_stride : 0);
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (pl->timing) {
     if (pl->ev_used + 2 > pl->ev.size()) {
@@ -784,33 +805,26 @@ int rs_hip_step(RsPlan *pl, const RsForcing *f, const RsOutputs *o, const RsPoin
     HIP_OK(hipEventRecord(e0, pl->stream));
   }
   hipError_t le;
-  if (pl->f32 && (coupled || f->depth || pl->c.tsurfOutputDepth >= 0.0 || ((full || skyview) && pl->c.NLayers != 15)))
-    /* the general fp32 kernel (rs_kernels_f32.hip): every point replays its coupling window inside the one launch; or
-     * an output depth, or the FULL feature set / sky view at a layer count the two-wavefront kernels are not built for */
-    le = rs32_launch_step_coupled(a, pl->c.NLayers, pl->stream);
-  else if (pl->f32)
-    le = rs32_launch_step(a, pl->c.NLayers, pl->variant, pl->history_score, full || skyview, skyview, pl->stream);
-  else if (skyview && !coupled)
-    le = rs_launch_step_sky(a, pl->c.NLayers, pl->history_score, pl->stream); /* lock-step FULL + sky view */
-  else if (coupled) {
+  if (coupled && !pl->f32) {
     /* Rounds instead of "every wavefront replays until its slowest lane is through"
      * (src/Coupling.f90:61-78,324: up to 25 replays of a window of up to 360 indices, per point):
      *   1. every point steps to the end of its coupling window and parks there;
      *   2. while some points ask for another replay: those points, compacted into full
      *      wavefronts, rewind, replay their window and park again;
      *   3. every point goes on from behind its window to the end of the series.
-     * A point's arithmetic is the same sequence whichever round executes it. */
+     * A point's arithmetic is the same sequence whichever round executes it.  (The fp32 general kernel replays
+     * inside its one launch.) */
     a.cpl_stop = 1;
-    le = rs_launch_step_coupled(a, pl->c.NLayers, pl->stream);
-    if (le == hipSuccess && cpl_replay_rounds(pl, a) != 0) return -1;
+    le = launch_step(pl, a, s);
+    if (le == hipSuccess && cpl_replay_rounds(pl, a, s) != 0) return -1;
     if (le == hipSuccess) {
       a.cpl_list = nullptr;
       a.cpl_nlist = 0;
       a.cpl_stop = 0;
-      le = rs_launch_step_coupled(a, pl->c.NLayers, pl->stream);
+      le = launch_step(pl, a, s);
     }
   } else
-    le = rs_launch_step(a, pl->c.NLayers, full, pl->variant, pl->history_score, pl->stream);
+    le = launch_step(pl, a, s);
   if (le != hipSuccess) /* the pair stays unused: ev_used has not advanced */
     return set_err("rs_hip_step: kernel launch failed: %s", hipGetErrorString(le));
   if (pl->timing) {
@@ -846,10 +860,8 @@ int rs_hip_step_knots(RsPlan *pl, const RsSynthSpec *spec, const double *knots, 
     const int64_t first = ((int64_t)t0 - 1 + o->decimate - 1) / o->decimate;
     if (first < o->row0) return set_err("rs_hip_step_knots: output row0 beyond first row");
   }
-  const int64_t out_rows = ((int64_t)t0 + nsteps - 2) / o->decimate - o->row0 + 1;
   if (pl->c.NLayers != 15 || pl->c.tsurfOutputDepth >= 0.0 || pp->sky_view ||
-      (pl->c.use_coupling && pp->coupling_index) ||
-      (!pl->f32 && (uint64_t)o->t_stride * (uint64_t)(out_rows > 0 ? out_rows : 1) >= rs_a32_limit()))
+      (pl->c.use_coupling && pp->coupling_index) || (!pl->f32 && !window_a32(o, t0, nsteps, 0, 0)))
     return set_err("rs_hip_step_knots: NLayers = 15, no output depth, sky view or coupling and (fp64) an output "
                    "window below 4 GiB per stream only - use rs_hip_expand_forcing_ordered + rs_hip_step");
   /* the FULL feature set as far as the knots carry it: the dew point (CheckValues' test), the observation
@@ -862,21 +874,10 @@ int rs_hip_step_knots(RsPlan *pl, const RsSynthSpec *spec, const double *knots, 
   if (!order) return -1;
   HIP_OK(hipSetDevice(pl->device));
   rs::StepArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.consts = pl->f32 ? pl->consts32_dev : pl->consts_dev;
+  step_args(pl, o, pp, t0, nsteps, a);
   a.f.t_stride = pl->np_pad; /* no window: nothing of `f` is read */
-  a.o = *o;
-  a.pp = *pp;
-  a.state = pl->state;
-  a.npoints = pl->npoints;
-  a.np_pad = pl->np_pad;
-  a.t0 = t0;
-  a.nsteps = nsteps;
-  a.wave_start = pl->wave_tab_valid ? pl->wave_tab : nullptr;
-  a.wave_cnt = pl->wave_tab_valid ? pl->wave_tab + pl->wave_n : nullptr;
-  a.wave_n = pl->wave_n;
-  a.duo_full_ok = full ? 3 : 0; /* bit 1: the dew-point test (the knots always carry a dew point) */
-  a.surface_prio = underfilled(pl);
+  wave_args(pl, a);
+  a.knots_tdew = full ? 2 : 0; /* the dew-point test (the knots always carry a dew point) */
   a.knots = knots;
   a.knot_gather = order;
   a.knot_k0 = k0;
@@ -884,7 +885,9 @@ int rs_hip_step_knots(RsPlan *pl, const RsSynthSpec *spec, const double *knots, 
   a.spk = spk;
   a.start_hour = spec->start_hour;
   a.r_spk = 1.0 / (double)spk;
-  a.diag = nullptr;
+  rs::StepShape s;
+  s.src = rs::StepSource::KNOTS;
+  s.full = full;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (pl->timing) {
     if (pl->ev_used + 2 > pl->ev.size()) {
@@ -902,8 +905,7 @@ int rs_hip_step_knots(RsPlan *pl, const RsSynthSpec *spec, const double *knots, 
     HIP_OK(hipEventRecord(e0, pl->stream));
   }
   /* fp32: two points per lane, each lane interpolating its own forcing (rs_kernels_f32.hip) */
-  const hipError_t le = pl->f32 ? rs32_launch_step_knots(a, pl->history_score, full, pl->stream)
-                                : rs_launch_step_duo_knots(a, pl->history_score, pl->stream);
+  const hipError_t le = launch_step(pl, a, s);
   if (le != hipSuccess) return set_err("rs_hip_step_knots: kernel launch failed: %s", hipGetErrorString(le));
   if (pl->timing) {
     HIP_OK(hipEventRecord(e1, pl->stream));
@@ -935,8 +937,7 @@ int rs_step_raw(RsPlan *pl, const rs::RawForcing *raw, const double *sun, const 
     return set_err("rs_step_raw: window [%d,%d) outside [1,SimLen=%d]", t0, t0 + nsteps, pl->c.SimLen);
   const int64_t first = ((int64_t)t0 - 1 + o->decimate - 1) / o->decimate;
   if (first < o->row0) return set_err("rs_step_raw: output row0 beyond first row");
-  const int64_t out_rows = ((int64_t)t0 + nsteps - 2) / o->decimate - o->row0 + 1;
-  if (!rs_step_raw_ok(pl) || (uint64_t)o->t_stride * (uint64_t)(out_rows > 0 ? out_rows : 1) >= rs_a32_limit())
+  if (!rs_step_raw_ok(pl) || !window_a32(o, t0, nsteps, 0, 0))
     return set_err("rs_step_raw: NLayers = 15, fp64, no output depth and an output window below 4 GiB per stream only");
   const bool coupled = pl->c.use_coupling != 0;
   if (coupled && (!pp->coupling_index || !pp->coupling_tsurf))
@@ -949,27 +950,20 @@ int rs_step_raw(RsPlan *pl, const rs::RawForcing *raw, const double *sun, const 
   if (raw->seg0 < 0 || raw->seg0 >= raw->nseg) return set_err("rs_step_raw: seg0 outside the segment table");
   HIP_OK(hipSetDevice(pl->device));
   rs::StepArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.consts = pl->consts_dev;
+  step_args(pl, o, pp, t0, nsteps, a);
   a.f.t_stride = pl->np_pad; /* no window: nothing of `f` but the sun rows is read */
   a.f.sun = sun;
-  a.o = *o;
-  a.pp = *pp;
-  a.state = pl->state;
-  a.npoints = pl->npoints;
-  a.np_pad = pl->np_pad;
-  a.t0 = t0;
-  a.nsteps = nsteps;
-  a.wave_start = pl->wave_tab_valid ? pl->wave_tab : nullptr;
-  a.wave_cnt = pl->wave_tab_valid ? pl->wave_tab + pl->wave_n : nullptr;
-  a.wave_n = pl->wave_n;
-  a.duo_full_ok = 3; /* the driver's series always carry a dew point (completed from the humidity where absent) */
-  a.surface_prio = underfilled(pl);
+  wave_args(pl, a);
+  a.knots_tdew = 2; /* the driver's series always carry a dew point (completed from the humidity where absent) */
   a.raw = *raw;
-  a.diag = nullptr;
   /* out_by_point: the rows of slot s go to column order[s] of `o` (scattered stores: meant for decimated rows) */
   a.out_index = (out_by_point && pl->order) ? pl->order : nullptr;
-  const hipError_t le = rs_launch_step_duo_raw(a, pl->history_score, sky, coupled, pl->stream);
+  rs::StepShape s;
+  s.src = rs::StepSource::RAW;
+  s.full = true;
+  s.sky = sky;
+  s.cpl = coupled ? rs::StepCoupling::CHUNK : rs::StepCoupling::NONE;
+  const hipError_t le = launch_step(pl, a, s);
   if (le != hipSuccess) return set_err("rs_step_raw: kernel launch failed: %s", hipGetErrorString(le));
   return 0;
 }
@@ -989,25 +983,15 @@ int rs_cpl_replay_raw(RsPlan *pl, const rs::RawForcing *raw, const RsOutputs *o,
     return set_err("rs_cpl_replay_raw: all six output streams are required");
   if (t0 < 1 || nsteps < 1 || (int64_t)t0 + nsteps - 1 >= pl->c.SimLen)
     return set_err("rs_cpl_replay_raw: the block [%d,%d] must lie inside [1, SimLen - 1]", t0, t0 + nsteps - 1);
-  const int64_t out_rows = ((int64_t)t0 + nsteps - 2) / o->decimate - o->row0 + 1;
-  if ((uint64_t)o->t_stride * (uint64_t)(out_rows > 0 ? out_rows : 1) >= rs_a32_limit())
+  if (!window_a32(o, t0, nsteps, 0, 0))
     return set_err("rs_cpl_replay_raw: output window of 4 GiB per stream or more");
   if (raw->seg0 < 0 || raw->seg0 >= raw->nseg) return set_err("rs_cpl_replay_raw: seg0 outside the segment table");
   HIP_OK(hipSetDevice(pl->device));
   rs::StepArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.consts = pl->consts_dev;
+  step_args(pl, o, pp, t0, nsteps, a);
   a.f.t_stride = pl->np_pad;
-  a.o = *o;
-  a.pp = *pp;
-  a.state = pl->state;
-  a.npoints = pl->npoints;
-  a.np_pad = pl->np_pad;
-  a.t0 = t0;
-  a.nsteps = nsteps;
-  a.duo_full_ok = 3;
+  a.knots_tdew = 2;
   a.raw = *raw;
-  a.diag = nullptr;
   a.out_index = (out_by_point && pl->order) ? pl->order : nullptr;
   { /* the block must cover the coupling windows of the points that replay (as rs_hip_cpl_replay checks) */
     if (!pl->cpl_list) {
@@ -1026,7 +1010,11 @@ int rs_cpl_replay_raw(RsPlan *pl, const rs::RawForcing *raw, const RsOutputs *o,
       return set_err("rs_cpl_replay_raw: the block [%d,%d] does not cover the coupling windows of the points that "
                      "replay, [%d,%d]", t0, t0 + nsteps - 1, b[0], b[1] + 1);
   }
-  if (cpl_replay_rounds(pl, a, true, true)) return -1;
+  rs::StepShape s;
+  s.src = rs::StepSource::RAW;
+  s.full = true;
+  s.cpl = rs::StepCoupling::REPLAY;
+  if (cpl_replay_rounds(pl, a, s)) return -1;
   if (rounds) *rounds = pl->cpl_rounds_last;
   return 0;
 }
@@ -1061,31 +1049,10 @@ static int cpl_args(RsPlan *pl, const RsForcing *f, const RsOutputs *o, const Rs
   if (o->t_stride < pl->npoints || o->decimate < 1) return set_err("%s: bad output window", who);
   if (t0 < 1 || nsteps < 1 || (int64_t)t0 + nsteps - 1 > pl->c.SimLen)
     return set_err("%s: window [%d,%d) outside [1,SimLen=%d]", who, t0, t0 + nsteps, pl->c.SimLen);
-  a.consts = pl->consts_dev;
+  step_args(pl, o, pp, t0, nsteps, a);
   a.f = *f;
-  a.o = *o;
-  a.pp = *pp;
-  a.state = pl->state;
-  a.npoints = pl->npoints;
-  a.np_pad = pl->np_pad;
-  a.t0 = t0;
-  a.nsteps = nsteps;
-  a.wb = rs::Writeback{nullptr, nullptr, nullptr, 0};
-  a.cpl_list = nullptr;
-  a.cpl_nlist = 0;
-  a.cpl_stop = 0;
-  a.cpl_inner = a.cpl_prio = 0;
   a.out_index = (pl->output_by_point && pl->order) ? pl->order : nullptr;
-  a.wave_start = a.wave_cnt = nullptr;
-  a.wave_n = 0;
-  a.duo_full_ok = 0;
-  a.surface_prio = 0;
-  a.diag = nullptr; /* (the lock-step coupling launches have no instance with diagnostics) */
-  a.knots = nullptr;
-  a.knot_gather = nullptr;
-  a.knot_k0 = a.knot_n = a.spk = a.start_hour = 0;
-  a.r_spk = 0.0;
-  std::memset(&a.raw, 0, sizeof(a.raw));
+  /* (no write-back, wave table or diagnostics: the lock-step coupling launches have no instance with diagnostics) */
   return 0;
 }
 
@@ -1094,7 +1061,11 @@ int rs_hip_step_cpl(RsPlan *pl, const RsForcing *f, const RsOutputs *o, const Rs
   rs::StepArgs a;
   if (cpl_args(pl, f, o, pp, t0, nsteps, "rs_hip_step_cpl", a)) return -1;
   HIP_OK(hipSetDevice(pl->device));
-  HIP_OK(rs_launch_step_cpl(a, pl->c.NLayers, pl->stream));
+  rs::StepShape s;
+  s.full = true;
+  s.sky = pp->sky_view != nullptr;
+  s.cpl = rs::StepCoupling::CHUNK;
+  HIP_OK(launch_step(pl, a, s));
   return 0;
 }
 
@@ -1135,7 +1106,11 @@ int rs_hip_cpl_replay(RsPlan *pl, const RsForcing *f, const RsOutputs *o, const 
                        t0, t0 + nsteps - 1, b[0], need_hi);
     }
   }
-  if (cpl_replay_rounds(pl, a, lockstep)) return -1;
+  rs::StepShape s;
+  s.full = true;
+  s.sky = pp->sky_view != nullptr;
+  s.cpl = lockstep ? rs::StepCoupling::REPLAY : rs::StepCoupling::GENERAL;
+  if (cpl_replay_rounds(pl, a, s)) return -1;
   if (rounds) *rounds = pl->cpl_rounds_last;
   return 0;
 }

@@ -1,21 +1,12 @@
 /* rs_kernels.h — kernel argument blocks and host launchers (internal). */
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cstddef>
+#include <type_traits>
 #include "../../include/roadsurf.h"
 #include "rs_synth.h"
 #include "rs_raw.hpp"
-
-#define RS_BLOCK 256
-
-enum { RS_VARIANT_AUTO = 0, RS_VARIANT_REG = 1, RS_VARIANT_LDS = 2, RS_VARIANT_DUO = 3, RS_VARIANT_HYBRID = 4 };
-/* AUTO takes the two-wavefronts-per-64-points flavour for launches of at most this many points:
- * 1 024 wavefronts, a quarter of the chip's slots (measured, tools/r3_duo.sh: two plans of 62 500
- * points 1.13e10 against 1.06e10 point-timesteps/s with one point per lane; four such plans in
- * flight at once are better off with one point per lane - a caller that runs that many sets the
- * flavour itself, as bench.py does) */
-#ifndef RS_DUO_MAX_POINTS
-#define RS_DUO_MAX_POINTS 65536
-#endif
+#include "rs_step_select.hpp"
 
 namespace rs {
 
@@ -26,55 +17,65 @@ struct Writeback {
   int64_t t_stride;
 };
 
+/* Every field defaults to null / zero: an entry point sets what its launch uses (rs_api.hip).  The kernels read the
+ * block as their kernel argument: its layout is pinned below. */
 struct StepArgs {
-  const void *consts; /* the plan's constants in HBM: RsConstants (fp64 kernels) or RsConstantsF
-                         (fp32 kernels); read through the scalar cache (address space 4) */
-  RsForcing f;
-  RsOutputs o;
-  RsPointParams pp;
-  double *state;
-  int64_t npoints, np_pad;
-  int32_t t0, nsteps;
-  Writeback wb;
+  const void *consts = nullptr; /* the plan's constants in HBM: RsConstants (fp64 kernels) or RsConstantsF
+                                   (fp32 kernels); read through the scalar cache (address space 4) */
+  RsForcing f{};
+  RsOutputs o{};
+  RsPointParams pp{};
+  double *state = nullptr;
+  int64_t npoints = 0, np_pad = 0;
+  int32_t t0 = 0, nsteps = 0;
+  Writeback wb{};
   /* coupling rounds (step_kernel_coupled): thread g works on point cpl_list[g] (NULL: point g);
    * cpl_stop: a point parks right after the Coupling_control of its window end */
-  const int32_t *cpl_list;
-  int32_t cpl_nlist, cpl_stop;
+  const int32_t *cpl_list = nullptr;
+  int32_t cpl_nlist = 0, cpl_stop = 0;
   /* lock-step replay kernels: a listed point may run up to this many replays of its window in ONE
    * launch, until its Coupling_control stops asking (0 or 1: one replay, the round structure of
    * rs_hip_cpl_replay); cpl_prio: raise the wavefronts' issue priority (a sparse late round beside
    * another plan's full launches runs at the speed of its own dependency chain) */
-  int32_t cpl_inner, cpl_prio;
+  int32_t cpl_inner = 0, cpl_prio = 0;
   /* coupling kernels: the outputs of slot s go to column out_index[s] of the output window
    * (NULL: column s).  With the plan order as index the (decimated) outputs land in point order
    * whatever order the slots are in (rs_hip_set_output_by_point). */
-  const int32_t *out_index;
+  const int32_t *out_index = nullptr;
   /* two-wavefront flavour: wavefront w steps the slots [wave_start[w], wave_start[w] + wave_cnt[w]) and the
    * launch has wave_n workgroups (rs_cluster_wave_table: no wavefront mixes two classes of the sort key);
    * NULL: wavefront w steps the slots 64 w ... */
-  const int32_t *wave_start, *wave_cnt;
-  int32_t wave_n;
-  /* the launch's FULL feature set is one the two-wavefront flavour has (rs_hip_step: no sky view, no
-   * coupling, no depth stream, no tsurfOutputDepth) */
-  int32_t duo_full_ok;
+  const int32_t *wave_start = nullptr, *wave_cnt = nullptr;
+  int32_t wave_n = 0;
+  /* knot-reading kernels: bit 1 (& 2) set - the knots carry a dew point, run CheckValues' dew-point test */
+  int32_t knots_tdew = 0;
   /* two-wavefront flavour: the surface wave runs at raised issue priority (rs_api.hip: set while all live
    * plans of the device together leave its SIMDs underfilled) */
-  int32_t surface_prio;
+  int32_t surface_prio = 0;
   /* two-wavefront flavour on the synthetic workload (rs_hip_step_knots): no forcing window - the ground
    * wave makes the forcing of the next index from the hourly knots itself, with expand_kernel's arithmetic
    * (knots [knot - knot_k0][RS_KNOT_FIELDS][np_pad] in point order, column knot_gather[slot]; NULL knots:
    * the window `f`) */
-  const double *knots;
-  const int32_t *knot_gather;
-  int32_t knot_k0, knot_n, spk, start_hour;
-  double r_spk;
+  const double *knots = nullptr;
+  const int32_t *knot_gather = nullptr;
+  int32_t knot_k0 = 0, knot_n = 0, spk = 0, start_hour = 0;
+  double r_spk = 0.0;
   /* two-wavefront flavour behind rs_driver_run (rs_step_raw): no forcing window either - the ground wave
    * makes the forcing of the next index from the RAW series (JsonSource::interpolate + the GetWeather
    * overlay, rs_raw.hpp); raw.nsrc = 0: not this launch */
-  RawForcing raw;
+  RawForcing raw{};
   /* the plan's diagnostics block (rs_hip_set_diagnostics; rs_state.h RsDiagRow), or NULL */
-  double *diag;
+  double *diag = nullptr;
 };
+static_assert(std::is_trivially_copyable<StepArgs>::value, "StepArgs is a kernel argument");
+static_assert(sizeof(StepArgs) == 912 && offsetof(StepArgs, f) == 8 && offsetof(StepArgs, o) == 136 &&
+                  offsetof(StepArgs, pp) == 208 && offsetof(StepArgs, state) == 328 && offsetof(StepArgs, t0) == 352 &&
+                  offsetof(StepArgs, wb) == 360 && offsetof(StepArgs, cpl_list) == 392 &&
+                  offsetof(StepArgs, out_index) == 416 && offsetof(StepArgs, wave_n) == 440 &&
+                  offsetof(StepArgs, knots_tdew) == 444 && offsetof(StepArgs, surface_prio) == 448 &&
+                  offsetof(StepArgs, knots) == 456 && offsetof(StepArgs, r_spk) == 488 &&
+                  offsetof(StepArgs, raw) == 496 && offsetof(StepArgs, diag) == 904,
+              "the kernels' view of StepArgs");
 
 struct InitArgs {
   const void *consts;
@@ -127,16 +128,9 @@ hipError_t rs_launch_humidity_fill(const double *tair, double *tdew, double *rhz
                                    hipStream_t stream);
 /* exp/log tables of the device (same for every plan) */
 hipError_t rs_upload_math_tables(hipStream_t stream);
-hipError_t rs_launch_step(const rs::StepArgs &a, int NL, bool full, int variant, bool score,
-                          hipStream_t stream);
-/* the two-wavefront flavour with the forcing made from the knots in the kernel (StepArgs::knots) */
-hipError_t rs_launch_step_duo_knots(const rs::StepArgs &a, bool score, hipStream_t stream);
-/* ... and from the raw series of the driver path (StepArgs::raw); sky: per-point sky view on the ground wave */
-hipError_t rs_launch_step_duo_raw(const rs::StepArgs &a, bool score, bool sky, bool cpl, hipStream_t stream);
-/* the step of rs_driver_run's blocks (rs_api.hip): NLayers = 15, fp64, no output depth; pp in SLOT order, raw
- * series in point order behind raw.col.  A coupled plan (use_coupling, pp->coupling_index): a LOCK-STEP chunk as
- * rs_hip_step_cpl runs it - points park behind their coupling window until rs_hip_cpl_replay has run. */
-hipError_t rs_launch_step_duo_raw_replay(const rs::StepArgs &a, hipStream_t stream);
+/* the step kernel rs::select_step chose (rs_step_select.hpp), with its grid, workgroup and dynamic LDS: the fp64
+ * instances here, the fp32 ones in rs_kernels_f32.hip; hipErrorInvalidValue for an instance of the other precision */
+hipError_t rs_launch_step(const rs::StepArgs &a, const rs::StepLaunch &l, hipStream_t stream);
 struct RsPlan;
 /* the replay rounds of a coupled plan whose lock-step chunks run through rs_step_raw: as rs_hip_cpl_replay, the
  * forcing of the block [t0, t0 + nsteps) from the raw series (no sky view; the block must end before SimLen) */
@@ -148,11 +142,11 @@ int rs_cpl_replay_raw(RsPlan *pl, const rs::RawForcing *raw, const RsOutputs *o,
  * windows of megabytes instead of gigabytes. */
 uint64_t rs_a32_limit(void);
 bool rs_step_raw_ok(const RsPlan *pl); /* a plan whose settings rs_step_raw can run */
+/* the step of rs_driver_run's blocks (rs_api.hip): NLayers = 15, fp64, no output depth; pp in SLOT order, raw
+ * series in point order behind raw.col.  A coupled plan (use_coupling, pp->coupling_index): a LOCK-STEP chunk as
+ * rs_hip_step_cpl runs it - points park behind their coupling window until rs_hip_cpl_replay has run. */
 int rs_step_raw(RsPlan *pl, const rs::RawForcing *raw, const double *sun, const RsOutputs *o,
                 const RsPointParams *pp, int32_t t0, int32_t nsteps, bool out_by_point);
-hipError_t rs_launch_step_cpl_replay(const rs::StepArgs &a, int NL, hipStream_t stream);
-hipError_t rs_launch_step_coupled(const rs::StepArgs &a, int NL, hipStream_t stream);
-hipError_t rs_launch_step_cpl(const rs::StepArgs &a, int NL, hipStream_t stream);
 /* out[2] (device): min couplingStartI / max couplingEndI over the points that ask for a replay */
 hipError_t rs_launch_cpl_window_bounds(const rs::StepArgs &a, int32_t *out, hipStream_t stream);
 /* list of the points whose coupling asks for another replay (start_coupling_again): list[0..*count) */
@@ -160,7 +154,6 @@ size_t rs_cpl_select_scratch_bytes(int64_t npoints);
 hipError_t rs_cpl_select_again(const double *state, int64_t np_pad, int64_t npoints, int32_t *flags,
                                int32_t *list, int32_t *count_dev, void *tmp, size_t tmp_bytes,
                                hipStream_t stream);
-hipError_t rs_launch_step_sky(const rs::StepArgs &a, int NL, bool score, hipStream_t stream);
 hipError_t rs_launch_init(const rs::InitArgs &a, hipStream_t stream);
 hipError_t rs_launch_knots(const rs::KnotArgs &a, int32_t nknots, hipStream_t stream);
 hipError_t rs_launch_expand(const rs::ExpandArgs &a, int32_t nintervals, hipStream_t stream);
@@ -205,8 +198,6 @@ hipError_t rs_cluster_apply(const double *state_src, double *state_dst, bool f32
 /* single-precision mirror of the constants: fills *dst (device, rs32_constants_bytes() bytes) */
 size_t rs32_constants_bytes(void);
 hipError_t rs32_upload_constants(void *dst, const RsConstants *c, hipStream_t stream);
-hipError_t rs32_launch_step(const rs::StepArgs &a, int NL, int variant, bool score, bool full, bool sky, hipStream_t stream);
-hipError_t rs32_launch_step_coupled(const rs::StepArgs &a, int NL, hipStream_t stream);
-hipError_t rs32_launch_step_knots(const rs::StepArgs &a, bool score, bool full, hipStream_t stream);
+hipError_t rs32_launch_step(const rs::StepArgs &a, const rs::StepLaunch &l, hipStream_t stream);
 hipError_t rs32_launch_init(const rs::InitArgs &a, hipStream_t stream);
 hipError_t rs32_launch_expand(const rs::ExpandArgs &a, int32_t nintervals, hipStream_t stream);

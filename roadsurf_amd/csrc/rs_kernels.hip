@@ -1192,7 +1192,7 @@ __device__ __forceinline__ double bl_score_key(int32_t score, const Scalars &s) 
   return (double)(lo | (covered << 19) | (((score >> 30) & 1) << 20));
 }
 
-/* (waves per SIMD: LEAN four, FULL three - measured, rs_launch_step; the choice was a digit of the variant until
+/* (waves per SIMD: LEAN four, FULL three - measured, rs_step_select.hpp; the choice was a digit of the variant until
  * round 6) */
 template <int NL, bool FULL, bool SCORE = true, bool A32 = false>
 __global__ void __launch_bounds__(kBlock, FULL ? 3 : 4) step_kernel_reg(const StepArgs a) {
@@ -2046,7 +2046,7 @@ __device__ __forceinline__ void duo_ground(const MathTab &mt, DuoMailT<FULL ? PR
   auto prep = [&](const ConstsAS &c, const Forcing &f, int32_t in, double &obs) -> ForcingPrep {
     if (!FULL) return forcing_prep(c, mt, f, in, in < c.SimLen);
     bool bad;
-    const bool has_tdew = RAW ? true : KNOTS ? (ka->duo_full_ok & 2) != 0 : ka->f.tdew != nullptr;
+    const bool has_tdew = RAW ? true : KNOTS ? (ka->knots_tdew & 2) != 0 : ka->f.tdew != nullptr;
     double vz = forcing_prep_head(c, f, in, in < c.SimLen, has_tdew, bad);
     double tair = f.tair, rhz = f.rhz;
     obs = R4(-9999.9);
@@ -2310,7 +2310,7 @@ __global__ void __launch_bounds__(kBlock, 3) step_kernel_sky(const StepArgs a) {
   a.state[(int64_t)RS_ST_BLSCORE * a.np_pad + p] = bl_score_key(score, s);
 }
 
-/* The same for NLayers = 15 with the hybrid profile at W waves per SIMD (rs_launch_step_sky). */
+/* The same for NLayers = 15 with the hybrid profile at W waves per SIMD (rs_step_select.hpp). */
 template <int W>
 __global__ void __launch_bounds__(kBlock, W) step_kernel_sky_h(const StepArgs a) {
   __shared__ double math_lds[RS_MATH_LDS_DOUBLES];
@@ -2954,150 +2954,13 @@ hipError_t rs_launch_forecast_keys(const rs::ForecastArgs &a, hipStream_t stream
   return hipGetLastError();
 }
 
-hipError_t rs_launch_step_sky(const rs::StepArgs &a, int NL, bool score, hipStream_t stream) {
-  const size_t lds = (size_t)NL * RS_BLOCK * sizeof(double);
-  /* NLayers = 15: the hybrid profile at four waves per SIMD (measured, rs_driver_run with sky view, 262 144 points
-   * in four blocks: LDS profile at three waves 6.9e9, hybrid at three 7.1e9, at four 7.4e9); other layer counts:
-   * the LDS profile.
-   * Two wavefronts per 64 points (no output depth, 32-bit window offsets: what rs_hip_step checked, StepArgs::
-   * duo_full_ok bit 2) - no spills (128 registers) where the one-point-per-lane sky kernels spill 62-106 - for
-   * launches of at most RS_DUO_MAX_POINTS points, like the other two-wavefront instances: rs_driver_run with sky
-   * view, 65 536 points 3.5e9 -> 4.8e9, 200 000 points (four blocks) 7.6e9 -> 8.6e9; at 1 M points (blocks of
-   * 250 000) 1.06e10 -> 1.03e10 - four of its wavefronts leave a SIMD no register for the other blocks' window
-   * expansion, which then queues. */
-  if (NL == 15 && a.npoints <= RS_DUO_MAX_POINTS && (a.duo_full_ok & 4) && !a.diag) {
-    const dim3 gd(a.wave_start ? (unsigned)a.wave_n : (unsigned)((a.npoints + 63) / 64));
-    if (score) hipLaunchKernelGGL((rs::step_kernel_duo<15, true, rs::SRC_WINDOW, true, true>), gd, dim3(128), 0, stream, a);
-    else hipLaunchKernelGGL((rs::step_kernel_duo<15, false, rs::SRC_WINDOW, true, true>), gd, dim3(128), 0, stream, a);
-    return hipGetLastError();
-  }
-  /* (a plan with diagnostics: the instance that carries bl_diagnose - here and below) */
-  if (a.diag) hipLaunchKernelGGL(rs::step_kernel_sky<true>, grid_for(a.npoints), dim3(RS_BLOCK), lds, stream, a);
-  else if (NL == 15) hipLaunchKernelGGL((rs::step_kernel_sky_h<4>), grid_for(a.npoints), dim3(RS_BLOCK), 0, stream, a);
-  else hipLaunchKernelGGL(rs::step_kernel_sky<false>, grid_for(a.npoints), dim3(RS_BLOCK), lds, stream, a);
-  return hipGetLastError();
-}
-
-
-hipError_t rs_launch_step_duo_knots(const rs::StepArgs &a, bool score, hipStream_t stream) {
-  const dim3 gd(a.wave_start ? (unsigned)a.wave_n : (unsigned)((a.npoints + 63) / 64));
-  const bool full = (a.duo_full_ok & 1) != 0;
-  if (full && score) hipLaunchKernelGGL((rs::step_kernel_duo<15, true, rs::SRC_KNOTS, true>), gd, dim3(128), 0, stream, a);
-  else if (full) hipLaunchKernelGGL((rs::step_kernel_duo<15, false, rs::SRC_KNOTS, true>), gd, dim3(128), 0, stream, a);
-  else if (score) hipLaunchKernelGGL((rs::step_kernel_duo<15, true, rs::SRC_KNOTS>), gd, dim3(128), 0, stream, a);
-  else hipLaunchKernelGGL((rs::step_kernel_duo<15, false, rs::SRC_KNOTS>), gd, dim3(128), 0, stream, a);
-  return hipGetLastError();
-}
-
-hipError_t rs_launch_step_duo_raw(const rs::StepArgs &a, bool score, bool sky, bool cpl, hipStream_t stream) {
-  const dim3 gd(a.wave_start ? (unsigned)a.wave_n : (unsigned)((a.npoints + 63) / 64));
-  if (cpl) { /* lock-step chunk of a coupled plan (rs_step_raw with coupling): the history score is kept */
-    if (sky) hipLaunchKernelGGL((rs::step_kernel_duo<15, true, rs::SRC_RAW, true, true, true>), gd, dim3(192), 0, stream, a);
-    else hipLaunchKernelGGL((rs::step_kernel_duo<15, true, rs::SRC_RAW, true, false, true>), gd, dim3(128), 0, stream, a);
-    return hipGetLastError();
-  }
-  if (sky && score) hipLaunchKernelGGL((rs::step_kernel_duo<15, true, rs::SRC_RAW, true, true>), gd, dim3(192), 0, stream, a);
-  else if (sky) hipLaunchKernelGGL((rs::step_kernel_duo<15, false, rs::SRC_RAW, true, true>), gd, dim3(192), 0, stream, a);
-  else if (score) hipLaunchKernelGGL((rs::step_kernel_duo<15, true, rs::SRC_RAW, true>), gd, dim3(128), 0, stream, a);
-  else hipLaunchKernelGGL((rs::step_kernel_duo<15, false, rs::SRC_RAW, true>), gd, dim3(128), 0, stream, a);
-  return hipGetLastError();
-}
-
-/* one replay round of the coupling windows over the listed points, forcing from the raw series */
-hipError_t rs_launch_step_duo_raw_replay(const rs::StepArgs &a, hipStream_t stream) {
-  if (!a.cpl_list || a.cpl_nlist < 1) return hipSuccess;
-  const dim3 gd((unsigned)((a.cpl_nlist + 63) / 64));
-  hipLaunchKernelGGL((rs::step_kernel_duo<15, true, rs::SRC_RAW, true, false, true, true>), gd, dim3(128), 0, stream, a);
-  return hipGetLastError();
-}
-
-hipError_t rs_launch_step_cpl(const rs::StepArgs &a, int NL, hipStream_t stream) {
-  /* NLayers = 15: the hybrid profile at three waves per SIMD (measured, tools/r3_cpl.sh, rs_driver_run with
-   * coupling, 1 M points: 7.75e9; LDS profile at 3 waves 7.0e9, hybrid at 4 waves - spills - 6.6e9; a profile wholly
-   * in registers was twice as slow); other layer counts: the LDS profile */
-  const size_t lds = (size_t)NL * RS_BLOCK * sizeof(double);
-  const dim3 g = grid_for(a.npoints);
-  if (NL == 15 && a.pp.sky_view) hipLaunchKernelGGL((rs::step_kernel_cpl_h<3, true>), g, dim3(RS_BLOCK), 0, stream, a);
-  else if (NL == 15) hipLaunchKernelGGL((rs::step_kernel_cpl_h<3, false>), g, dim3(RS_BLOCK), 0, stream, a);
-  else if (a.pp.sky_view) hipLaunchKernelGGL(rs::step_kernel_cpl<true>, g, dim3(RS_BLOCK), lds, stream, a);
-  else hipLaunchKernelGGL(rs::step_kernel_cpl<false>, g, dim3(RS_BLOCK), lds, stream, a);
-  return hipGetLastError();
-}
-
-hipError_t rs_launch_step_cpl_replay(const rs::StepArgs &a, int NL, hipStream_t stream) {
-  if (!a.cpl_list || a.cpl_nlist < 1) return hipSuccess;
-  const size_t lds = (size_t)NL * RS_BLOCK * sizeof(double);
-  const dim3 g = grid_for(a.cpl_nlist);
-  if (NL == 15 && a.pp.sky_view) hipLaunchKernelGGL((rs::step_kernel_cpl_replay_h<3, true>), g, dim3(RS_BLOCK), 0, stream, a);
-  else if (NL == 15) hipLaunchKernelGGL((rs::step_kernel_cpl_replay_h<3, false>), g, dim3(RS_BLOCK), 0, stream, a);
-  else if (a.pp.sky_view) hipLaunchKernelGGL(rs::step_kernel_cpl_replay<true>, g, dim3(RS_BLOCK), lds, stream, a);
-  else hipLaunchKernelGGL(rs::step_kernel_cpl_replay<false>, g, dim3(RS_BLOCK), lds, stream, a);
-  return hipGetLastError();
-}
-
-hipError_t rs_launch_step_coupled(const rs::StepArgs &a, int NL, hipStream_t stream) {
-  const size_t lds = (size_t)NL * RS_BLOCK * sizeof(double);
-  const int64_t n = a.cpl_list ? (int64_t)a.cpl_nlist : a.npoints;
-  if (n < 1) return hipSuccess;
-  if (a.diag) hipLaunchKernelGGL(rs::step_kernel_coupled<true>, grid_for(n), dim3(RS_BLOCK), lds, stream, a);
-  else hipLaunchKernelGGL(rs::step_kernel_coupled<false>, grid_for(n), dim3(RS_BLOCK), lds, stream, a);
-  return hipGetLastError();
-}
-
-hipError_t rs_launch_step(const rs::StepArgs &a, int NL, bool full, int variant, bool score,
-                          hipStream_t stream) {
-  const dim3 g = grid_for(a.npoints), b(RS_BLOCK);
-  const bool auto_variant = variant == RS_VARIANT_AUTO;
-  /* measured (tools/r3_full2.sh, 1 M points): FULL feature set - layers 8-15 in LDS at 4 waves/SIMD
-   * 1.36e10, all in registers at 3 waves/SIMD (167 VGPRs) 1.34e10, at 4 waves (14 doubles spilled)
-   * 1.23e10, all in LDS 1.28e10.  LEAN: registers, 4 waves.  (tools/bench_driver_path.py relax, 1 M points, one
-   * plan: the FULL feature set in the register flavour at 3 waves/SIMD 0.745 s, at 2 waves 0.80 s, at 4 waves -
-   * 130 spilled VGPRs - 0.87 s; with the profile in LDS 0.86 s (3 waves) / 0.88 s (4 waves).)  The waves-per-SIMD
-   * bound was a digit of the variant until round 6; the measured choices are the kernels' launch bounds now. */
-  if (a.diag) variant = RS_VARIANT_LDS;
-  else if (auto_variant) variant = (NL != 15) ? RS_VARIANT_LDS : full ? RS_VARIANT_HYBRID : RS_VARIANT_REG;
-  /* 32-bit window offsets (WinOff) where every stream of both windows spans < 4 GiB (rs_a32_limit: the tests
-   * lower it to reach the 64-bit instances with windows of megabytes) */
-  const int64_t out_rows = ((int64_t)a.t0 + a.nsteps - 2) / a.o.decimate - a.o.row0 + 1;
-  const bool a32 = (uint64_t)a.f.t_stride * (uint64_t)a.nsteps < rs_a32_limit() &&
-                   (uint64_t)a.o.t_stride * (uint64_t)(out_rows > 0 ? out_rows : 1) < rs_a32_limit();
-  /* small shards: two wavefronts per 64 points (step_kernel_duo).  Measured on MI355X (tools/r3_eval.sh): faster
-   * than one point per lane below RS_DUO_MAX_POINTS points per launch */
-  const bool duo_ok = (!full || a.duo_full_ok) && NL == 15 && a32;
-  if (variant == RS_VARIANT_DUO && !duo_ok) { /* not this launch: as AUTO */
-    variant = (NL != 15) ? RS_VARIANT_LDS : full ? RS_VARIANT_HYBRID : RS_VARIANT_REG;
-  } else if (variant == RS_VARIANT_DUO || (auto_variant && !a.diag && duo_ok && a.npoints <= RS_DUO_MAX_POINTS)) {
-    const dim3 gd(a.wave_start ? (unsigned)a.wave_n : (unsigned)((a.npoints + 63) / 64));
-    if (full && score) hipLaunchKernelGGL((rs::step_kernel_duo<15, true, rs::SRC_WINDOW, true>), gd, dim3(128), 0, stream, a);
-    else if (full) hipLaunchKernelGGL((rs::step_kernel_duo<15, false, rs::SRC_WINDOW, true>), gd, dim3(128), 0, stream, a);
-    else if (score) hipLaunchKernelGGL((rs::step_kernel_duo<15, true>), gd, dim3(128), 0, stream, a);
-    else hipLaunchKernelGGL((rs::step_kernel_duo<15, false>), gd, dim3(128), 0, stream, a);
-    return hipGetLastError();
-  }
-  if (variant == RS_VARIANT_HYBRID && (NL != 15 || !full)) /* not this launch: as AUTO */
-    variant = (NL == 15) ? RS_VARIANT_REG : RS_VARIANT_LDS;
-  if (variant == RS_VARIANT_HYBRID) {
-#define RS_HYB(S, A) \
-  if (score == S && a32 == A) hipLaunchKernelGGL((rs::step_kernel_hybrid<S, A>), g, b, 0, stream, a);
-    RS_HYB(false, false) RS_HYB(false, true) RS_HYB(true, false) RS_HYB(true, true)
-#undef RS_HYB
-    return hipGetLastError();
-  }
-  if (variant == RS_VARIANT_REG) {
-    if (NL != 15) return hipErrorInvalidValue;
-#define RS_REG(F, S, A) \
-  if (full == F && score == S && a32 == A) hipLaunchKernelGGL((rs::step_kernel_reg<15, F, S, A>), g, b, 0, stream, a);
-#define RS_REG_A(F, S) RS_REG(F, S, false) RS_REG(F, S, true)
-    RS_REG_A(false, true) RS_REG_A(false, false) RS_REG_A(true, true) RS_REG_A(true, false)
-#undef RS_REG_A
-#undef RS_REG
-  } else {
-    const size_t lds = (size_t)NL * RS_BLOCK * sizeof(double);
-    /* (diagnostics: the FULL instance whatever the launch's feature set - it reads a missing optional stream as
-     * "no value" and is exact for a LEAN launch too) */
-    if (a.diag) hipLaunchKernelGGL((rs::step_kernel_lds<true, true>), g, b, lds, stream, a);
-    else if (full) hipLaunchKernelGGL((rs::step_kernel_lds<true>), g, b, lds, stream, a);
-    else hipLaunchKernelGGL((rs::step_kernel_lds<false>), g, b, lds, stream, a);
+hipError_t rs_launch_step(const rs::StepArgs &a, const rs::StepLaunch &l, hipStream_t stream) {
+  switch (l.kernel) {
+#define RS_STEP_CASE(id, ...) \
+  case rs::StepKernel::id: hipLaunchKernelGGL((__VA_ARGS__), dim3(l.grid), dim3(l.block), l.lds, stream, a); break;
+    RS_STEP_KERNELS_F64(RS_STEP_CASE)
+#undef RS_STEP_CASE
+    default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
 }

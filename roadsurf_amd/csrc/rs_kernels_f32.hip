@@ -815,7 +815,7 @@ __device__ __forceinline__ void x2d_ground(X2Mail &mail, const rs::StepArgs &a) 
       hour_u = rs_sy_hour(in, spk, ka->start_hour);
       if (FULL) { /* expand_kernel_f32: the dew point like the others, the observation at index 1 only */
         tdew = fma2(w, kdv[NK - 1], kv0[NK - 1]);
-        has_tdew = (ka->duo_full_ok & 2) != 0;
+        has_tdew = (ka->knots_tdew & 2) != 0;
         if (t == 0) {
           const double *k7 = ka->knots + ((int64_t)(kk - ka->knot_k0) * RS_KNOT_FIELDS + 7) * np;
           tsobs = f2{(float)k7[kcolx], (float)k7[kcoly]};
@@ -1689,51 +1689,14 @@ hipError_t rs32_upload_constants(void *dst, const RsConstants *c, hipStream_t st
   return hipStreamSynchronize(stream); /* f is stack scratch */
 }
 
-static inline dim3 grid_x2(int64_t n) { return dim3((unsigned)((n + 127) / 128)); } /* a workgroup steps 128 points */
-
-#define RS32_DUO(SRC)                                                                                                  \
-  do {                                                                                                                 \
-    const dim3 g2 = grid_x2(a.npoints);                                                                                \
-    if (full && score) hipLaunchKernelGGL((rs32::step_kernel_f32duo<SRC, true, true>), g2, dim3(128), 0, stream, a);   \
-    else if (full) hipLaunchKernelGGL((rs32::step_kernel_f32duo<SRC, false, true>), g2, dim3(128), 0, stream, a);      \
-    else if (score) hipLaunchKernelGGL((rs32::step_kernel_f32duo<SRC, true, false>), g2, dim3(128), 0, stream, a);     \
-    else hipLaunchKernelGGL((rs32::step_kernel_f32duo<SRC, false, false>), g2, dim3(128), 0, stream, a);               \
-  } while (0)
-
-/* full: the launch carries the FULL feature set (dew point, observation forcing, relaxation): the two-points-per-lane
- * kernel only (NLayers = 15); sky: and per-point sky view (a window with SW_dir and LW_net, the sun table) */
-hipError_t rs32_launch_step(const rs::StepArgs &a, int NL, int variant, bool score, bool full, bool sky, hipStream_t stream) {
-  const dim3 g = grid_for32(a.npoints), b(RS_BLOCK);
-  const int v = variant;
-  if (sky) {
-    if (NL != 15) return hipErrorInvalidValue;
-    const dim3 g2 = grid_x2(a.npoints);
-    if (score) hipLaunchKernelGGL((rs32::step_kernel_f32duo<rs32::X2_WINDOW, true, true, true>), g2, dim3(128), 0, stream, a);
-    else hipLaunchKernelGGL((rs32::step_kernel_f32duo<rs32::X2_WINDOW, false, true, true>), g2, dim3(128), 0, stream, a);
-    return hipGetLastError();
+hipError_t rs32_launch_step(const rs::StepArgs &a, const rs::StepLaunch &l, hipStream_t stream) {
+  switch (l.kernel) {
+#define RS_STEP_CASE(id, ...) \
+  case rs::StepKernel::id: hipLaunchKernelGGL((__VA_ARGS__), dim3(l.grid), dim3(l.block), l.lds, stream, a); break;
+    RS_STEP_KERNELS_F32(RS_STEP_CASE)
+#undef RS_STEP_CASE
+    default: return hipErrorInvalidValue;
   }
-  if (NL == 15 && (full || (v != RS_VARIANT_REG && v != RS_VARIANT_LDS))) {
-    /* two points per lane, two wavefronts per 128 points (round 6); RS_VARIANT_REG / _LDS: round 2-5's one point
-     * per lane with the profile in LDS, for A/B (and what other layer counts take) */
-    RS32_DUO(rs32::X2_WINDOW);
-  } else {
-    if (full) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(rs32::step_kernel_f32_lds, g, b, (size_t)NL * RS_BLOCK * sizeof(float), stream, a);
-  }
-  return hipGetLastError();
-}
-
-/* the two-points-per-lane kernel reading the hourly knots itself (StepArgs::knots): no forcing window */
-hipError_t rs32_launch_step_knots(const rs::StepArgs &a, bool score, bool full, hipStream_t stream) {
-  RS32_DUO(rs32::X2_KNOTS);
-  return hipGetLastError();
-}
-#undef RS32_DUO
-
-/* the general kernel: a coupled plan's whole series (every point replays its coupling window inside the launch), or a
- * chunk of a plan without coupling whose features the two-wavefront kernels do not have */
-hipError_t rs32_launch_step_coupled(const rs::StepArgs &a, int NL, hipStream_t stream) {
-  hipLaunchKernelGGL(rs32::step_kernel_f32_coupled, grid_for32(a.npoints), dim3(RS_BLOCK), (size_t)NL * RS_BLOCK * sizeof(float), stream, a);
   return hipGetLastError();
 }
 

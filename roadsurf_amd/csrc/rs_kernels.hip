@@ -16,6 +16,8 @@
  *                        touches 8-byte word l of a 2-KiB row).
  * Each comes in a LEAN variant (no observation forcing beyond index 1, no output
  * depth, no relaxation, no Tdew check: the BASELINE workload) and a FULL variant.
+ * These, step_kernel_hybrid and the lock-step sky-view and coupling kernels
+ * (step_kernel_sky*, step_kernel_cpl*) share one body, step_lanes.
  *
  * No MFMA: there is no contraction anywhere in this path.  The time loop is
  * sequential per point (explicit Euler in time), points are independent.
@@ -1192,31 +1194,70 @@ __device__ __forceinline__ double bl_score_key(int32_t score, const Scalars &s) 
   return (double)(lo | (covered << 19) | (((score >> 30) & 1) << 20));
 }
 
+/* The profile of this lane in a one-point-per-lane kernel; `lds`: the kernel's LDS columns of the profile,
+ * [layer][lane] (none for RegProfile). */
+template <int NL>
+__device__ __forceinline__ void lane_profile(RegProfile<NL> &, double *, const StepArgs &) {}
+template <int NL, int NREG>
+__device__ __forceinline__ void lane_profile(HybridProfile<NL, NREG> &T, double *lds, const StepArgs &) {
+  T.col = lds + threadIdx.x;
+}
+__device__ __forceinline__ void lane_profile(LdsProfile &T, double *lds, const StepArgs &a) {
+  T.col = lds + threadIdx.x;
+  T.n = consts_of(&a).NLayers;
+}
+
+/* One point per lane, lock step: the body of step_kernel_reg, _hybrid, _lds, _sky, _sky_h, _cpl, _cpl_h and
+ * _cpl_replay_h (step_kernel_cpl_replay keeps a copy of its own: see there).  The workgroup fills the math tables;
+ * a lane without a point leaves (no barriers below: each lane owns its column of the profile); the lane's state is
+ * loaded, run through time_loop and stored back, and with SCORE its history score goes beside it.  The entry points
+ * differ only in the profile (Prof, set up by lane_profile), time_loop's flags and their launch bounds.  They
+ * declare the LDS themselves and pass it down (a __shared__ in a __device__ function goes through the module-LDS
+ * lowering and can move): math_lds, and prof_lds for the columns of HybridProfile / LdsProfile.
+ * REPLAY: the lane's point is its entry of the compacted list cpl_list, run at raised priority with cpl_prio, and
+ * replays its window up to cpl_inner times in this launch, as long as its Coupling_control asks for another
+ * (start_coupling_again, bit 0 of the flags it has just stored): the secant iteration of src/Coupling.f90:363-449
+ * is per point - only the launches were sequential.  The state goes through the state block between two replays
+ * exactly as it does between two rounds. */
+template <class Prof, bool FULL, bool SKY = false, bool SCORE = true, bool CPL = false, bool REPLAY = false,
+          bool A32 = false, bool DIAG = false>
+__device__ __forceinline__ void step_lanes(const StepArgs &a, double *math_lds, double *prof_lds) {
+  const MathTab mt = fill_math_tables(math_lds);
+  __syncthreads();
+  const int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (g >= (REPLAY ? (int64_t)a.cpl_nlist : a.npoints)) return;
+  const int64_t p = REPLAY ? (int64_t)a.cpl_list[g] : g;
+  if (REPLAY && a.cpl_prio) __builtin_amdgcn_s_setprio(2);
+  Prof T;
+  lane_profile(T, prof_lds, a);
+  Scalars s;
+  int32_t score = 0;
+#ifdef RS_WAVE_TIMING /* tools/wave_times.py: when each wavefront of step_kernel_reg<15, false> starts and ends (100 MHz ticks) */
+  constexpr bool WT = !FULL && std::is_same<Prof, RegProfile<15>>::value;
+  const uint64_t wt0 = WT ? __builtin_amdgcn_s_memrealtime() : 0;
+#endif
+  for (int32_t rnd = 0;; ++rnd) {
+    load_state<FULL>(a.state, a.np_pad, p, T, s);
+    time_loop<FULL, Prof, SKY, SCORE, CPL, REPLAY, A32, DIAG>(mt, T, s, score, REPLAY ? (uint32_t)p : 0u);
+    store_state<FULL>(a.state, a.np_pad, p, T, s);
+    if (!REPLAY || rnd + 1 >= a.cpl_inner) break;
+    if ((((int32_t)a.state[(int64_t)RS_ST_CPL_FLAGS * a.np_pad + p]) & 1) == 0) break;
+  }
+  if (SCORE) a.state[(int64_t)RS_ST_BLSCORE * a.np_pad + p] = bl_score_key(score, s);
+#ifdef RS_WAVE_TIMING
+  if (WT) {
+    a.state[(int64_t)RS_ST_VZ_END * a.np_pad + p] = (double)(wt0 & 0xffffffffffffull);
+    a.state[(int64_t)RS_ST_RH_END * a.np_pad + p] = (double)(__builtin_amdgcn_s_memrealtime() & 0xffffffffffffull);
+  }
+#endif
+}
+
 /* (waves per SIMD: LEAN four, FULL three - measured, rs_step_select.hpp; the choice was a digit of the variant until
  * round 6) */
 template <int NL, bool FULL, bool SCORE = true, bool A32 = false>
 __global__ void __launch_bounds__(kBlock, FULL ? 3 : 4) step_kernel_reg(const StepArgs a) {
   __shared__ double math_lds[RS_MATH_LDS_DOUBLES];
-  const MathTab mt = fill_math_tables(math_lds);
-  __syncthreads();
-  const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (p >= a.npoints) return;
-  RegProfile<NL> T;
-  Scalars s;
-  int32_t score = 0;
-#ifdef RS_WAVE_TIMING /* tools/wave_times.py: when each wavefront of a launch starts and ends (100 MHz ticks) */
-  const uint64_t wt0 = __builtin_amdgcn_s_memrealtime();
-#endif
-  load_state<FULL>(a.state, a.np_pad, p, T, s);
-  time_loop<FULL, RegProfile<NL>, false, SCORE, false, false, A32>(mt, T, s, score);
-  store_state<FULL>(a.state, a.np_pad, p, T, s);
-  if (SCORE) a.state[(int64_t)RS_ST_BLSCORE * a.np_pad + p] = bl_score_key(score, s);
-#ifdef RS_WAVE_TIMING
-  if (!FULL) {
-    a.state[(int64_t)RS_ST_VZ_END * a.np_pad + p] = (double)(wt0 & 0xffffffffffffull);
-    a.state[(int64_t)RS_ST_RH_END * a.np_pad + p] = (double)(__builtin_amdgcn_s_memrealtime() & 0xffffffffffffull);
-  }
-#endif
+  step_lanes<RegProfile<NL>, FULL, false, SCORE, false, false, A32>(a, math_lds, nullptr);
 }
 
 /* FULL feature set, NLayers = 15, four waves per SIMD: layers 1..RS_HYBRID_REG in registers, the
@@ -1228,18 +1269,7 @@ template <bool SCORE, bool A32>
 __global__ void __launch_bounds__(kBlock, 4) step_kernel_hybrid(const StepArgs a) {
   __shared__ double math_lds[RS_MATH_LDS_DOUBLES];
   __shared__ double prof_lds[(15 - RS_HYBRID_REG) * kBlock];
-  const MathTab mt = fill_math_tables(math_lds);
-  __syncthreads();
-  const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (p >= a.npoints) return; /* no barriers below: each lane owns its column */
-  HybridProfile<15, RS_HYBRID_REG> T;
-  T.col = prof_lds + threadIdx.x;
-  Scalars s;
-  int32_t score = 0;
-  load_state<true>(a.state, a.np_pad, p, T, s);
-  time_loop<true, HybridProfile<15, RS_HYBRID_REG>, false, SCORE, false, false, A32>(mt, T, s, score);
-  store_state<true>(a.state, a.np_pad, p, T, s);
-  if (SCORE) a.state[(int64_t)RS_ST_BLSCORE * a.np_pad + p] = bl_score_key(score, s);
+  step_lanes<HybridProfile<15, RS_HYBRID_REG>, true, false, SCORE, false, false, A32>(a, math_lds, prof_lds);
 }
 
 /* DIAG (here, step_kernel_sky and step_kernel_coupled): the instance a plan with diagnostics runs (bl_diagnose): a
@@ -1249,17 +1279,7 @@ template <bool FULL, bool DIAG = false>
 __global__ void __launch_bounds__(kBlock, 4) step_kernel_lds(const StepArgs a) {
   extern __shared__ double lds[]; /* [NLayers][kBlock] */
   __shared__ double math_lds[RS_MATH_LDS_DOUBLES];
-  const MathTab mt = fill_math_tables(math_lds);
-  __syncthreads();
-  const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (p >= a.npoints) return; /* no barriers below: each lane owns its column */
-  LdsProfile T{lds + threadIdx.x, consts_of(&a).NLayers};
-  Scalars s;
-  int32_t score = 0;
-  load_state<FULL>(a.state, a.np_pad, p, T, s);
-  time_loop<FULL, LdsProfile, false, true, false, false, false, DIAG>(mt, T, s, score);
-  store_state<FULL>(a.state, a.np_pad, p, T, s);
-  a.state[(int64_t)RS_ST_BLSCORE * a.np_pad + p] = bl_score_key(score, s);
+  step_lanes<LdsProfile, FULL, false, true, false, false, false, DIAG>(a, math_lds, lds);
 }
 
 /* ---- two wavefronts per 64 points: the flavour for small shards --------------------------------
@@ -2297,17 +2317,7 @@ template <bool DIAG = false>
 __global__ void __launch_bounds__(kBlock, 3) step_kernel_sky(const StepArgs a) {
   extern __shared__ double lds[]; /* [NLayers][kBlock] */
   __shared__ double math_lds[RS_MATH_LDS_DOUBLES];
-  const MathTab mt = fill_math_tables(math_lds);
-  __syncthreads();
-  const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (p >= a.npoints) return;
-  LdsProfile T{lds + threadIdx.x, consts_of(&a).NLayers};
-  Scalars s;
-  int32_t score = 0;
-  load_state<true>(a.state, a.np_pad, p, T, s);
-  time_loop<true, LdsProfile, true, true, false, false, false, DIAG>(mt, T, s, score);
-  store_state<true>(a.state, a.np_pad, p, T, s);
-  a.state[(int64_t)RS_ST_BLSCORE * a.np_pad + p] = bl_score_key(score, s);
+  step_lanes<LdsProfile, true, true, true, false, false, false, DIAG>(a, math_lds, lds);
 }
 
 /* The same for NLayers = 15 with the hybrid profile at W waves per SIMD (rs_step_select.hpp). */
@@ -2315,90 +2325,41 @@ template <int W>
 __global__ void __launch_bounds__(kBlock, W) step_kernel_sky_h(const StepArgs a) {
   __shared__ double math_lds[RS_MATH_LDS_DOUBLES];
   __shared__ double prof_lds[(15 - RS_HYBRID_REG) * kBlock];
-  const MathTab mt = fill_math_tables(math_lds);
-  __syncthreads();
-  const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (p >= a.npoints) return;
-  HybridProfile<15, RS_HYBRID_REG> T;
-  T.col = prof_lds + threadIdx.x;
-  Scalars s;
-  int32_t score = 0;
-  load_state<true>(a.state, a.np_pad, p, T, s);
-  time_loop<true, HybridProfile<15, RS_HYBRID_REG>, true>(mt, T, s, score);
-  store_state<true>(a.state, a.np_pad, p, T, s);
-  a.state[(int64_t)RS_ST_BLSCORE * a.np_pad + p] = bl_score_key(score, s);
+  step_lanes<HybridProfile<15, RS_HYBRID_REG>, true, true>(a, math_lds, prof_lds);
 }
 
 /* FULL feature set + coupling in lock step (time_loop<CPL>): everything of a coupled run except
  * the replays.  LDS profile (any NLayers).  SKY: with the sky-view radiation of the points that have
  * one (src/ModRadiation.f90:7-73) - the forcing windows are read-only here, so what the reference
  * saves and restores of SW / SW_dir / LW around a window (src/Coupling.f90:204-208,249-253) is simply
- * the window as it stands. */
+ * the window as it stands.  (The history score of a parked lane is cheap.) */
 template <bool SKY>
 __global__ void __launch_bounds__(kBlock, 3) step_kernel_cpl(const StepArgs a) {
   extern __shared__ double lds[]; /* [NLayers][kBlock] */
   __shared__ double math_lds[RS_MATH_LDS_DOUBLES];
-  const MathTab mt = fill_math_tables(math_lds);
-  __syncthreads();
-  const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (p >= a.npoints) return;
-  LdsProfile T{lds + threadIdx.x, consts_of(&a).NLayers};
-  Scalars s;
-  int32_t score = 0;
-  load_state<true>(a.state, a.np_pad, p, T, s);
-  time_loop<true, LdsProfile, SKY, true, true>(mt, T, s, score);
-  store_state<true>(a.state, a.np_pad, p, T, s);
-  a.state[(int64_t)RS_ST_BLSCORE * a.np_pad + p] = bl_score_key(score, s); /* parked lanes: cheap */
+  step_lanes<LdsProfile, true, SKY, true, true>(a, math_lds, lds);
 }
 
-/* The same two kernels for NLayers = 15 with the hybrid profile (layers 1-RS_HYBRID_REG in
- * registers, the rest in LDS) at W waves per SIMD. */
+/* The same for NLayers = 15 with the hybrid profile at W waves per SIMD. */
 template <int W, bool SKY = false>
 __global__ void __launch_bounds__(kBlock, W) step_kernel_cpl_h(const StepArgs a) {
   __shared__ double math_lds[RS_MATH_LDS_DOUBLES];
   __shared__ double prof_lds[(15 - RS_HYBRID_REG) * kBlock];
-  const MathTab mt = fill_math_tables(math_lds);
-  __syncthreads();
-  const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (p >= a.npoints) return;
-  HybridProfile<15, RS_HYBRID_REG> T;
-  T.col = prof_lds + threadIdx.x;
-  Scalars s;
-  int32_t score = 0;
-  load_state<true>(a.state, a.np_pad, p, T, s);
-  time_loop<true, HybridProfile<15, RS_HYBRID_REG>, SKY, true, true>(mt, T, s, score);
-  store_state<true>(a.state, a.np_pad, p, T, s);
-  a.state[(int64_t)RS_ST_BLSCORE * a.np_pad + p] = bl_score_key(score, s);
+  step_lanes<HybridProfile<15, RS_HYBRID_REG>, true, SKY, true, true>(a, math_lds, prof_lds);
 }
 
+/* One replay round in lock step over the compacted list (time_loop<REPLAY>): NLayers = 15 with the hybrid profile
+ * at W waves per SIMD, ... */
 template <int W, bool SKY = false>
 __global__ void __launch_bounds__(kBlock, W) step_kernel_cpl_replay_h(const StepArgs a) {
   __shared__ double math_lds[RS_MATH_LDS_DOUBLES];
   __shared__ double prof_lds[(15 - RS_HYBRID_REG) * kBlock];
-  const MathTab mt = fill_math_tables(math_lds);
-  __syncthreads();
-  const int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (g >= (int64_t)a.cpl_nlist) return;
-  const int64_t p = (int64_t)a.cpl_list[g];
-  if (a.cpl_prio) __builtin_amdgcn_s_setprio(2);
-  HybridProfile<15, RS_HYBRID_REG> T;
-  T.col = prof_lds + threadIdx.x;
-  Scalars s;
-  int32_t score = 0;
-  /* cpl_inner replays of the point's window in this launch, as long as its Coupling_control asks for
-   * another (start_coupling_again, bit 0 of the flags it has just stored): the secant iteration of
-   * src/Coupling.f90:363-449 is per point - only the launches were sequential.  The state goes through
-   * the state block between two replays exactly as it does between two rounds. */
-  for (int32_t rnd = 0;; ++rnd) {
-    load_state<true>(a.state, a.np_pad, p, T, s);
-    time_loop<true, HybridProfile<15, RS_HYBRID_REG>, SKY, false, true, true>(mt, T, s, score, (uint32_t)p);
-    store_state<true>(a.state, a.np_pad, p, T, s);
-    if (rnd + 1 >= a.cpl_inner) break;
-    if ((((int32_t)a.state[(int64_t)RS_ST_CPL_FLAGS * a.np_pad + p]) & 1) == 0) break;
-  }
+  step_lanes<HybridProfile<15, RS_HYBRID_REG>, true, SKY, false, true, true>(a, math_lds, prof_lds);
 }
 
-/* One replay round in lock step over the compacted list (time_loop<REPLAY>). */
+/* ... and with the LDS profile (any NLayers).  The one kernel that keeps its own copy of step_lanes<REPLAY>: through
+ * the shared body the compiler spills two more VGPRs in step_kernel_cpl_replay<false> (23 -> 25, scratch 112 ->
+ * 128 B; tools/compare_device_code.py), whatever form the replay loop takes there. */
 template <bool SKY>
 __global__ void __launch_bounds__(kBlock, 3) step_kernel_cpl_replay(const StepArgs a) {
   extern __shared__ double lds[]; /* [NLayers][kBlock] */
@@ -2412,7 +2373,7 @@ __global__ void __launch_bounds__(kBlock, 3) step_kernel_cpl_replay(const StepAr
   LdsProfile T{lds + threadIdx.x, consts_of(&a).NLayers};
   Scalars s;
   int32_t score = 0;
-  for (int32_t rnd = 0;; ++rnd) { /* as in step_kernel_cpl_replay_h */
+  for (int32_t rnd = 0;; ++rnd) {
     load_state<true>(a.state, a.np_pad, p, T, s);
     time_loop<true, LdsProfile, SKY, false, true, true>(mt, T, s, score, (uint32_t)p);
     store_state<true>(a.state, a.np_pad, p, T, s);

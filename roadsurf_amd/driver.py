@@ -245,14 +245,20 @@ def read_json_source(path: str, is_observation: bool = False, utc: bool = True):
 
     with open(path) as fh:
         stations = json.load(fh)
+    if not stations:  # a file without stations: a source of no points
+        return RawSource(np.zeros(0, np.int64), {}, is_observation), [], np.zeros(0), np.zeros(0)
     ids, lats, lons, axes = [], [], [], []
     cols = {v: [] for v in JSON_VARIABLES.values()}
     present = set()
+    seconds = {}  # time stamp -> epoch seconds: stations share their stamps, strptime is the slow part
+
+    def epoch(s):
+        tm = _time.strptime(s, "%Y-%m-%d %H:%M")
+        t = seconds[s] = _cal.timegm(tm) if utc else int(_time.mktime(tm))
+        return t
+
     for st in stations:
-        tt = []
-        for s in st.get("time", []):
-            tm = _time.strptime(s, "%Y-%m-%d %H:%M")
-            tt.append(_cal.timegm(tm) if utc else int(_time.mktime(tm)))
+        tt = [seconds[s] if s in seconds else epoch(s) for s in st.get("time", [])]
         axes.append(np.asarray(tt, np.int64))
         ids.append(int(st["statId"]))
         lats.append(float(st["lat"]))

@@ -780,93 +780,54 @@ struct TileRaw {
   Dev ptimes[RS_MAX_SOURCES], plen[RS_MAX_SOURCES], prp[RS_MAX_SOURCES];
   Dev fld[RS_MAX_SOURCES][NFLD];
   bool any_pp = false;
-  Dev stage; /* landing block of the H2D copies */
+  Dev stage; /* landing block of the H2D copies ... */
+  size_t off[RS_MAX_SOURCES][NFLD + 1] = {}; /* ... byte offset of (source, field) in it; NFLD: the times */
+  bool has[RS_MAX_SOURCES][NFLD + 1] = {};
   Dev segs;  /* Common::segs */
   SrcSet S{};
 };
 
-/* The tile's raw series onto the device, in two halves.  `upload_copies` lands every host array of the
- * tile - point-major rows [m][n_times], as the caller holds them - in ONE landing block with back-to-
- * back copies and waits for them: that is the part that owns the PCIe link, and the part the workers of
- * a device take in turns (rs_devices.hpp: copy_gate).  `upload_finish` turns the rows into the
- * [n_times][mp] columns the kernels read (LDS-tiled transposes), completes Tdew / RH and positions the
- * per-point walks - device work on the worker's own stream, beside the next worker's copies.  (Round 3
- * had one landing buffer per field, so copy and transpose alternated inside the gate and the blocks of a
- * call started ~38 ms apart; the copies alone take less than half of that.) */
-struct TileLanding {
-  size_t off[RS_MAX_SOURCES][NFLD + 1] = {}; /* byte offset of (source, field) in the landing block; NFLD: the times */
-  bool has[RS_MAX_SOURCES][NFLD + 1] = {};
-  /* copies issued on a stream of their own (the worker's copy stream): landed[s][f] is recorded behind the
-   * copy of (source, field), and the worker's stream waits for it before it touches the piece - the
-   * transposes of the first fields run while the last fields are still on the link (round 5: a block's first
-   * step launch used to wait for all copies AND then all transposes, 16 + 6 ms at 250 000 points) */
-  hipEvent_t landed[RS_MAX_SOURCES][NFLD + 1] = {};
-  bool transposed[RS_MAX_SOURCES][NFLD] = {}; /* upload_copies has issued the piece's transpose already */
-  hipEvent_t extra[2] = {nullptr, nullptr};    /* tile start, horizons landed */
-  bool async = false;
-  ~TileLanding() {
-    for (auto &row : landed)
-      for (hipEvent_t e : row)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : extra)
-      if (e) (void)hipEventDestroy(e);
+/* ROADSURF_HIP_DRIVER_TIMING=1: wall time per phase of rs_driver_run on stderr (synchronises) */
+struct PhaseTimer {
+  bool on;
+  hipStream_t s;
+  double t0;
+  double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  static double now() {
+    timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return ts.tv_sec + 1e-9 * ts.tv_nsec;
+  }
+  PhaseTimer(hipStream_t st, bool enabled) : on(enabled), s(st), t0(now()) {}
+  void lap(int k) {
+    if (!on) return;
+    (void)hipStreamSynchronize(s);
+    const double t = now();
+    acc[k] += t - t0;
+    t0 = t;
+  }
+  void report() const {
+    if (!on) return;
+    fprintf(stderr,
+            "rs_driver_run phases [s]: setup %.3f  upload+transpose %.3f  scan/decide %.3f  alloc/params %.3f  "
+            "expand+step %.3f  outputs %.3f  window alloc %.3f  free %.3f\n", acc[0], acc[1], acc[2], acc[3],
+            acc[4], acc[5], acc[6], acc[7]);
   }
 };
 
-int upload_copies(const RsDriverInput *in, const Common &c, int64_t p0, int m, int64_t mp,
-                  TileRaw &T, TileLanding &Ld, hipStream_t stream, hipStream_t work = nullptr) {
-  size_t total = 0;
-  for (int s = 0; s < c.nsrc; ++s) {
-    const RsRawSource &rs = in->sources[s];
-    if (rs.n_times < 1) continue;
-    const size_t piece = ((size_t)m * rs.n_times * sizeof(double) + 255) & ~(size_t)255;
-    if (rs.times_per_point) {
-      Ld.off[s][NFLD] = total;
-      Ld.has[s][NFLD] = true;
-      total += piece;
-    }
-    for (int f = 0; f < NFLD; ++f)
-      if (raw_field(rs, f)) {
-        Ld.off[s][f] = total;
-        Ld.has[s][f] = true;
-        total += piece;
-      }
-  }
-  HOK(T.stage.alloc(total));
-  char *base = T.stage.as<char>();
-  for (int s = 0; s < c.nsrc; ++s) {
-    const RsRawSource &rs = in->sources[s];
-    if (Ld.has[s][NFLD]) {
-      HOK(hipMemcpyAsync(base + Ld.off[s][NFLD], rs.times + (size_t)p0 * rs.n_times,
-                         (size_t)m * rs.n_times * sizeof(int64_t), hipMemcpyHostToDevice, stream));
-      if (Ld.async) {
-        HOK(hipEventCreateWithFlags(&Ld.landed[s][NFLD], hipEventDisableTiming));
-        HOK(hipEventRecord(Ld.landed[s][NFLD], stream));
-      }
-    }
-    for (int f = 0; f < NFLD; ++f)
-      if (Ld.has[s][f]) {
-        HOK(hipMemcpyAsync(base + Ld.off[s][f], raw_field(rs, f) + (size_t)p0 * rs.n_times,
-                           (size_t)m * rs.n_times * sizeof(double), hipMemcpyHostToDevice, stream));
-        if (Ld.async) {
-          HOK(hipEventCreateWithFlags(&Ld.landed[s][f], hipEventDisableTiming));
-          HOK(hipEventRecord(Ld.landed[s][f], stream));
-          if (work) { /* the piece's transpose right behind it, on the worker's stream, beside the next copy
-                         (a copy from pageable memory returns when its bytes are on their way) */
-            HOK(T.fld[s][f].alloc((size_t)rs.n_times * mp * sizeof(double)));
-            HOK(hipStreamWaitEvent(work, Ld.landed[s][f], 0));
-            HOK(transpose(reinterpret_cast<const double *>(base + Ld.off[s][f]), T.fld[s][f].as<double>(), m,
-                          rs.n_times, rs.n_times, mp, work));
-            Ld.transposed[s][f] = true;
-          }
-        }
-      }
-  }
-  return 0;
-}
-
+/* The tile's raw series onto the device, in two halves.  `upload_tile` lands every host array of the
+ * tile - point-major rows [m][n_times], as the caller holds them - in ONE landing block with back-to-
+ * back copies: that is the part that owns the PCIe link, and the part the workers of a device take in
+ * turns (rs_devices.hpp: copy_gate).  `upload_finish` turns the rows into the [n_times][mp] columns the
+ * kernels read (LDS-tiled transposes), completes Tdew / RH and positions the per-point walks.  (Round 3
+ * had one landing buffer per field, so copy and transpose alternated inside the gate and the blocks of a
+ * call started ~38 ms apart; the copies alone take less than half of that.)
+ * All of it on the worker's one stream.  The copies on a stream of their own, each piece's transpose behind
+ * its event, were measured and taken out: a process has four hardware queues, and with two streams per
+ * worker two blocks' compute streams can land on one queue, their step kernels then take turns (the call
+ * 0.64 s instead of 0.58 s; round 5 again: 0.35 -> 0.43 s, profiles/r05_ab_upload_stream.txt). */
 int upload_finish(const RsDriverInput *in, const Common &c, int64_t p0, int m, int64_t mp,
-                  TileRaw &T, const TileLanding &Ld, hipStream_t stream) {
+                  TileRaw &T, hipStream_t stream) {
   T.S.nsrc = c.nsrc;
   T.S.simlen = c.L;
   T.S.np_pad = mp;
@@ -877,17 +838,13 @@ int upload_finish(const RsDriverInput *in, const Common &c, int64_t p0, int m, i
   for (int s = 0; s < c.nsrc; ++s) {
     const RsRawSource &rs = in->sources[s];
     SrcDev &d = T.S.src[s];
+    d = SrcDev{};
     d.n_times = rs.n_times;
     d.is_obs = rs.is_observation;
-    d.plan = nullptr;
-    d.ptimes = nullptr;
-    d.plen = nullptr;
-    d.prp = nullptr;
     if (rs.times_per_point && rs.n_times > 0) {
       /* per-point axes: times [m][n_times] -> [n_times][mp], lengths, walk positions */
       HOK(T.ptimes[s].alloc((size_t)rs.n_times * mp * sizeof(int64_t)));
-      if (Ld.landed[s][NFLD]) HOK(hipStreamWaitEvent(stream, Ld.landed[s][NFLD], 0));
-      HOK(transpose(reinterpret_cast<const int64_t *>(base + Ld.off[s][NFLD]), T.ptimes[s].as<int64_t>(), m,
+      HOK(transpose(reinterpret_cast<const int64_t *>(base + T.off[s][NFLD]), T.ptimes[s].as<int64_t>(), m,
                     rs.n_times, rs.n_times, mp, stream));
       HOK(T.plen[s].alloc(mp * sizeof(int32_t)));
       if (rs.lengths) {
@@ -911,21 +868,16 @@ int upload_finish(const RsDriverInput *in, const Common &c, int64_t p0, int m, i
       d.plan = T.plan[s].as<PlanStep>();
     }
     for (int f = 0; f < NFLD; ++f) {
-      const bool h = Ld.has[s][f];
+      const bool h = T.has[s][f];
       d.fld[f] = nullptr;
       /* Tdew and RH can be completed from each other: both exist if either does */
       const bool derived = (f == R_TDEW && rs.rhz && rs.tair) || (f == R_RHZ && rs.tdew && rs.tair);
       if ((!h && !derived) || rs.n_times == 0) continue;
       const size_t ne = (size_t)rs.n_times * mp;
-      if (h && Ld.transposed[s][f]) {
-        d.fld[f] = T.fld[s][f].as<double>();
-        continue;
-      }
       HOK(T.fld[s][f].alloc(ne * sizeof(double)));
       double *dst = T.fld[s][f].as<double>();
       if (h) {
-        if (Ld.landed[s][f]) HOK(hipStreamWaitEvent(stream, Ld.landed[s][f], 0));
-        HOK(transpose(reinterpret_cast<const double *>(base + Ld.off[s][f]), dst, m, rs.n_times, rs.n_times,
+        HOK(transpose(reinterpret_cast<const double *>(base + T.off[s][f]), dst, m, rs.n_times, rs.n_times,
                       mp, stream));
       } else {
         hipLaunchKernelGGL(fill_f64_kernel, grid1((int64_t)ne), dim3(RS_BLOCK), 0, stream, dst,
@@ -951,11 +903,57 @@ int upload_finish(const RsDriverInput *in, const Common &c, int64_t p0, int m, i
   return 0;
 }
 
-int upload_tile(const RsDriverInput *in, const Common &c, int64_t p0, int m, int64_t mp,
-                TileRaw &T, hipStream_t stream) {
-  TileLanding Ld;
-  if (int rc = upload_copies(in, c, p0, m, mp, T, Ld, stream)) return rc;
-  return upload_finish(in, c, p0, m, mp, T, Ld, stream);
+/* one tile's turn on the link: its series and, where `hzpt` is given, its local horizons */
+int upload_tile(const RsDriverInput *in, const Common &c, int32_t device, int64_t p0, int m, int64_t mp,
+                TileRaw &T, Dev *hzpt, bool timing, hipStream_t stream) {
+  const double tg0 = PhaseTimer::now();
+  std::lock_guard<std::mutex> turn(rsu::copy_gate(device)); /* rs_devices.hpp: uploads take turns */
+  const double tg1 = PhaseTimer::now();
+  size_t total = 0;
+  for (int s = 0; s < c.nsrc; ++s) {
+    const RsRawSource &rs = in->sources[s];
+    if (rs.n_times < 1) continue;
+    const size_t piece = ((size_t)m * rs.n_times * sizeof(double) + 255) & ~(size_t)255;
+    if (rs.times_per_point) {
+      T.off[s][NFLD] = total;
+      T.has[s][NFLD] = true;
+      total += piece;
+    }
+    for (int f = 0; f < NFLD; ++f)
+      if (raw_field(rs, f)) {
+        T.off[s][f] = total;
+        T.has[s][f] = true;
+        total += piece;
+      }
+  }
+  HOK(T.stage.alloc(total));
+  char *base = T.stage.as<char>();
+  for (int s = 0; s < c.nsrc; ++s) {
+    const RsRawSource &rs = in->sources[s];
+    if (T.has[s][NFLD])
+      HOK(hipMemcpyAsync(base + T.off[s][NFLD], rs.times + (size_t)p0 * rs.n_times,
+                         (size_t)m * rs.n_times * sizeof(int64_t), hipMemcpyHostToDevice, stream));
+    for (int f = 0; f < NFLD; ++f)
+      if (T.has[s][f])
+        HOK(hipMemcpyAsync(base + T.off[s][f], raw_field(rs, f) + (size_t)p0 * rs.n_times,
+                           (size_t)m * rs.n_times * sizeof(double), hipMemcpyHostToDevice, stream));
+  }
+  /* the tile's local horizons (2.9 KB per point: as many bytes as all the series together) in the same
+   * turn on the link, so that the block's first launch waits for ITS bytes only - enqueued later, the
+   * copy shared the link with the next block's series and the first step started 58 ms into the call */
+  if (hzpt) {
+    HOK(hzpt->alloc((size_t)m * 360 * sizeof(double)));
+    HOK(hipMemcpyAsync(hzpt->p, in->horizons + (size_t)p0 * 360, (size_t)m * 360 * sizeof(double),
+                       hipMemcpyHostToDevice, stream));
+  }
+  HOK(hipStreamSynchronize(stream));
+  if (int rc = upload_finish(in, c, p0, m, mp, T, stream)) return rc;
+  const double tg2 = PhaseTimer::now();
+  HOK(hipStreamSynchronize(stream)); /* the turn on the link ends when the last byte has landed */
+  if (timing)
+    fprintf(stderr, "rs_driver_run upload: waited %.1f ms for the link, issued the copies in %.1f ms, "
+                    "drained in %.1f ms\n", 1e3 * (tg1 - tg0), 1e3 * (tg2 - tg1), 1e3 * (PhaseTimer::now() - tg2));
+  return 0;
 }
 
 /* Per-point decisions of read_input for one tile (device arrays, [mp]). */
@@ -1096,14 +1094,6 @@ int report_finish(const Common &c, const InputSettings *st, TileReport &R, Local
   return 0;
 }
 
-int report_tile(const Common &c, const InputSettings *st, const TileDecisions &D, int64_t p0, int m,
-                LocalParameters *local, int32_t *status, int32_t *missing_index,
-                hipStream_t stream) {
-  TileReport R;
-  if (int rc = report_issue(D, p0, m, R, stream)) return rc;
-  return report_finish(c, st, R, local, status, missing_index);
-}
-
 int check_device(int32_t device) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
@@ -1112,33 +1102,58 @@ int check_device(int32_t device) {
   return 0;
 }
 
-/* ROADSURF_HIP_DRIVER_TIMING=1: wall time per phase of rs_driver_run on stderr (synchronises) */
-struct PhaseTimer {
-  bool on;
-  hipStream_t s;
-  double t0;
-  double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  static double now() {
-    timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return ts.tv_sec + 1e-9 * ts.tv_nsec;
-  }
-  explicit PhaseTimer(hipStream_t st) : on(getenv("ROADSURF_HIP_DRIVER_TIMING") != nullptr), s(st), t0(now()) {}
-  void lap(int k) {
-    if (!on) return;
-    (void)hipStreamSynchronize(s);
-    const double t = now();
-    acc[k] += t - t0;
-    t0 = t;
-  }
-  void report() const {
-    if (!on) return;
-    fprintf(stderr,
-            "rs_driver_run phases [s]: setup %.3f  upload+transpose %.3f  scan/decide %.3f  alloc/params %.3f  "
-            "expand+step %.3f  outputs %.3f  window alloc %.3f  free %.3f\n", acc[0], acc[1], acc[2], acc[3],
-            acc[4], acc[5], acc[6], acc[7]);
+struct StreamGuard {
+  hipStream_t s = nullptr;
+  ~StreamGuard() {
+    if (s) (void)hipStreamDestroy(s);
   }
 };
+struct PlanGuard {
+  RsPlan *p = nullptr;
+  ~PlanGuard() {
+    if (p) rs_hip_plan_destroy(p);
+  }
+};
+
+/* What rs_driver_expand and rs_driver_run hand to every tile of a call. */
+struct Call {
+  const RsDriverInput *in;
+  const InputSettings *st;
+  const Common &c;
+  const RsConstants &consts;
+  int32_t device;
+  hipStream_t stream;
+  LocalParameters *local;
+  int32_t *status, *missing_index; /* the decisions go to these two and to `local` (each may be null) */
+};
+
+/* A tile's plan, its raw series on the device and read_input's decisions about its points. */
+struct TileHead {
+  PlanGuard pg;
+  int64_t mp = 0; /* the plan's padded point count: the stride of every [row][point] array of the tile */
+  TileRaw T;
+  Dev d_hzpt; /* local horizons [m][360], with `horizons` */
+  TileDecisions D;
+  TileReport rep;
+};
+
+/* Plan, upload, decide, report for points [p0, p0+m).  The decisions are enqueued for the caller's arrays; they
+ * are there on return with `report_now` (or with the timer on, whose laps drain the stream anyway), else
+ * after the caller's own report_finish. */
+int tile_prologue(const Call &k, int64_t p0, int m, bool horizons, bool report_now, PhaseTimer &pt, TileHead &H) {
+  H.pg.p = rs_hip_plan_create(k.device, m, &k.consts, k.stream);
+  if (!H.pg.p) return -11;
+  H.mp = rs_hip_plan_npoints_padded(H.pg.p);
+  if (int rc = upload_tile(k.in, k.c, k.device, p0, m, H.mp, H.T, horizons ? &H.d_hzpt : nullptr, pt.on, k.stream))
+    return rc;
+  pt.lap(1);
+  if (int rc = decide_tile(k.c, k.st, H.T, H.D, k.stream)) return rc;
+  if (int rc = report_issue(H.D, p0, m, H.rep, k.stream)) return rc;
+  if (report_now || pt.on)
+    if (int rc = report_finish(k.c, k.st, H.rep, k.local, k.status, k.missing_index)) return rc;
+  pt.lap(2);
+  return 0;
+}
 
 /* The forcing windows are the one large allocation (up to 64 GB with coupling).  The amdgpu
  * driver wipes VRAM when it is released, and a hipMalloc that lands on pages still being
@@ -1213,18 +1228,763 @@ struct WindowLease {
   }
 };
 
-struct StreamGuard {
-  hipStream_t s = nullptr;
-  ~StreamGuard() {
-    if (s) (void)hipStreamDestroy(s);
+struct ArenaScope {
+  rsu::Arena *prev;
+  explicit ArenaScope(rsu::Arena *a) : prev(rsu::tls_arena()) { rsu::tls_arena() = a; }
+  ~ArenaScope() { rsu::tls_arena() = prev; }
+};
+
+/* Decided once per call (one device's share of it), from the arguments and the environment: every getenv
+ * of the run path is in make_run_policy (ROADSURF_HIP_SCAN_FULL, which rs_driver_expand shares: prepare). */
+struct RunPolicy {
+  int step = 0, n_out = 0; /* output decimation and rows (check_run_arguments) */
+  bool coupled = false;
+  bool cpl_chunked = false;  /* coupling in time chunks: lock step, replay rounds, lock step */
+  bool use_raw = false;      /* the step kernel makes its forcing from the raw series: no windows */
+  bool skyview = false;
+  bool small_block = false;
+  bool want_cluster = false; /* plan order, if the tile has more than one launch (TilePolicy::cluster) */
+  bool timing = false;       /* ROADSURF_HIP_DRIVER_TIMING */
+  int P = 0;                 /* points per tile */
+  int TC = 0;                /* indices per launch */
+  int nwin = 0;              /* forcing windows of a tile (SW_dir / LW_net only with sky view) */
+  size_t win_budget = 0;     /* bytes of forcing windows one worker may hold */
+};
+
+void make_run_policy(const InputSettings *st, const RsConstants &consts, const Common &c,
+                     const LocalParameters *local, int64_t pbeg, int64_t pend, RunPolicy &R) {
+  const int L = c.L;
+  R.timing = getenv("ROADSURF_HIP_DRIVER_TIMING") != nullptr;
+  R.coupled = st->use_coupling == 1;
+  for (int p = 0; p < c.n; ++p)
+    if (local[p].sky_view < 1.0 && local[p].sky_view > (double)-0.01f) R.skyview = true;
+  R.nwin = R.skyview ? NFLD : NFLD - 2;
+  /* Coupling runs time-chunked too (rs_hip_step_cpl / rs_hip_cpl_replay): lock-step
+   * chunks that park a point behind its coupling window, replay rounds over a window-sized block,
+   * lock-step chunks again - with sky view too (in natural order: the per-point geometry is not
+   * gathered into a plan order). */
+  R.cpl_chunked = R.coupled && !getenv("ROADSURF_HIP_CPL_WHOLE");
+  /* The blocks' step kernel makes its forcing from the raw series itself (rs_step_raw: the two-wavefront
+   * flavour, ground wave = JsonSource::interpolate + overlay one index ahead) wherever it can: sources on
+   * shared time axes (the segment table exists), NLayers = 15, no output depth.  No forcing window, no
+   * expansion kernel - with coupling for the lock-step chunks; the replay rounds keep a window over the
+   * coupling windows of the tile (rs_hip_cpl_replay).  ROADSURF_HIP_DRIVER_WINDOWS=1: the windows and the one-point-per-lane
+   * kernels as before (tests compare the two). */
+  R.use_raw = !c.segs.empty() && (!R.coupled || R.cpl_chunked) && consts.NLayers == 15 &&
+              !(st->tsurfOutputDepth >= 0.0) && !getenv("ROADSURF_HIP_DRIVER_WINDOWS");
+  /* Tile of points: large enough to fill the chip (256 CUs x 4 workgroups of 256 points is
+   * 262144 points per round).  With coupling the windows hold the whole series (a point
+   * replays its coupling window), so the tile follows from a 64 GB window budget. */
+  const char *ep = getenv("ROADSURF_HIP_TILE_POINTS"), *et = getenv("ROADSURF_HIP_CHUNK_STEPS");
+  int64_t Pdef = 524288;
+  if (R.coupled && !R.cpl_chunked) {
+    Pdef = (int64_t)(64e9 / ((double)L * NFLD * sizeof(double)));
+    Pdef = std::max<int64_t>(4096, std::min<int64_t>(262144, Pdef / 4096 * 4096));
+  }
+  int64_t Pcap = INT64_MAX;
+  if (R.use_raw) {
+    /* the raw-series step kernels address a tile's whole output window (every decimated row of the series,
+     * padded stride) with 32-bit offsets: rs_step_raw / rs_cpl_replay_raw refuse a window of rs_a32_limit()
+     * elements per stream or more (e.g. 250 000 points x 48 h with outputStep = 1 min: 7.2e8), so the tile is
+     * cut to fit - whatever ROADSURF_HIP_TILE_POINTS asks for */
+    Pcap = std::max<int64_t>(RS_BLOCK, (int64_t)((rs_a32_limit() - 1) / (uint64_t)R.n_out) / RS_BLOCK * RS_BLOCK);
+  }
+  R.P = (int)std::min<int64_t>(std::min<int64_t>(pend - pbeg, Pcap), ep ? std::max(1, atoi(ep)) : Pdef);
+  /* A block of a few wavefronts (the reference's operational example: 401 stations) is the latency of its
+   * dependent steps whatever the order of its points: no re-sorts, and launches of eight hours (154 against 165 ms
+   * per call of that example, profiles/r05_operational_shape.txt) */
+  R.small_block = pend - pbeg < 4096;
+  const char *ec = getenv("ROADSURF_HIP_CLUSTER"); /* 0 / 1: natural / plan order whatever the size */
+  R.want_cluster = ec ? atoi(ec) != 0 : !R.small_block;
+  R.TC = (R.coupled && !R.cpl_chunked) ? L : std::min(L, et ? std::max(1, atoi(et)) : R.use_raw ? (R.want_cluster ? RS_DRIVER_RAW_CHUNK : 960) : 256);
+  /* Budget of one worker's forcing windows.  Chunked coupling sizes its replay block from the
+   * tile's couplingIndexI values (known only after read_input has run on the device): one station
+   * that stopped reporting hours before the others stretches the block towards SimLen, and at the
+   * default tile that is > 100 GB per worker.  Such a tile is cut in halves until it fits. */
+  const char *eb = getenv("ROADSURF_HIP_WINDOW_BUDGET_MB");
+  R.win_budget = eb ? (size_t)std::max(1, atoi(eb)) << 20 : (size_t)24 << 30;
+}
+
+/* Decided per tile, once read_input's decisions about its points are back in `local`: where the coupling
+ * windows lie, what the replay rounds read, how many window rows that takes - and whether the tile fits. */
+struct TilePolicy {
+  bool any_on = false;                    /* some point of the tile has a coupling window */
+  int cs_min = 0, ce_min = 0, ce_max = 0; /* first window start, first and last window end */
+  int r_lo = 0, r_hi = 0;                 /* replay block, 1-based inclusive */
+  bool replay_raw = false;                /* the replay rounds read the raw series too (rs_cpl_replay_raw) */
+  bool need_win = false;                  /* the tile expands forcing windows at all */
+  int WR = 0;                             /* rows of a window */
+  bool cluster = false;                   /* plan order: the slots are re-sorted between launches */
+  bool forecast_key = false;              /* ... by a forecast of the next launch (else by the last one's history) */
+  int halve_to = 0;                       /* > 0: the windows would pass the budget - start again with so many points */
+};
+
+TilePolicy make_tile_policy(const RunPolicy &R, const Common &c, const InputSettings *st,
+                            const LocalParameters *local, int64_t p0, int m, int64_t mp, bool any_pp) {
+  const int L = c.L, TC = R.TC;
+  TilePolicy t;
+  /* chunked coupling: where the tile's coupling windows lie */
+  if (R.cpl_chunked) {
+    for (int p = 0; p < m; ++p) {
+      const LocalParameters &lp = local[p0 + p];
+      if (lp.couplingTsurf < -100 || lp.couplingIndexI < 1) continue; /* src/InputOutput.f90:34-36 */
+      const int ce = lp.couplingIndexI;
+      /* initCouplingTimes, src/Coupling.f90:512-517 */
+      const int cs = ((double)ce <= (double)(st->coupling_minutes * 60) / st->DTSecs) ? 1 : ce - c.cplLen;
+      if (!t.any_on) { t.cs_min = cs; t.ce_min = t.ce_max = ce; t.any_on = true; }
+      t.cs_min = std::min(t.cs_min, cs); t.ce_min = std::min(t.ce_min, ce); t.ce_max = std::max(t.ce_max, ce);
+    }
+  }
+  t.r_lo = t.cs_min;
+  t.r_hi = std::min(t.ce_max + 1, L);
+  const int rlen = t.r_hi - t.r_lo + 1;
+  /* the replay rounds read the raw series too (rs_cpl_replay_raw) where the block ends before SimLen and
+   * there is no sky view */
+  /* ... and is COMPACT - not much longer than one coupling window, rs_hip_cpl_replay's own rule: stations whose
+   * observations end hours apart (the reference's operational example) make a block in which a lock-step
+   * replay would step every listed point through all of it, round after round - those keep the forcing window
+   * and the per-lane replay kernel */
+  t.replay_raw = R.use_raw && R.cpl_chunked && t.any_on && !R.skyview && std::min(t.ce_max + 1, L) < L &&
+                 (int64_t)rlen * 4 <= ((int64_t)c.cplLen + 2) * 5;
+  t.need_win = !R.use_raw || (R.cpl_chunked && t.any_on && !t.replay_raw); /* raw-series stepping: windows for such replays only */
+  t.WR = (R.cpl_chunked && t.any_on) ? (R.use_raw ? rlen : std::max(TC, rlen)) : TC;
+  if (R.cpl_chunked && t.WR > TC && (size_t)R.nwin * mp * t.WR * sizeof(double) > R.win_budget && m > 4096)
+    t.halve_to = std::max(4096, (m / 2 + 4095) / 4096 * 4096);
+  /* Plan order (rs_hip_recluster): with more than one launch per tile the slots
+   * are re-sorted by regime after every launch; windows and per-point parameters are then
+   * produced in slot order and each launch's output rows are mapped back.  Time-chunked
+   * coupling runs that way too: the lock-step chunks are re-sorted like the uncoupled launches,
+   * and the coupling kernels' outputs - the replays' included - go straight to their point's
+   * column (rs_hip_set_output_by_point).  Measured at 1 M points, four plans: 0.90 s against
+   * 0.96 s in natural order with the history key (-12 % vector instructions in the lock-step
+   * kernel), see DESIGN.md 6 for the forecast key.  ROADSURF_HIP_CLUSTER=0 switches the order
+   * off.  Sky view (round 4): the four geometry scalars are gathered like the other per-point
+   * parameters, the local-horizon table is read through the order row. */
+  t.cluster = (!R.coupled || R.cpl_chunked) && TC < L && R.want_cluster;
+  /* Re-sort of the slots for the window [t_next, t_next+len_next): by a FORECAST of that window
+   * (rs_hip_recluster_forecast) - air temperature and wind speed at three of its
+   * indices, produced from the raw series in the CURRENT slot order by the expansion kernel
+   * itself (only those two fields, one index each) - or, where the raw series have per-point time
+   * axes (their walks would have to be re-positioned for every preview), by the history of the
+   * last launch. */
+  t.forecast_key = !any_pp;
+  return t;
+}
+
+/* Hour and sun position per simulation index on the device, the points' geometry on the host: shared by the tiles. */
+struct SharedAxes {
+  Dev d_hour, d_sun;
+  std::vector<double> sun, slat, clat, lrad; /* (this worker's points only: index q of the last three is point pbeg + q) */
+};
+
+/* One device's share of a call, points [pbeg, pend): what its tiles are given. */
+struct Run : Call {
+  const InputParameters *params;
+  const RsDriverOutput *out;
+  const RunPolicy &R;
+  int64_t pbeg, pend;
+  double tbottom;
+  const SharedAxes &ax;
+  PhaseTimer &pt;
+  WindowLease &win;
+  size_t win_bytes; /* of the block `win` holds */
+};
+
+/* tiles the calling thread's last single-device rs_driver_run stepped (tests: the window budget), and how many
+ * of its step launches made their forcing from the raw series (rs_step_raw) */
+thread_local int g_last_tiles = 0, g_last_raw_launches = 0;
+
+void outputs_at(RsOutputs &o, double *b, size_t os) { /* six output blocks of `os` elements each */
+  o.tsurf = b; o.snow = b + os; o.water = b + 2 * os; o.ice = b + 3 * os;
+  o.deposit = b + 4 * os; o.ice2 = b + 5 * os;
+}
+void geometry_at(RsPointParams &p, const double *g, int64_t mp) { /* four rows of `mp`: d_geo, d_geo_s */
+  p.sky_view = g; p.sin_lat = g + mp; p.cos_lat = g + 2 * mp; p.lon_rad = g + 3 * mp;
+}
+
+/* A tile's device buffers and the argument blocks that point into them, from the per-point parameters to
+ * the outputs' way home.  The stages are called in this order by driver_run_range. */
+struct Tile : TileHead {
+  Run &r;
+  const RunPolicy &R;
+  const Common &c;
+  const hipStream_t stream;
+  const int64_t p0;
+  const int m;
+  TilePolicy tp;
+  /* (in the order they are allocated) */
+  Dev d_tb, d_geo;                /* bottom temperature; sky view, sin / cos latitude, longitude in point order */
+  Dev d_phase, d_out, d_outpt;    /* PrecPhase window; the six outputs [n_out][mp]; one of them [m][n_out] */
+  Dev d_outc, d_pp_s, d_geo_s;    /* slot order: one launch's output rows, per-point parameters, geometry */
+  Dev d_prev, d_row1;             /* preview rows of the forecast key; index 1's rows for the initial profile */
+  RsPointParams pp, pps;          /* in point order, in slot order */
+  RsOutputs oo, oc;               /* the result [n_out][mp]; one launch's rows in slot order (rows_c) */
+  size_t os = 0;                  /* mp * n_out */
+  int rows_c = 0;                 /* output rows one launch can produce */
+  ExpandRawArgs ea;
+  rs::RawForcing rf;
+  int walk_at = 0;                /* 0-based index the per-point raw walks are positioned at */
+  size_t seg = 0;                 /* segment of the index the raw-series kernels start at (seek_seg) */
+
+  Tile(Run &run, int64_t p0_, int m_) : r(run), R(run.R), c(run.c), stream(run.stream), p0(p0_), m(m_) {}
+  const RsPointParams &ppx() const { return tp.cluster ? pps : pp; }
+  const int32_t *col() const { return tp.cluster ? ea.order : nullptr; }
+
+  /* per-point parameters in point order */
+  int point_params() {
+    HOK(d_tb.alloc(mp * sizeof(double)));
+    hipLaunchKernelGGL(fill_f64_kernel, grid1(mp), dim3(RS_BLOCK), 0, stream, d_tb.as<double>(), mp, r.tbottom);
+    HOK(hipGetLastError());
+    std::memset(&pp, 0, sizeof(pp));
+    pp.tbottom = d_tb.as<double>();
+    pp.initlen = D.initlen.as<int32_t>();
+    if (r.st->use_relaxation == 1) {
+      pp.tair_relax = D.tair_relax.as<double>();
+      pp.vz_relax = D.vz_relax.as<double>();
+      pp.rh_relax = D.rh_relax.as<double>();
+    }
+    if (R.coupled) {
+      pp.coupling_index = D.cpl_index.as<int32_t>();
+      pp.coupling_tsurf = D.cpl_tsurf.as<double>();
+    }
+    if (R.skyview) {
+      HOK(d_geo.alloc((size_t)4 * mp * sizeof(double)));
+      std::vector<double> g((size_t)4 * mp, 1.0);
+      for (int p = 0; p < m; ++p) {
+        g[p] = r.local[p0 + p].sky_view;
+        g[(size_t)mp + p] = r.ax.slat[p0 - r.pbeg + p];
+        g[(size_t)2 * mp + p] = r.ax.clat[p0 - r.pbeg + p];
+        g[(size_t)3 * mp + p] = r.ax.lrad[p0 - r.pbeg + p];
+      }
+      HOK(hipMemcpyAsync(d_geo.p, g.data(), g.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+      HOK(hipStreamSynchronize(stream)); /* g goes out of scope */
+      geometry_at(pp, d_geo.as<double>(), mp);
+      pp.albedo_surroundings = r.params->Albedo_surroundings;
+      /* the horizon table as the caller holds it, [point][360] (RsPointParams::horizons_by_point): no
+       * transpose, half the device memory, and a point's neighbouring degrees in one cache line; no table
+       * at all where the caller has none (the kernels read a missing table as 0) */
+      pp.horizons = r.in->horizons ? d_hzpt.as<double>() : nullptr; /* (uploaded with the series, tile_prologue) */
+      pp.horizons_by_point = 1;
+    }
+    return 0;
+  }
+  /* the forcing windows (where the tile has any), the outputs, the slot-order copies, and the argument blocks over them */
+  int buffers() {
+    if (tp.need_win && (size_t)R.nwin * mp * tp.WR * sizeof(double) > r.win_bytes) {
+      r.win.release();
+      r.win_bytes = (size_t)R.nwin * mp * tp.WR * sizeof(double);
+      HOK(r.win.acquire(r.win_bytes, r.device));
+    }
+    const size_t fs = (size_t)mp * tp.WR;
+    if (tp.need_win) {
+      HOK(d_phase.alloc(fs * sizeof(int32_t)));
+      hipLaunchKernelGGL(fill_i32_kernel, grid1((int64_t)fs), dim3(RS_BLOCK), 0, stream,
+                         d_phase.as<int32_t>(), (int64_t)fs, -9999); /* InputData.cpp:16 */
+      HOK(hipGetLastError());
+    }
+    os = (size_t)mp * R.n_out;
+    HOK(d_out.alloc((size_t)6 * os * sizeof(double)));
+    /* OutputData.cpp:5-13: rows the simulation never saves read -9999.0 */
+    hipLaunchKernelGGL(fill_f64_kernel, grid1((int64_t)(6 * os)), dim3(RS_BLOCK), 0, stream,
+                       d_out.as<double>(), (int64_t)(6 * os), -9999.0);
+    HOK(hipGetLastError());
+    HOK(d_outpt.alloc((size_t)m * R.n_out * sizeof(double)));
+
+    ea.S = T.S; /* (expand_window: the sources of the current window) */
+    /* window f lives at slot k of the leased block (SW_dir / LW_net only with sky view) */
+    double *wb = static_cast<double *>(r.win.p);
+    for (int f = 0, k = 0; f < NFLD; ++f) {
+      const bool used = tp.need_win && (R.skyview || (f != R_SWDIR && f != R_LWNET));
+      ea.out[f] = used ? wb + (size_t)(k++) * fs : nullptr;
+    }
+    ea.status = D.status.as<int32_t>();
+    ea.cpl_hi = R.coupled ? D.cpl_hi.as<int32_t>() : nullptr;
+    ea.cplLen = c.cplLen;
+    ea.stride = mp;
+    ea.order = nullptr;
+
+    outputs_at(oo, d_out.as<double>(), os);
+    oo.t_stride = mp;
+    oo.decimate = R.step;
+    oo.row0 = 0;
+
+    std::memset(&rf, 0, sizeof(rf));
+    if (R.use_raw) { /* the step kernel's view of the raw series (rs_step_raw, rs_cpl_replay_raw) */
+      rf.nsrc = T.S.nsrc;
+      for (int k = 0; k < T.S.nsrc; ++k) {
+        for (int f = 0; f < NFLD; ++f) rf.src[k].fld[f] = T.S.src[k].fld[f];
+        rf.src[k].plan = T.S.src[k].plan;
+      }
+      rf.nseg = (int32_t)c.segs.size();
+      rf.segs = T.segs.as<ScanSeg>();
+      rf.np_pad = mp;
+      rf.status = D.status.as<int32_t>();
+      rf.hour = r.ax.d_hour.as<int32_t>();
+    }
+
+    /* plan order (TilePolicy::cluster): the slot-order copies of what the launches read and write per point */
+    rows_c = R.TC / R.step + 2;
+    oc = oo;
+    pps = pp;
+    if (tp.cluster && R.skyview) { /* the four geometry scalars in slot order (padding: sky view 1.0 = off) */
+      HOK(d_geo_s.alloc((size_t)4 * mp * sizeof(double)));
+      hipLaunchKernelGGL(fill_f64_kernel, grid1((int64_t)(4 * mp)), dim3(RS_BLOCK), 0, stream,
+                         d_geo_s.as<double>(), (int64_t)(4 * mp), 1.0);
+      HOK(hipGetLastError());
+      geometry_at(pps, d_geo_s.as<double>(), mp);
+    }
+    if (tp.cluster) {
+      if (!R.use_raw) { /* (the raw-series step kernel writes its rows straight into point order) */
+        HOK(d_outc.alloc((size_t)6 * rows_c * mp * sizeof(double)));
+        outputs_at(oc, d_outc.as<double>(), (size_t)rows_c * mp);
+      }
+      /* slot-order copies: 4 doubles (3 relaxation targets, coupling observation), 2 int32 */
+      HOK(d_pp_s.alloc((size_t)mp * (2 * sizeof(int32_t) + 4 * sizeof(double))));
+      double *pd = d_pp_s.as<double>();
+      const bool relax = r.st->use_relaxation == 1;
+      pps.tair_relax = relax ? pd : nullptr;
+      pps.vz_relax = relax ? pd + mp : nullptr;
+      pps.rh_relax = relax ? pd + 2 * mp : nullptr;
+      pps.initlen = reinterpret_cast<int32_t *>(pd + 4 * mp);
+      if (R.coupled) {
+        pps.coupling_tsurf = pd + 3 * mp;
+        pps.coupling_index = reinterpret_cast<int32_t *>(pd + 4 * mp) + mp;
+      }
+      HOK(hipMemsetAsync(d_pp_s.p, 0, (size_t)mp * (2 * sizeof(int32_t) + 4 * sizeof(double)), stream));
+      if (int rc = gather_params()) return rc;
+    }
+    return 0;
+  }
+  /* per-point parameters into the plan's current slot order */
+  int gather_params() {
+    ea.order = rs_hip_plan_order(pg.p); /* identity until the first recluster */
+    if (!ea.order) return -14;
+    double *pd = d_pp_s.as<double>();
+    const bool coupled = R.coupled, skyview = R.skyview;
+    hipLaunchKernelGGL(gather_params_kernel, grid1(m), dim3(RS_BLOCK), 0, stream, ea.order, (int64_t)m,
+                       pp.initlen, const_cast<int32_t *>(pps.initlen), D.tair_relax.as<double>(), pd,
+                       D.vz_relax.as<double>(), pd + mp, D.rh_relax.as<double>(), pd + 2 * mp,
+                       coupled ? pp.coupling_index : nullptr,
+                       coupled ? const_cast<int32_t *>(pps.coupling_index) : nullptr,
+                       coupled ? pp.coupling_tsurf : nullptr,
+                       coupled ? const_cast<double *>(pps.coupling_tsurf) : nullptr,
+                       skyview ? pp.sky_view : nullptr, skyview ? d_geo_s.as<double>() : nullptr, (int64_t)mp);
+    HOK(hipGetLastError());
+    if (skyview) pps.horizon_index = ea.order; /* slot -> column of the horizon table */
+    return 0;
+  }
+  /* The sources that can supply a value somewhere in [i0, i0+n): a shared-axis source whose plan is
+   * K_NONE over the whole range - the observations behind their last report, i.e. for seven windows
+   * out of eight of a 48 h run - is left out of the launch (it would cost a plan load and a branch
+   * per index and variable for nothing).  Order kept: later sources win. */
+  SrcSet sources_for(int i0, int n) const {
+    SrcSet s = T.S;
+    if (T.any_pp) return s;
+    s.nsrc = 0;
+    for (int k = 0; k < T.S.nsrc; ++k) {
+      const std::vector<int32_t> &act = c.active_prefix[k];
+      if (act[std::min(i0 + n, c.L)] - act[std::min(i0, c.L)] > 0) s.src[s.nsrc++] = T.S.src[k];
+    }
+    for (int k = s.nsrc; k < RS_MAX_SOURCES; ++k) s.src[k] = SrcDev{};
+    return s;
+  }
+  /* one window [t0, t0+len): raw series -> step-resolution forcing on the device */
+  int expand_window(int t0, int len, RsForcing &fo) {
+    if (T.any_pp && walk_at != t0 - 1) { /* not the continuation of the last window: re-position */
+      hipLaunchKernelGGL(pp_init_kernel, grid1(mp), dim3(RS_BLOCK), 0, stream, T.S);
+      HOK(hipGetLastError());
+      if (t0 > 1) {
+        hipLaunchKernelGGL(pp_advance_kernel, grid1(mp), dim3(RS_BLOCK), 0, stream, T.S, (int32_t)0,
+                           (int32_t)(t0 - 1));
+        HOK(hipGetLastError());
+      }
+      walk_at = t0 - 1;
+    }
+    ea.i0 = t0 - 1;
+    ea.nsteps = len;
+    ea.S = sources_for(t0 - 1, len);
+    launch_expand_raw(T.any_pp, mp, ea, stream);
+    HOK(hipGetLastError());
+    if (T.any_pp && t0 + len <= c.L) { /* per-point walks: move to the start of the next window */
+      hipLaunchKernelGGL(pp_advance_kernel, grid1(mp), dim3(RS_BLOCK), 0, stream, T.S,
+                         (int32_t)(t0 - 1), (int32_t)len);
+      HOK(hipGetLastError());
+      walk_at = t0 - 1 + len;
+    }
+    std::memset(&fo, 0, sizeof(fo));
+    fo.tair = ea.out[R_TAIR]; fo.tdew = ea.out[R_TDEW]; fo.vz = ea.out[R_VZ];
+    fo.rhz = ea.out[R_RHZ]; fo.prec = ea.out[R_PREC]; fo.sw = ea.out[R_SW]; fo.lw = ea.out[R_LW];
+    fo.tsurfobs = ea.out[R_OBS];
+    fo.depth = nullptr; /* InputData.cpp:18: Depth is never filled by the driver */
+    fo.precphase = d_phase.as<int32_t>();
+    fo.hour = r.ax.d_hour.as<int32_t>() + (t0 - 1);
+    fo.t_stride = mp;
+    fo.hour_pstride = 0;
+    if (R.skyview) {
+      fo.sw_dir = ea.out[R_SWDIR];
+      fo.lw_net = ea.out[R_LWNET];
+      fo.sun = r.ax.d_sun.as<double>() + (size_t)(t0 - 1) * RS_SUN_COLS;
+    }
+    return 0;
+  }
+  /* Plan order: re-sort of the slots for the launch that starts at t_next (TilePolicy::forecast_key), and the
+   * per-point parameters into the new order. */
+  int resort(int t_next) {
+    if (!tp.cluster) return 0;
+    const int len_next = std::min(R.TC, c.L - t_next + 1);
+    if (!tp.forecast_key) {
+      if (rs_hip_recluster(pg.p) != 0) return -14;
+      return gather_params();
+    }
+    if (!d_prev.p) HOK(d_prev.alloc((size_t)9 * mp * sizeof(double)));
+    double *prev = d_prev.as<double>();
+    const int idx[3] = {t_next, t_next + len_next / 2, t_next + len_next - 1};
+    RsPreview pv;
+    std::memset(&pv, 0, sizeof(pv));
+    if (R.use_raw) { /* air temperature and wind speed of the three indices in one launch ... */
+      RawRowsArgs ra;
+      std::memset(&ra, 0, sizeof(ra));
+      ra.S = T.S;
+      ra.status = ea.status;
+      ra.order = ea.order;
+      /* ... with their precipitation: nine rows (RsPreview::prec, the key's precipitation bit: +1.7 % / +4 %,
+       * profiles/r05_ab_precip_bit.txt) */
+      ra.nrows = 9;
+      for (int q = 0; q < 3; ++q) {
+        const int row[3] = {2 * q, 2 * q + 1, 6 + q}, fld[3] = {R_TAIR, R_VZ, R_PREC};
+        for (int k = 0; k < 3; ++k) {
+          ra.fld[row[k]] = fld[k];
+          ra.idx[row[k]] = idx[q] - 1;
+          ra.out[row[k]] = prev + (size_t)row[k] * mp;
+        }
+        pv.tair[q] = ra.out[2 * q];
+        pv.vz[q] = ra.out[2 * q + 1];
+        pv.prec[q] = ra.out[6 + q];
+        pv.hour[q] = r.in->hour[idx[q] - 1];
+      }
+      hipLaunchKernelGGL(raw_rows_kernel, dim3((unsigned)(mp / RS_BLOCK), (unsigned)ra.nrows), dim3(RS_BLOCK), 0, stream, ra);
+      HOK(hipGetLastError());
+    } else {
+      ExpandRawArgs pe = ea; /* current order, same decisions */
+      for (int q = 0; q < 3; ++q) {
+        for (int f = 0; f < NFLD; ++f) pe.out[f] = nullptr;
+        pe.out[R_TAIR] = prev + (size_t)(2 * q) * mp;
+        pe.out[R_VZ] = prev + (size_t)(2 * q + 1) * mp;
+        pe.i0 = idx[q] - 1;
+        pe.nsteps = 1;
+        pe.S = sources_for(idx[q] - 1, 1);
+        launch_expand_raw(false, mp, pe, stream);
+        HOK(hipGetLastError());
+        pv.tair[q] = pe.out[R_TAIR];
+        pv.vz[q] = pe.out[R_VZ];
+        pv.hour[q] = r.in->hour[idx[q] - 1];
+      }
+    }
+    /* the boundary-layer regime at the window's first and last index; the middle one makes the key's count
+     * fields finer and the order no better (relaxation 0.346 -> 0.343 s without it, as bench.py's FULL leg with
+     * its windows of whole hours: profiles/r05_ab_driver_previews.txt).
+     * Its precipitation row stays: the key's precipitation bit reads every row it is given. */
+    pv.n = 2;
+    pv.tair[1] = pv.tair[2];
+    pv.vz[1] = pv.vz[2];
+    pv.hour[1] = pv.hour[2];
+    pv.tair_now = pv.tair[0];
+    pv.alpha = 0.5;
+    pv.mode = 378059; /* 10 bits + the ground digit: the plan's own counting sort (rs_cluster.hip) */
+    if (rs_hip_recluster_forecast(pg.p, &pv) != 0) return -14;
+    return gather_params();
+  }
+  /* The initial profile where there is no forcing window: index 1's air temperature and observation
+   * (src/Initialization.f90:256-259) as two rows of the raw series */
+  int init_state_from_raw() {
+    HOK(d_row1.alloc((size_t)2 * mp * sizeof(double)));
+    RawRowsArgs ra;
+    std::memset(&ra, 0, sizeof(ra));
+    ra.S = T.S;
+    ra.status = ea.status;
+    ra.order = col();
+    ra.nrows = 2;
+    ra.fld[0] = R_TAIR;
+    ra.fld[1] = R_OBS;
+    ra.out[0] = d_row1.as<double>();
+    ra.out[1] = d_row1.as<double>() + mp;
+    hipLaunchKernelGGL(raw_rows_kernel, dim3((unsigned)(mp / RS_BLOCK), 2), dim3(RS_BLOCK), 0, stream, ra);
+    HOK(hipGetLastError());
+    RsForcing f1;
+    std::memset(&f1, 0, sizeof(f1));
+    f1.tair = f1.vz = f1.rhz = f1.prec = f1.sw = f1.lw = ra.out[0]; /* (only tair and tsurfobs are read) */
+    f1.tsurfobs = ra.out[1];
+    f1.precphase = reinterpret_cast<const int32_t *>(ra.out[0]);
+    f1.hour = r.ax.d_hour.as<int32_t>();
+    f1.t_stride = mp;
+    return rs_hip_init_state(pg.p, &f1, &ppx()) != 0 ? -12 : 0;
+  }
+  /* `seg` and rf.seg0 to the segment that holds the 0-based index i (stage 3 of chunked coupling starts behind the
+   * first window end: back) */
+  void seek_seg(int i) {
+    while (seg > 0 && c.segs[seg].i0 > i) --seg;
+    while (seg + 1 < c.segs.size() && c.segs[seg].i1 <= i) ++seg;
+    rf.seg0 = (int32_t)seg;
+  }
+  /* one launch over [t0, t0+len) from the raw series; its (decimated) rows go straight to their point's column
+   * of the result */
+  int step_raw(int t0, int len) {
+    if (t0 == 1)
+      if (int rc = init_state_from_raw()) return rc;
+    seek_seg(t0 - 1);
+    rf.col = col();
+    const double *sunrows = R.skyview ? r.ax.d_sun.as<double>() + (size_t)(t0 - 1) * RS_SUN_COLS : nullptr;
+    if (rs_step_raw(pg.p, &rf, sunrows, &oo, &ppx(), t0, len, tp.cluster) != 0) return -13;
+    ++g_last_raw_launches;
+    return 0;
+  }
+  /* a lock-step chunk of chunked coupling: from the raw series (rs_step_raw: no window) where the block steps that way */
+  int lockstep(int t0, int len, RsForcing &fo) {
+    if (R.use_raw) return step_raw(t0, len);
+    if (int rc = expand_window(t0, len, fo)) return rc;
+    if (t0 == 1 && rs_hip_init_state(pg.p, &fo, &ppx()) != 0) return -12;
+    if (rs_hip_step_cpl(pg.p, &fo, &oo, &ppx(), t0, len) != 0) return -13;
+    return 0;
+  }
+  /* Chunked coupling.  Stage 1: lock step to the last window end; stage 2: the replay rounds over the block
+   * [first window start, last window end + 1]; stage 3: lock step from behind the first
+   * window end (points whose window ends later wait there: they step only the index they
+   * are due for).  Plan order: the slots are re-sorted after every lock-step chunk; windows and per-point
+   * parameters are produced in slot order, outputs go to their point's column. */
+  int loop_cpl_chunked() {
+    const int L = c.L, TC = R.TC;
+    RsForcing fo;
+    if (tp.cluster && rs_hip_set_output_by_point(pg.p, 1) != 0) return -14;
+    const int s1_hi = tp.any_on ? std::min(tp.ce_max, L) : L;
+    for (int t0 = 1; t0 <= s1_hi; t0 += TC) {
+      const int len = std::min(TC, s1_hi - t0 + 1);
+      if (int rc = lockstep(t0, len, fo)) return rc;
+      /* the next lock-step chunk: the one behind this, or stage 3's first */
+      const int t_next = (t0 + len <= s1_hi) ? t0 + len : (tp.any_on && tp.ce_min + 1 <= L) ? tp.ce_min + 1 : 0;
+      if (t_next > 0)
+        if (int rc = resort(t_next)) return rc;
+    }
+    if (!tp.any_on) return 0;
+    int32_t rounds = 0;
+    const int rlen = tp.r_hi - tp.r_lo + 1;
+    if (tp.replay_raw) {
+      seek_seg(tp.r_lo - 1);
+      rf.col = col();
+      if (rs_cpl_replay_raw(pg.p, &rf, &oo, &ppx(), tp.r_lo, rlen, tp.cluster, &rounds) != 0) return -13;
+    } else {
+      if (int rc = expand_window(tp.r_lo, rlen, fo)) return rc;
+      if (rs_hip_cpl_replay(pg.p, &fo, &oo, &ppx(), tp.r_lo, rlen, &rounds) != 0) return -13;
+    }
+    /* every window is behind the plan: stage 3's re-sorts need not move the saved state */
+    if (rs_hip_coupling_windows_closed(pg.p, 1) != 0) return -14;
+    for (int t0 = tp.ce_min + 1; t0 <= L; t0 += TC) {
+      const int len = std::min(TC, L - t0 + 1);
+      if (int rc = lockstep(t0, len, fo)) return rc;
+      if (t0 + len <= L)
+        if (int rc = resort(t0 + len)) return rc;
+    }
+    return 0;
+  }
+  /* no windows: the step kernel's ground wave reads the raw series (rs_step_raw) */
+  int loop_raw() {
+    const int L = c.L, TC = R.TC;
+    for (int t0 = 1; t0 <= L; t0 += TC) {
+      const int len = std::min(TC, L - t0 + 1);
+      if (int rc = step_raw(t0, len)) return rc;
+      if (t0 + len <= L)
+        if (int rc = resort(t0 + len)) return rc;
+    }
+    return 0;
+  }
+  /* forcing windows for the one-point-per-lane kernels (rs_hip_step) */
+  int loop_windows() {
+    const int L = c.L, TC = R.TC, step = R.step;
+    for (int t0 = 1; t0 <= L; t0 += TC) {
+      const int len = std::min(TC, L - t0 + 1);
+      RsForcing fo;
+      if (int rc = expand_window(t0, len, fo)) return rc;
+      /* in plan order this launch's rows go to the launch buffer in slot order, then home */
+      const int64_t r_first = ((int64_t)t0 - 1 + step - 1) / step;
+      const int64_t r_last = ((int64_t)t0 + len - 2) / step;
+      oc.row0 = r_first;
+      if (t0 == 1 && rs_hip_init_state(pg.p, &fo, &ppx()) != 0) return -12;
+      if (rs_hip_step(pg.p, &fo, tp.cluster ? &oc : &oo, &ppx(), t0, len) != 0) return -13;
+      if (!tp.cluster) continue;
+      if (r_last >= r_first) {
+        hipLaunchKernelGGL(unpermute_rows_kernel, dim3((unsigned)(mp / RS_BLOCK), 6), dim3(RS_BLOCK), 0,
+                           stream, ea.order, (int64_t)m, (const double *)d_outc.as<double>(),
+                           (int64_t)rows_c, d_out.as<double>(), (int64_t)R.n_out, r_first,
+                           (int32_t)(r_last - r_first + 1), (int64_t)mp);
+        HOK(hipGetLastError());
+      }
+      if (t0 + len <= L)
+        if (int rc = resort(t0 + len)) return rc;
+    }
+    return 0;
+  }
+  /* blank what read_input rejected, then [row][point] -> [point][row] -> the caller's arrays */
+  int outputs_home() {
+    double *ob = d_out.as<double>();
+    hipLaunchKernelGGL(blank_rejected_kernel, grid1(m), dim3(RS_BLOCK), 0, stream, ob, (int64_t)mp,
+                       (int32_t)R.n_out, (int64_t)m, (const int32_t *)D.status.as<int32_t>());
+    HOK(hipGetLastError());
+    double *dst[6] = {r.out->tsurf, r.out->snow, r.out->water, r.out->ice, r.out->deposit, r.out->ice2};
+    for (int f = 0; f < 6; ++f) {
+      if (!dst[f]) continue;
+      HOK(transpose((const double *)ob + (size_t)f * os, d_outpt.as<double>(), R.n_out, m, mp, R.n_out, stream));
+      HOK(hipMemcpyAsync(dst[f] + (size_t)p0 * R.n_out, d_outpt.p, (size_t)m * R.n_out * sizeof(double),
+                         hipMemcpyDeviceToHost, stream));
+    }
+    HOK(hipStreamSynchronize(stream));
+    r.pt.lap(5);
+    for (Dev *d : {&d_phase, &d_outc, &d_pp_s, &d_geo_s, &d_out, &d_outpt, &d_prev}) d->release();
+    r.pt.lap(7);
+    return 0;
   }
 };
-struct PlanGuard {
-  RsPlan *p = nullptr;
-  ~PlanGuard() {
-    if (p) rs_hip_plan_destroy(p);
+
+int check_run_arguments(const RsDriverInput *in, const InputSettings *st, const InputParameters *params,
+                        const LocalParameters *local, const RsDriverOutput *out, const Common &c, RunPolicy &R,
+                        RsConstants &consts) {
+  if (!params || !local || !out) return fail_msg("rs_driver_run: params, local and out are required", -1);
+  if (!in->year || !in->month || !in->day || !in->hour || !in->minute || !in->second)
+    return fail_msg("rs_driver_run: the calendar arrays of the simulation times are required", -1);
+  /* roadrunner.cpp:290: int step = outputStep*60/DTSecs */
+  R.step = (int)((double)(st->outputStep * 60) / st->DTSecs);
+  if (R.step < 1) return fail_msg("rs_driver_run: outputStep*60/DTSecs < 1", -1);
+  R.n_out = (c.L + R.step - 1) / R.step;
+  if (out->n_out != R.n_out) {
+    char b[160];
+    snprintf(b, sizeof(b), "rs_driver_run: n_out must be ceil(SimLen/step) = %d (step %d)", R.n_out, R.step);
+    return fail_msg(b, -1);
   }
-};
+  int32_t rc32 = 0;
+  rs_build_constants(st, params, &consts, &rc32);
+  if (rc32 != 0)
+    return fail_msg("rs_driver_run: bad settings (NLayers in 5..32, SimLen >= 1, DTSecs > 0)", -1);
+  return 0;
+}
+
+/* Every buffer of a tile other than the forcing windows comes out of one block this worker keeps
+ * across calls (rs_devutil.hpp: Arena): no hipMalloc / hipFree inside the tile loop.  The size is
+ * an estimate from the tile's shape; what does not fit is allocated the old way. */
+size_t arena_estimate(const RsDriverInput *in, const Common &c, const RunPolicy &R) {
+  const size_t mpx = ((size_t)R.P + RS_BLOCK - 1) / RS_BLOCK * RS_BLOCK, L = (size_t)c.L, TC = (size_t)R.TC;
+  size_t raw = 0;
+  for (int k = 0; k < c.nsrc; ++k) {
+    const size_t nt = (size_t)std::max(in->sources[k].n_times, 1);
+    raw += nt * mpx * 8 * (NFLD + 1) + L * sizeof(PlanStep) + 3 * mpx * 8;
+  }
+  const size_t rows = R.cpl_chunked ? (size_t)std::max(R.TC, std::min(c.L, c.cplLen + 2)) : TC;
+  size_t need = 2 * raw                                /* raw series + their landing block */
+                + mpx * 160                            /* decisions, bottom temperature, slot-order copies */
+                + mpx * rows * 4                       /* PrecPhase window */
+                + 7 * mpx * (size_t)R.n_out * 8        /* outputs + their point-major copy */
+                + 6 * mpx * (TC / R.step + 2) * 8      /* one launch's rows in slot order */
+                + 6 * mpx * 8 + L * 40;                /* previews, hour, sun */
+  if (R.skyview) need += 2 * (size_t)360 * mpx * 8 + 8 * mpx * 8;
+  need += mpx * ((size_t)2 * RS_NSTATE * 8 + 64) + ((size_t)16 << 20); /* the tile's plan: two state blocks, order rows, sort scratch */
+  need += need / 16 + ((size_t)64 << 10) * 64; /* alignment of ~60 pieces, slack */
+  return need;
+}
+
+int upload_shared_axes(const Call &k, const RunPolicy &R, int64_t pbeg, int64_t pend, SharedAxes &A) {
+  const RsDriverInput *in = k.in;
+  const int L = k.c.L;
+  HOK(A.d_hour.alloc((size_t)L * sizeof(int32_t)));
+  HOK(hipMemcpyAsync(A.d_hour.p, in->hour, (size_t)L * sizeof(int32_t), hipMemcpyHostToDevice, k.stream));
+  if (!R.skyview) return 0;
+  A.sun.resize((size_t)L * RS_SUN_COLS);
+  rs_sun_table(L, in->year, in->month, in->day, in->hour, in->minute, in->second, A.sun.data());
+  HOK(A.d_sun.alloc(A.sun.size() * sizeof(double)));
+  HOK(hipMemcpyAsync(A.d_sun.p, A.sun.data(), A.sun.size() * sizeof(double), hipMemcpyHostToDevice, k.stream));
+  A.slat.resize(pend - pbeg);
+  A.clat.resize(pend - pbeg);
+  A.lrad.resize(pend - pbeg);
+  rs_point_geometry((int32_t)(pend - pbeg), k.local + pbeg, A.slat.data(), A.clat.data(), A.lrad.data());
+  return 0;
+}
+
+/* points [pbeg, pend) of the input on one device */
+int driver_run_range(const RsDriverInput *in, const InputSettings *st, const InputParameters *params,
+                     LocalParameters *local, const RsDriverOutput *out, int32_t device, int64_t pbeg,
+                     int64_t pend) {
+  Common c;
+  RunPolicy R;
+  RsConstants consts;
+  if (int rc = prepare(in, st, c)) return rc;
+  if (int rc = check_run_arguments(in, st, params, local, out, c, R, consts)) return rc;
+  if (int rc = check_device(device)) return rc;
+  HOK(hipSetDevice(device));
+  StreamGuard sg; /* the worker's one stream: uploads, kernels and downloads of its tiles (upload_tile) */
+  HOK(hipStreamCreate(&sg.s));
+  const hipStream_t stream = sg.s;
+  make_run_policy(st, consts, c, local, pbeg, pend, R);
+  const Call call{in, st, c, consts, device, stream, local, out->status, out->missing_index};
+
+  WindowLease arena_lease; /* (declared behind the stream guard: WindowLease::release) */
+  arena_lease.stream = stream;
+  arena_lease.cache = g_arenacache;
+  rsu::Arena arena;
+  const size_t arena_bytes = arena_estimate(in, c, R);
+  if (arena_lease.acquire(arena_bytes, device) == hipSuccess) {
+    arena.base = static_cast<char *>(arena_lease.p);
+    arena.cap = arena_bytes;
+  }
+  ArenaScope arena_scope(arena.base ? &arena : nullptr);
+  SharedAxes ax;
+  if (int rc = upload_shared_axes(call, R, pbeg, pend, ax)) return rc;
+
+  PhaseTimer pt(stream, R.timing);
+  pt.lap(0);
+  WindowLease win;
+  win.stream = stream;
+  /* chunked coupling: the replay block spans a coupling window plus the index behind it
+   * (usually more rows than a chunk); a tile whose windows are spread further re-leases (Tile::buffers).
+   * A block that steps from the raw series needs windows for the replay rounds of coupling only: sized per tile. */
+  const int64_t Ppad = ((int64_t)R.P + RS_BLOCK - 1) / RS_BLOCK * RS_BLOCK;
+  const int rows0 = R.cpl_chunked ? std::max(R.TC, std::min(c.L, c.cplLen + 2)) : R.TC;
+  Run run{call, params, out, R, pbeg, pend,
+          rs_bottom_temperature(params, &consts, in->year[0], in->month[0], in->day[0]), ax, pt, win,
+          R.use_raw ? 0 : (size_t)R.nwin * Ppad * rows0 * sizeof(double)};
+  if (run.win_bytes) HOK(win.acquire(run.win_bytes, device));
+  pt.lap(6);
+
+  int Pcur = R.P;
+  g_last_tiles = 0;
+  g_last_raw_launches = 0;
+  const size_t arena_mark = arena.off; /* the shared axes stay; a tile's buffers go when it is done */
+  for (int64_t p0 = pbeg; p0 < pend;) {
+    arena.rewind(arena_mark); /* the last tile's buffers are gone (same stream: what still runs there runs first) */
+    const int m = (int)std::min<int64_t>(Pcur, pend - p0);
+    Tile X(run, p0, m);
+    /* (chunked coupling sizes its replay block from the decisions: it needs them at once) */
+    if (int rc = tile_prologue(run, p0, m, R.skyview && in->horizons, R.cpl_chunked, pt, X)) return rc;
+    if (int rc = X.point_params()) return rc;
+    X.tp = make_tile_policy(R, c, st, local, p0, m, X.mp, X.T.any_pp);
+    if (X.tp.halve_to) { /* started again at the same p0 */
+      Pcur = X.tp.halve_to;
+      continue;
+    }
+    if (int rc = X.buffers()) return rc;
+    pt.lap(3);
+    /* The three organisations of the time loop share one cycle - the forcing for [t0, t0+len), the initial state at
+     * t0 = 1, the step, the re-sort for the next chunk - and differ in the rs_* entries they call.  (With the
+     * forecast key nobody reads the step kernels' history score: the instances run without it.) */
+    if (rs_hip_set_history_score(X.pg.p, (X.tp.cluster && X.tp.forecast_key && !R.cpl_chunked) ? 0 : 1) != 0) return -14;
+    if (int rc = R.cpl_chunked ? X.loop_cpl_chunked() : R.use_raw ? X.loop_raw() : X.loop_windows()) return rc;
+    X.d_row1.release();
+    /* everything is enqueued: the decisions go to the caller's arrays while the device works */
+    if (int rc = report_finish(c, st, X.rep, local, out->status, out->missing_index)) return rc;
+    pt.lap(4);
+    if (int rc = X.outputs_home()) return rc;
+    p0 += m;
+    ++g_last_tiles;
+    Pcur = R.P; /* the next tile starts at full size again */
+  }
+  pt.report();
+  return 0;
+}
 
 }  // namespace
 
@@ -1247,36 +2007,32 @@ int rs_driver_expand(const RsDriverInput *in, const InputSettings *st, LocalPara
   int32_t rc32 = 0;
   rs_build_constants(&s15, &prm, &consts, &rc32);
   if (rc32 != 0) return fail_msg("rs_driver_expand: bad settings", -1);
+  const Call call{in, st, c, consts, device, sg.s, local, status, missing_index};
+  PhaseTimer pt(sg.s, false);
   const int P = std::min(c.n, 4096);
   for (int64_t p0 = 0; p0 < c.n; p0 += P) {
     const int m = (int)std::min<int64_t>(P, c.n - p0);
-    PlanGuard pg;
-    pg.p = rs_hip_plan_create(device, m, &consts, sg.s);
-    if (!pg.p) return -11;
-    const int64_t mp = rs_hip_plan_npoints_padded(pg.p);
-    TileRaw T;
-    if (int rc = upload_tile(in, c, p0, m, mp, T, sg.s)) return rc;
-    TileDecisions D;
-    if (int rc = decide_tile(c, st, T, D, sg.s)) return rc;
-    if (int rc = report_tile(c, st, D, p0, m, local, status, missing_index, sg.s)) return rc;
-    Dev win, pt;
+    TileHead H;
+    if (int rc = tile_prologue(call, p0, m, false, true, pt, H)) return rc;
+    const int64_t mp = H.mp;
+    Dev win, pt_out;
     HOK(win.alloc((size_t)NFLD * c.L * mp * sizeof(double)));
-    HOK(pt.alloc((size_t)m * c.L * sizeof(double)));
+    HOK(pt_out.alloc((size_t)m * c.L * sizeof(double)));
     ExpandRawArgs ea;
-    ea.S = T.S;
+    ea.S = H.T.S;
     for (int f = 0; f < NFLD; ++f) ea.out[f] = win.as<double>() + (size_t)f * c.L * mp;
     ea.status = nullptr; /* the test hook shows what read_input returns, rejected or not */
     ea.order = nullptr;
-    ea.cpl_hi = st->use_coupling == 1 ? D.cpl_hi.as<int32_t>() : nullptr;
+    ea.cpl_hi = st->use_coupling == 1 ? H.D.cpl_hi.as<int32_t>() : nullptr;
     ea.cplLen = c.cplLen;
     ea.i0 = 0;
     ea.nsteps = c.L;
     ea.stride = mp;
-    launch_expand_raw(T.any_pp, mp, ea, sg.s);
+    launch_expand_raw(H.T.any_pp, mp, ea, sg.s);
     HOK(hipGetLastError());
     for (int f = 0; f < NFLD; ++f) {
-      HOK(transpose((const double *)ea.out[f], pt.as<double>(), c.L, m, mp, c.L, sg.s));
-      HOK(hipMemcpyAsync(merged + ((size_t)f * c.n + p0) * c.L, pt.p, (size_t)m * c.L * sizeof(double),
+      HOK(transpose((const double *)ea.out[f], pt_out.as<double>(), c.L, m, mp, c.L, sg.s));
+      HOK(hipMemcpyAsync(merged + ((size_t)f * c.n + p0) * c.L, pt_out.p, (size_t)m * c.L * sizeof(double),
                          hipMemcpyDeviceToHost, sg.s));
     }
     HOK(hipStreamSynchronize(sg.s));
@@ -1298,14 +2054,7 @@ void rs_driver_release_cache(void) {
   }
 }
 
-static int driver_run_range(const RsDriverInput *in, const InputSettings *st,
-                            const InputParameters *params, LocalParameters *local,
-                            const RsDriverOutput *out, int32_t device, int64_t pbeg, int64_t pend);
-
-/* tiles the calling thread's last single-device rs_driver_run stepped (tests: the window budget) */
-static thread_local int g_last_tiles = 0, g_last_raw_launches = 0;
 int rs_driver_last_tiles(void) { return g_last_tiles; }
-/* ... and how many of its step launches made their forcing from the raw series (rs_step_raw) */
 int rs_driver_last_raw_launches(void) { return g_last_raw_launches; }
 
 /* device >= 0: that device.  device < 0: the points are cut into contiguous blocks over the
@@ -1334,753 +2083,3 @@ int rs_driver_run(const RsDriverInput *in, const InputSettings *st, const InputP
 }
 
 } /* extern "C" */
-
-/* points [pbeg, pend) of the input on one device */
-static int driver_run_range(const RsDriverInput *in, const InputSettings *st,
-                            const InputParameters *params, LocalParameters *local,
-                            const RsDriverOutput *out, int32_t device, int64_t pbeg, int64_t pend) {
-  Common c;
-  if (int rc = prepare(in, st, c)) return rc;
-  if (!params || !local || !out) return fail_msg("rs_driver_run: params, local and out are required", -1);
-  if (!in->year || !in->month || !in->day || !in->hour || !in->minute || !in->second)
-    return fail_msg("rs_driver_run: the calendar arrays of the simulation times are required", -1);
-  /* roadrunner.cpp:290: int step = outputStep*60/DTSecs */
-  const int step = (int)((double)(st->outputStep * 60) / st->DTSecs);
-  if (step < 1) return fail_msg("rs_driver_run: outputStep*60/DTSecs < 1", -1);
-  const int n_out = (c.L + step - 1) / step;
-  if (out->n_out != n_out) {
-    char b[160];
-    snprintf(b, sizeof(b), "rs_driver_run: n_out must be ceil(SimLen/step) = %d (step %d)", n_out, step);
-    return fail_msg(b, -1);
-  }
-  RsConstants consts;
-  int32_t rc32 = 0;
-  rs_build_constants(st, params, &consts, &rc32);
-  if (rc32 != 0)
-    return fail_msg("rs_driver_run: bad settings (NLayers in 5..32, SimLen >= 1, DTSecs > 0)", -1);
-  if (int rc = check_device(device)) return rc;
-  HOK(hipSetDevice(device));
-  StreamGuard sg, sg_copy;
-  HOK(hipStreamCreate(&sg.s));
-  /* The uploads of a tile on a stream of their own, the transposes behind their pieces (TileLanding): measured
-   * and switched off - a process has four hardware queues, and with two streams per worker two blocks' compute
-   * streams can land on one queue, their step kernels then take turns (one queue with 102 of a call's 204 step
-   * launches, the call 0.64 s instead of 0.58 s; round 5 again: 0.35 -> 0.43 s, profiles/r05_ab_upload_stream.txt).
-   * A constant since round 6 (it was ROADSURF_HIP_UPLOAD_STREAM). */
-  constexpr bool upload_stream = false;
-  if (upload_stream) HOK(hipStreamCreate(&sg_copy.s));
-  hipStream_t stream = sg.s, copy_stream = upload_stream ? sg_copy.s : sg.s;
-
-  const int L = c.L;
-  const bool coupled = st->use_coupling == 1;
-  bool skyview = false;
-  for (int p = 0; p < c.n; ++p)
-    if (local[p].sky_view < 1.0 && local[p].sky_view > (double)-0.01f) skyview = true;
-  const double tbottom = rs_bottom_temperature(params, &consts, in->year[0], in->month[0], in->day[0]);
-
-  const char *ep = getenv("ROADSURF_HIP_TILE_POINTS"), *et = getenv("ROADSURF_HIP_CHUNK_STEPS");
-  /* Tile of points: large enough to fill the chip (256 CUs x 4 workgroups of 256 points is
-   * 262144 points per round).  With coupling the windows hold the whole series (a point
-   * replays its coupling window), so the tile follows from a 64 GB window budget. */
-  /* Coupling runs time-chunked too (rs_hip_step_cpl / rs_hip_cpl_replay): lock-step
-   * chunks that park a point behind its coupling window, replay rounds over a window-sized block,
-   * lock-step chunks again - with sky view too (in natural order: the per-point geometry is not
-   * gathered into a plan order). */
-  const bool cpl_chunked = coupled && !getenv("ROADSURF_HIP_CPL_WHOLE");
-  /* The blocks' step kernel makes its forcing from the raw series itself (rs_step_raw: the two-wavefront
-   * flavour, ground wave = JsonSource::interpolate + overlay one index ahead) wherever it can: sources on
-   * shared time axes (the segment table exists), NLayers = 15, no output depth.  No forcing window, no
-   * expansion kernel - with coupling for the lock-step chunks; the replay rounds keep a window over the
-   * coupling windows of the tile (rs_hip_cpl_replay).  ROADSURF_HIP_DRIVER_WINDOWS=1: the windows and the one-point-per-lane
-   * kernels as before (tests compare the two). */
-  const bool use_raw = !c.segs.empty() && (!coupled || cpl_chunked) && consts.NLayers == 15 &&
-                       !(st->tsurfOutputDepth >= 0.0) && !getenv("ROADSURF_HIP_DRIVER_WINDOWS");
-  int64_t Pdef = 524288;
-  if (coupled && !cpl_chunked) {
-    Pdef = (int64_t)(64e9 / ((double)L * NFLD * sizeof(double)));
-    Pdef = std::max<int64_t>(4096, std::min<int64_t>(262144, Pdef / 4096 * 4096));
-  }
-  int64_t Pcap = INT64_MAX;
-  if (use_raw) {
-    /* the raw-series step kernels address a tile's whole output window (every decimated row of the series,
-     * padded stride) with 32-bit offsets: rs_step_raw / rs_cpl_replay_raw refuse a window of rs_a32_limit()
-     * elements per stream or more (e.g. 250 000 points x 48 h with outputStep = 1 min: 7.2e8), so the tile is
-     * cut to fit - whatever ROADSURF_HIP_TILE_POINTS asks for */
-    Pcap = std::max<int64_t>(RS_BLOCK, (int64_t)((rs_a32_limit() - 1) / (uint64_t)n_out) / RS_BLOCK * RS_BLOCK);
-  }
-  const int P = (int)std::min<int64_t>(std::min<int64_t>(pend - pbeg, Pcap), ep ? std::max(1, atoi(ep)) : Pdef);
-  /* A block of a few wavefronts (the reference's operational example: 401 stations) is the latency of its
-   * dependent steps whatever the order of its points: no re-sorts, and launches of eight hours (154 against 165 ms
-   * per call of that example, profiles/r05_operational_shape.txt) */
-  const bool small_block = pend - pbeg < 4096;
-  const char *ec = getenv("ROADSURF_HIP_CLUSTER"); /* 0 / 1: natural / plan order whatever the size */
-  const bool want_cluster = ec ? atoi(ec) != 0 : !small_block;
-  const int TC = (coupled && !cpl_chunked) ? L : std::min(L, et ? std::max(1, atoi(et)) : use_raw ? (want_cluster ? RS_DRIVER_RAW_CHUNK : 960) : 256);
-
-  /* Every buffer of a tile other than the forcing windows comes out of one block this worker keeps
-   * across calls (rs_devutil.hpp: Arena): no hipMalloc / hipFree inside the tile loop.  The size is
-   * an estimate from the tile's shape; what does not fit is allocated the old way. */
-  WindowLease arena_lease;
-  arena_lease.stream = stream;
-  arena_lease.cache = g_arenacache;
-  rsu::Arena arena;
-  struct ArenaScope {
-    rsu::Arena *prev;
-    explicit ArenaScope(rsu::Arena *a) : prev(rsu::tls_arena()) { rsu::tls_arena() = a; }
-    ~ArenaScope() { rsu::tls_arena() = prev; }
-  };
-  {
-    const size_t mpx = ((size_t)P + RS_BLOCK - 1) / RS_BLOCK * RS_BLOCK;
-    size_t raw = 0;
-    for (int k = 0; k < c.nsrc; ++k) {
-      const size_t nt = (size_t)std::max(in->sources[k].n_times, 1);
-      raw += nt * mpx * 8 * (NFLD + 1) + (size_t)L * sizeof(PlanStep) + 3 * mpx * 8;
-    }
-    const int step_e = std::max(1, (int)((double)(st->outputStep * 60) / st->DTSecs));
-    const size_t n_out_e = ((size_t)L + step_e - 1) / step_e;
-    const size_t rows_e = cpl_chunked ? (size_t)std::max(TC, std::min(L, c.cplLen + 2)) : (size_t)TC;
-    size_t need = 2 * raw                                /* raw series + their landing block */
-                  + mpx * 160                            /* decisions, bottom temperature, slot-order copies */
-                  + mpx * rows_e * 4                     /* PrecPhase window */
-                  + 7 * mpx * n_out_e * 8                /* outputs + their point-major copy */
-                  + 6 * mpx * ((size_t)TC / step_e + 2) * 8 /* one launch's rows in slot order */
-                  + 6 * mpx * 8 + (size_t)L * 40;        /* previews, hour, sun */
-    if (skyview) need += 2 * (size_t)360 * mpx * 8 + 8 * mpx * 8;
-    need += mpx * ((size_t)2 * RS_NSTATE * 8 + 64) + ((size_t)16 << 20); /* the tile's plan: two state blocks, order rows, sort scratch */
-    need += need / 16 + ((size_t)64 << 10) * 64; /* alignment of ~60 pieces, slack */
-    if (arena_lease.acquire(need, device) == hipSuccess) {
-      arena.base = static_cast<char *>(arena_lease.p);
-      arena.cap = need;
-    }
-  }
-  ArenaScope arena_scope(arena.base ? &arena : nullptr);
-
-  /* shared axes */
-  Dev d_hour, d_sun;
-  HOK(d_hour.alloc((size_t)L * sizeof(int32_t)));
-  HOK(hipMemcpyAsync(d_hour.p, in->hour, (size_t)L * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-  std::vector<double> sun, slat, clat, lrad;
-  if (skyview) {
-    sun.resize((size_t)L * RS_SUN_COLS);
-    rs_sun_table(L, in->year, in->month, in->day, in->hour, in->minute, in->second, sun.data());
-    HOK(d_sun.alloc(sun.size() * sizeof(double)));
-    HOK(hipMemcpyAsync(d_sun.p, sun.data(), sun.size() * sizeof(double), hipMemcpyHostToDevice, stream));
-    /* (this worker's points only: index q of the three vectors is point pbeg + q) */
-    slat.resize(pend - pbeg);
-    clat.resize(pend - pbeg);
-    lrad.resize(pend - pbeg);
-    rs_point_geometry((int32_t)(pend - pbeg), local + pbeg, slat.data(), clat.data(), lrad.data());
-  }
-
-  PhaseTimer pt(stream);
-  pt.lap(0);
-  WindowLease win;
-  win.stream = stream;
-  const int nwin = skyview ? NFLD : NFLD - 2;
-  size_t win_bytes = 0;
-  {
-    const int64_t Ppad = ((int64_t)P + RS_BLOCK - 1) / RS_BLOCK * RS_BLOCK;
-    /* chunked coupling: the replay block spans a coupling window plus the index behind it
-     * (usually more rows than a chunk); a tile whose windows are spread further re-leases below */
-    const int rows0 = cpl_chunked ? std::max(TC, std::min(L, c.cplLen + 2)) : TC;
-    /* (a block that steps from the raw series needs windows for the replay rounds of coupling only: sized
-     * per tile, below) */
-    win_bytes = use_raw ? 0 : (size_t)nwin * Ppad * rows0 * sizeof(double);
-    if (win_bytes) HOK(win.acquire(win_bytes, device));
-  }
-  pt.lap(6);
-  /* Budget of one worker's forcing windows.  Chunked coupling sizes its replay block from the
-   * tile's couplingIndexI values (known only after read_input has run on the device): one station
-   * that stopped reporting hours before the others stretches the block towards SimLen, and at the
-   * default tile that is > 100 GB per worker.  Such a tile is cut in halves until it fits. */
-  const char *eb = getenv("ROADSURF_HIP_WINDOW_BUDGET_MB");
-  const size_t win_budget = eb ? (size_t)std::max(1, atoi(eb)) << 20 : (size_t)24 << 30;
-  int Pcur = P;
-  g_last_tiles = 0;
-  g_last_raw_launches = 0;
-  const size_t arena_mark = arena.off; /* the shared axes stay; a tile's buffers go when it is done */
-  for (int64_t p0 = pbeg, m_done = 0; p0 < pend; p0 += m_done) {
-    m_done = 0; /* a tile that has to be cut is started again at the same p0 */
-    arena.rewind(arena_mark); /* the last tile's buffers are gone (same stream: what still runs there runs first) */
-    const int m = (int)std::min<int64_t>(Pcur, pend - p0);
-    PlanGuard pg;
-    pg.p = rs_hip_plan_create(device, m, &consts, stream);
-    if (!pg.p) return -11;
-    const int64_t mp = rs_hip_plan_npoints_padded(pg.p);
-    TileRaw T;
-    TileLanding landing;
-    Dev d_hzpt;
-    {
-      const double tg0 = PhaseTimer::now();
-      std::lock_guard<std::mutex> turn(rsu::copy_gate(device)); /* rs_devices.hpp: uploads take turns */
-      const double tg1 = PhaseTimer::now();
-      /* default: copies and transposes one after the other on the worker's stream */
-      const bool inline_upload = !upload_stream;
-      landing.async = !inline_upload;
-      hipStream_t cs = inline_upload ? stream : copy_stream;
-      if (!inline_upload) { /* the landing block comes out of the arena the last tile's kernels may still be reading */
-        HOK(hipEventCreateWithFlags(&landing.extra[0], hipEventDisableTiming));
-        HOK(hipEventRecord(landing.extra[0], stream));
-        HOK(hipStreamWaitEvent(copy_stream, landing.extra[0], 0));
-      }
-      if (int rc = upload_copies(in, c, p0, m, mp, T, landing, cs, inline_upload ? nullptr : stream)) return rc;
-      /* the tile's local horizons (2.9 KB per point: as many bytes as all the series together) in the same
-       * turn on the link, so that the block's first launch waits for ITS bytes only - enqueued later, the
-       * copy shared the link with the next block's series and the first step started 58 ms into the call */
-      if (skyview && in->horizons) {
-        HOK(d_hzpt.alloc((size_t)m * 360 * sizeof(double)));
-        HOK(hipMemcpyAsync(d_hzpt.p, in->horizons + (size_t)p0 * 360, (size_t)m * 360 * sizeof(double),
-                           hipMemcpyHostToDevice, cs));
-      }
-      if (inline_upload) HOK(hipStreamSynchronize(stream));
-      /* the worker's own stream starts on the pieces as they land (upload_finish); the turn on the link
-       * ends when the last byte has */
-      if (int rc = upload_finish(in, c, p0, m, mp, T, landing, stream)) return rc;
-      const double tg2 = PhaseTimer::now();
-      HOK(hipStreamSynchronize(cs));
-      if (!inline_upload && skyview && in->horizons) { /* (the copy is done: the event orders the worker's stream behind it) */
-        HOK(hipEventCreateWithFlags(&landing.extra[1], hipEventDisableTiming));
-        HOK(hipEventRecord(landing.extra[1], copy_stream));
-        HOK(hipStreamWaitEvent(stream, landing.extra[1], 0));
-      }
-      if (pt.on)
-        fprintf(stderr, "rs_driver_run upload: waited %.1f ms for the link, issued the copies in %.1f ms, "
-                        "drained in %.1f ms\n", 1e3 * (tg1 - tg0), 1e3 * (tg2 - tg1), 1e3 * (PhaseTimer::now() - tg2));
-    }
-    pt.lap(1);
-    TileDecisions D;
-    if (int rc = decide_tile(c, st, T, D, stream)) return rc;
-    TileReport rep;
-    if (int rc = report_issue(D, p0, m, rep, stream)) return rc;
-    /* chunked coupling sizes its replay block from the decisions (below): it needs them now */
-    if (cpl_chunked || pt.on)
-      if (int rc = report_finish(c, st, rep, local, out->status, out->missing_index)) return rc;
-    pt.lap(2);
-
-    /* per-point parameters */
-    Dev d_tb, d_geo;
-    HOK(d_tb.alloc(mp * sizeof(double)));
-    hipLaunchKernelGGL(fill_f64_kernel, grid1(mp), dim3(RS_BLOCK), 0, stream, d_tb.as<double>(), mp,
-                       tbottom);
-    HOK(hipGetLastError());
-    RsPointParams pp;
-    std::memset(&pp, 0, sizeof(pp));
-    pp.tbottom = d_tb.as<double>();
-    pp.initlen = D.initlen.as<int32_t>();
-    if (st->use_relaxation == 1) {
-      pp.tair_relax = D.tair_relax.as<double>();
-      pp.vz_relax = D.vz_relax.as<double>();
-      pp.rh_relax = D.rh_relax.as<double>();
-    }
-    if (coupled) {
-      pp.coupling_index = D.cpl_index.as<int32_t>();
-      pp.coupling_tsurf = D.cpl_tsurf.as<double>();
-    }
-    if (skyview) {
-      HOK(d_geo.alloc((size_t)4 * mp * sizeof(double)));
-      std::vector<double> g((size_t)4 * mp, 1.0);
-      for (int p = 0; p < m; ++p) {
-        g[p] = local[p0 + p].sky_view;
-        g[(size_t)mp + p] = slat[p0 - pbeg + p];
-        g[(size_t)2 * mp + p] = clat[p0 - pbeg + p];
-        g[(size_t)3 * mp + p] = lrad[p0 - pbeg + p];
-      }
-      HOK(hipMemcpyAsync(d_geo.p, g.data(), g.size() * sizeof(double), hipMemcpyHostToDevice, stream));
-      HOK(hipStreamSynchronize(stream)); /* g goes out of scope */
-      pp.sky_view = d_geo.as<double>();
-      pp.sin_lat = d_geo.as<double>() + mp;
-      pp.cos_lat = d_geo.as<double>() + 2 * mp;
-      pp.lon_rad = d_geo.as<double>() + 3 * mp;
-      pp.albedo_surroundings = params->Albedo_surroundings;
-      /* the horizon table as the caller holds it, [point][360] (RsPointParams::horizons_by_point): no
-       * transpose, half the device memory, and a point's neighbouring degrees in one cache line; no table
-       * at all where the caller has none (the kernels read a missing table as 0) */
-      pp.horizons = nullptr;
-      pp.horizons_by_point = 1;
-      if (in->horizons) pp.horizons = d_hzpt.as<double>(); /* (uploaded with the series, above) */
-    }
-
-    /* chunked coupling: where the tile's coupling windows lie (the decisions are back in `local`) */
-    int cs_min = 0, ce_min = 0, ce_max = 0;
-    bool any_on = false;
-    if (cpl_chunked) {
-      for (int p = 0; p < m; ++p) {
-        const LocalParameters &lp = local[p0 + p];
-        if (lp.couplingTsurf < -100 || lp.couplingIndexI < 1) continue; /* src/InputOutput.f90:34-36 */
-        const int ce = lp.couplingIndexI;
-        /* initCouplingTimes, src/Coupling.f90:512-517 */
-        const int cs = ((double)ce <= (double)(st->coupling_minutes * 60) / st->DTSecs) ? 1 : ce - c.cplLen;
-        if (!any_on) { cs_min = cs; ce_min = ce_max = ce; any_on = true; }
-        cs_min = std::min(cs_min, cs); ce_min = std::min(ce_min, ce); ce_max = std::max(ce_max, ce);
-      }
-    }
-    const int r_lo = cs_min, r_hi = std::min(ce_max + 1, L); /* replay block, 1-based inclusive */
-    /* the replay rounds read the raw series too (rs_cpl_replay_raw) where the block ends before SimLen and
-     * there is no sky view */
-    /* ... and is COMPACT - not much longer than one coupling window, rs_hip_cpl_replay's own rule: stations whose
-     * observations end hours apart (the reference's operational example) make a block in which a lock-step
-     * replay would step every listed point through all of it, round after round - those keep the forcing window
-     * and the per-lane replay kernel */
-    const bool replay_raw = use_raw && cpl_chunked && any_on && !skyview && std::min(ce_max + 1, L) < L &&
-                            (int64_t)(r_hi - r_lo + 1) * 4 <= ((int64_t)c.cplLen + 2) * 5;
-    const bool need_win = !use_raw || (cpl_chunked && any_on && !replay_raw); /* raw-series stepping: windows for such replays only */
-    const int WR = (cpl_chunked && any_on) ? (use_raw ? r_hi - r_lo + 1 : std::max(TC, r_hi - r_lo + 1)) : TC;
-    if (cpl_chunked && WR > TC && (size_t)nwin * mp * WR * sizeof(double) > win_budget && m > 4096) {
-      Pcur = std::max(4096, (m / 2 + 4095) / 4096 * 4096);
-      continue;
-    }
-    if (need_win && (size_t)nwin * mp * WR * sizeof(double) > win_bytes) {
-      win.release();
-      win_bytes = (size_t)nwin * mp * WR * sizeof(double);
-      HOK(win.acquire(win_bytes, device));
-    }
-
-    /* windows */
-    const size_t fs = (size_t)mp * WR;
-    Dev d_phase, d_out, d_outpt;
-    if (need_win) {
-      HOK(d_phase.alloc(fs * sizeof(int32_t)));
-      hipLaunchKernelGGL(fill_i32_kernel, grid1((int64_t)fs), dim3(RS_BLOCK), 0, stream,
-                         d_phase.as<int32_t>(), (int64_t)fs, -9999); /* InputData.cpp:16 */
-      HOK(hipGetLastError());
-    }
-    const size_t os = (size_t)mp * n_out;
-    HOK(d_out.alloc((size_t)6 * os * sizeof(double)));
-    /* OutputData.cpp:5-13: rows the simulation never saves read -9999.0 */
-    hipLaunchKernelGGL(fill_f64_kernel, grid1((int64_t)(6 * os)), dim3(RS_BLOCK), 0, stream,
-                       d_out.as<double>(), (int64_t)(6 * os), -9999.0);
-    HOK(hipGetLastError());
-    HOK(d_outpt.alloc((size_t)m * n_out * sizeof(double)));
-
-    ExpandRawArgs ea;
-    ea.S = T.S;
-    /* window f lives at slot wslot[f] of the leased block (SW_dir / LW_net only with sky view) */
-    double *wb = static_cast<double *>(win.p);
-    for (int f = 0, k = 0; f < NFLD; ++f) {
-      const bool used = need_win && (skyview || (f != R_SWDIR && f != R_LWNET));
-      ea.out[f] = used ? wb + (size_t)(k++) * fs : nullptr;
-    }
-    ea.status = D.status.as<int32_t>();
-    ea.cpl_hi = coupled ? D.cpl_hi.as<int32_t>() : nullptr;
-    ea.cplLen = c.cplLen;
-    ea.stride = mp;
-    ea.order = nullptr;
-
-    RsOutputs oo;
-    double *ob = d_out.as<double>();
-    oo.tsurf = ob; oo.snow = ob + os; oo.water = ob + 2 * os; oo.ice = ob + 3 * os;
-    oo.deposit = ob + 4 * os; oo.ice2 = ob + 5 * os;
-    oo.t_stride = mp;
-    oo.decimate = step;
-    oo.row0 = 0;
-
-    /* Plan order (rs_hip_recluster): with more than one launch per tile the slots
-     * are re-sorted by regime after every launch; windows and per-point parameters are then
-     * produced in slot order and each launch's output rows are mapped back.  Time-chunked
-     * coupling runs that way too: the lock-step chunks are re-sorted like the uncoupled launches,
-     * and the coupling kernels' outputs - the replays' included - go straight to their point's
-     * column (rs_hip_set_output_by_point).  Measured at 1 M points, four plans: 0.90 s against
-     * 0.96 s in natural order with the history key (-12 % vector instructions in the lock-step
-     * kernel), see DESIGN.md 6 for the forecast key.  ROADSURF_HIP_CLUSTER=0 switches the order
-     * off.  Sky view (round 4): the four geometry scalars are gathered like the other per-point
-     * parameters, the local-horizon table is read through the order row. */
-    const bool cluster = (!coupled || cpl_chunked) && TC < L && want_cluster;
-    const int rows_c = TC / step + 2; /* output rows one launch can produce */
-    Dev d_outc, d_pp_s, d_geo_s;
-    RsOutputs oc = oo;
-    RsPointParams pps = pp;
-    if (cluster && skyview) { /* the four geometry scalars in slot order (padding: sky view 1.0 = off) */
-      HOK(d_geo_s.alloc((size_t)4 * mp * sizeof(double)));
-      hipLaunchKernelGGL(fill_f64_kernel, grid1((int64_t)(4 * mp)), dim3(RS_BLOCK), 0, stream,
-                         d_geo_s.as<double>(), (int64_t)(4 * mp), 1.0);
-      HOK(hipGetLastError());
-      pps.sky_view = d_geo_s.as<double>();
-      pps.sin_lat = d_geo_s.as<double>() + mp;
-      pps.cos_lat = d_geo_s.as<double>() + 2 * mp;
-      pps.lon_rad = d_geo_s.as<double>() + 3 * mp;
-    }
-    if (cluster) {
-      if (!use_raw) { /* (the raw-series step kernel writes its rows straight into point order) */
-        HOK(d_outc.alloc((size_t)6 * rows_c * mp * sizeof(double)));
-        double *cb = d_outc.as<double>();
-        const size_t cs = (size_t)rows_c * mp;
-        oc.tsurf = cb; oc.snow = cb + cs; oc.water = cb + 2 * cs; oc.ice = cb + 3 * cs;
-        oc.deposit = cb + 4 * cs; oc.ice2 = cb + 5 * cs;
-      }
-      /* slot-order copies: 4 doubles (3 relaxation targets, coupling observation), 2 int32 */
-      HOK(d_pp_s.alloc((size_t)mp * (2 * sizeof(int32_t) + 4 * sizeof(double))));
-      double *pd = d_pp_s.as<double>();
-      pps.tair_relax = st->use_relaxation == 1 ? pd : nullptr;
-      pps.vz_relax = st->use_relaxation == 1 ? pd + mp : nullptr;
-      pps.rh_relax = st->use_relaxation == 1 ? pd + 2 * mp : nullptr;
-      pps.initlen = reinterpret_cast<int32_t *>(pd + 4 * mp);
-      if (coupled) {
-        pps.coupling_tsurf = pd + 3 * mp;
-        pps.coupling_index = reinterpret_cast<int32_t *>(pd + 4 * mp) + mp;
-      }
-      HOK(hipMemsetAsync(d_pp_s.p, 0, (size_t)mp * (2 * sizeof(int32_t) + 4 * sizeof(double)), stream));
-    }
-    /* per-point parameters into the plan's current slot order */
-    auto gather_params = [&]() -> int {
-      ea.order = rs_hip_plan_order(pg.p); /* identity until the first recluster */
-      if (!ea.order) return -14;
-      double *pd = d_pp_s.as<double>();
-      hipLaunchKernelGGL(gather_params_kernel, grid1(m), dim3(RS_BLOCK), 0, stream, ea.order, (int64_t)m,
-                         pp.initlen, const_cast<int32_t *>(pps.initlen), D.tair_relax.as<double>(), pd,
-                         D.vz_relax.as<double>(), pd + mp, D.rh_relax.as<double>(), pd + 2 * mp,
-                         coupled ? pp.coupling_index : nullptr,
-                         coupled ? const_cast<int32_t *>(pps.coupling_index) : nullptr,
-                         coupled ? pp.coupling_tsurf : nullptr,
-                         coupled ? const_cast<double *>(pps.coupling_tsurf) : nullptr,
-                         skyview ? pp.sky_view : nullptr, skyview ? d_geo_s.as<double>() : nullptr, (int64_t)mp);
-      HOK(hipGetLastError());
-      if (skyview) pps.horizon_index = ea.order; /* slot -> column of the horizon table */
-      return 0;
-    };
-    if (cluster)
-      if (int rc = gather_params()) return rc;
-    pt.lap(3);
-    /* The sources that can supply a value somewhere in [i0, i0+n): a shared-axis source whose plan is
-     * K_NONE over the whole range - the observations behind their last report, i.e. for seven windows
-     * out of eight of a 48 h run - is left out of the launch (it would cost a plan load and a branch
-     * per index and variable for nothing).  Order kept: later sources win. */
-    const SrcSet S_full = T.S;
-    auto sources_for = [&](int i0, int n) -> SrcSet {
-      SrcSet r = S_full;
-      if (T.any_pp) return r;
-      r.nsrc = 0;
-      for (int k = 0; k < S_full.nsrc; ++k) {
-        const std::vector<int32_t> &act = c.active_prefix[k];
-        if (act[std::min(i0 + n, L)] - act[std::min(i0, L)] > 0) r.src[r.nsrc++] = S_full.src[k];
-      }
-      for (int k = r.nsrc; k < RS_MAX_SOURCES; ++k) r.src[k] = SrcDev{};
-      return r;
-    };
-    /* one window [t0, t0+len): raw series -> step-resolution forcing on the device */
-    int walk_at = 0; /* 0-based index the per-point raw walks are positioned at */
-    auto expand_window = [&](int t0, int len, RsForcing &fo) -> int {
-      if (T.any_pp && walk_at != t0 - 1) { /* not the continuation of the last window: re-position */
-        hipLaunchKernelGGL(pp_init_kernel, grid1(mp), dim3(RS_BLOCK), 0, stream, T.S);
-        HOK(hipGetLastError());
-        if (t0 > 1) {
-          hipLaunchKernelGGL(pp_advance_kernel, grid1(mp), dim3(RS_BLOCK), 0, stream, T.S, (int32_t)0,
-                             (int32_t)(t0 - 1));
-          HOK(hipGetLastError());
-        }
-        walk_at = t0 - 1;
-      }
-      ea.i0 = t0 - 1;
-      ea.nsteps = len;
-      ea.S = sources_for(t0 - 1, len);
-      launch_expand_raw(T.any_pp, mp, ea, stream);
-      HOK(hipGetLastError());
-      if (T.any_pp && t0 + len <= L) { /* per-point walks: move to the start of the next window */
-        hipLaunchKernelGGL(pp_advance_kernel, grid1(mp), dim3(RS_BLOCK), 0, stream, T.S,
-                           (int32_t)(t0 - 1), (int32_t)len);
-        HOK(hipGetLastError());
-        walk_at = t0 - 1 + len;
-      }
-      std::memset(&fo, 0, sizeof(fo));
-      fo.tair = ea.out[R_TAIR]; fo.tdew = ea.out[R_TDEW]; fo.vz = ea.out[R_VZ];
-      fo.rhz = ea.out[R_RHZ]; fo.prec = ea.out[R_PREC]; fo.sw = ea.out[R_SW]; fo.lw = ea.out[R_LW];
-      fo.tsurfobs = ea.out[R_OBS];
-      fo.depth = nullptr; /* InputData.cpp:18: Depth is never filled by the driver */
-      fo.precphase = d_phase.as<int32_t>();
-      fo.hour = d_hour.as<int32_t>() + (t0 - 1);
-      fo.t_stride = mp;
-      fo.hour_pstride = 0;
-      if (skyview) {
-        fo.sw_dir = ea.out[R_SWDIR];
-        fo.lw_net = ea.out[R_LWNET];
-        fo.sun = d_sun.as<double>() + (size_t)(t0 - 1) * RS_SUN_COLS;
-      }
-      return 0;
-    };
-    /* Re-sort of the slots for the window [t_next, t_next+len_next): by a FORECAST of that window
-     * (rs_hip_recluster_forecast) - air temperature and wind speed at three of its
-     * indices, produced from the raw series in the CURRENT slot order by the expansion kernel
-     * itself (only those two fields, one index each) - or, where the raw series have per-point time
-     * axes (their walks would have to be re-positioned for every preview), by the history of the
-     * last launch. */
-    Dev d_prev;
-    const bool forecast_key = !T.any_pp;
-    /* nobody reads the step kernels' history score then: run the instances without it */
-    if (rs_hip_set_history_score(pg.p, (cluster && forecast_key && !cpl_chunked) ? 0 : 1) != 0) return -14;
-    auto resort_for = [&](int t_next, int len_next) -> int {
-      if (!forecast_key) {
-        if (rs_hip_recluster(pg.p) != 0) return -14;
-        return gather_params();
-      }
-      if (!d_prev.p) HOK(d_prev.alloc((size_t)9 * mp * sizeof(double)));
-      const int idx[3] = {t_next, t_next + len_next / 2, t_next + len_next - 1};
-      ExpandRawArgs pe = ea; /* current order, same sources and decisions */
-      RsPreview pv;
-      std::memset(&pv, 0, sizeof(pv));
-      pv.n = 3;
-      if (use_raw) { /* the six rows in one launch */
-        RawRowsArgs ra;
-        std::memset(&ra, 0, sizeof(ra));
-        ra.S = S_full;
-        ra.status = ea.status;
-        ra.order = ea.order;
-        /* ... nine with the precipitation of the three indices (RsPreview::prec: the key's precipitation bit) */
-        constexpr bool wet_bit = true; /* (+1.7 % / +4 %: profiles/r05_ab_precip_bit.txt; a constant since round 6) */
-        ra.nrows = wet_bit ? 9 : 6;
-        for (int q = 0; q < 3; ++q) {
-          ra.fld[2 * q] = R_TAIR;
-          ra.fld[2 * q + 1] = R_VZ;
-          ra.idx[2 * q] = ra.idx[2 * q + 1] = idx[q] - 1;
-          ra.out[2 * q] = d_prev.as<double>() + (size_t)(2 * q) * mp;
-          ra.out[2 * q + 1] = d_prev.as<double>() + (size_t)(2 * q + 1) * mp;
-          pv.tair[q] = ra.out[2 * q];
-          pv.vz[q] = ra.out[2 * q + 1];
-          pv.hour[q] = in->hour[idx[q] - 1];
-          if (wet_bit) {
-            ra.fld[6 + q] = R_PREC;
-            ra.idx[6 + q] = idx[q] - 1;
-            ra.out[6 + q] = d_prev.as<double>() + (size_t)(6 + q) * mp;
-            pv.prec[q] = ra.out[6 + q];
-          }
-        }
-        hipLaunchKernelGGL(raw_rows_kernel, dim3((unsigned)(mp / RS_BLOCK), (unsigned)ra.nrows), dim3(RS_BLOCK), 0, stream, ra);
-        HOK(hipGetLastError());
-      } else
-      for (int q = 0; q < 3; ++q) {
-        for (int f = 0; f < NFLD; ++f) pe.out[f] = nullptr;
-        pe.out[R_TAIR] = d_prev.as<double>() + (size_t)(2 * q) * mp;
-        pe.out[R_VZ] = d_prev.as<double>() + (size_t)(2 * q + 1) * mp;
-        pe.i0 = idx[q] - 1;
-        pe.nsteps = 1;
-        pe.S = sources_for(idx[q] - 1, 1);
-        launch_expand_raw(false, mp, pe, stream);
-        HOK(hipGetLastError());
-        pv.tair[q] = pe.out[R_TAIR];
-        pv.vz[q] = pe.out[R_VZ];
-        pv.hour[q] = in->hour[idx[q] - 1];
-      }
-      /* the boundary-layer regime at the window's first and last index; the middle one makes the key's count
-       * fields finer and the order no better (relaxation 0.346 -> 0.343 s without it, as bench.py's FULL leg with
-       * its windows of whole hours: profiles/r05_ab_driver_previews.txt).
-       * Its precipitation row stays: the key's precipitation bit reads every row it is given. */
-      {
-        pv.n = 2;
-        pv.tair[1] = pv.tair[2];
-        pv.vz[1] = pv.vz[2];
-        pv.hour[1] = pv.hour[2];
-      }
-      pv.tair_now = pv.tair[0];
-      pv.alpha = 0.5;
-      pv.mode = 378059; /* 10 bits + the ground digit: the plan's own counting sort (rs_cluster.hip) */
-      if (rs_hip_recluster_forecast(pg.p, &pv) != 0) return -14;
-      return gather_params();
-    };
-    if (cpl_chunked) {
-      /* stage 1: lock step to the last window end; stage 2: the replay rounds over the block
-       * [first window start, last window end + 1]; stage 3: lock step from behind the first
-       * window end (points whose window ends later wait there: they step only the index they
-       * are due for) */
-      RsForcing fo;
-      /* plan order: the slots are re-sorted after every lock-step chunk; windows and per-point
-       * parameters are produced in slot order, outputs go to their point's column */
-      const RsPointParams &ppx = cluster ? pps : pp;
-      if (cluster && rs_hip_set_output_by_point(pg.p, 1) != 0) return -14;
-      auto resort = [&](int t_next) -> int {
-        if (!cluster) return 0;
-        if (forecast_key) return resort_for(t_next, std::min(TC, L - t_next + 1));
-        if (rs_hip_recluster(pg.p) != 0) return -14;
-        return gather_params();
-      };
-      /* a lock-step chunk: from the raw series (rs_step_raw: no window) where the block steps that way */
-      rs::RawForcing rf;
-      std::memset(&rf, 0, sizeof(rf));
-      Dev d_row1;
-      size_t seg = 0;
-      if (use_raw) {
-        rf.nsrc = S_full.nsrc;
-        for (int k = 0; k < S_full.nsrc; ++k) {
-          for (int f = 0; f < NFLD; ++f) rf.src[k].fld[f] = S_full.src[k].fld[f];
-          rf.src[k].plan = S_full.src[k].plan;
-        }
-        rf.nseg = (int32_t)c.segs.size();
-        rf.segs = T.segs.as<ScanSeg>();
-        rf.np_pad = mp;
-        rf.status = D.status.as<int32_t>();
-        rf.hour = d_hour.as<int32_t>();
-        HOK(d_row1.alloc((size_t)2 * mp * sizeof(double)));
-      }
-      auto lockstep = [&](int t0, int len) -> int {
-        if (!use_raw) {
-          if (int rc = expand_window(t0, len, fo)) return rc;
-          if (t0 == 1 && rs_hip_init_state(pg.p, &fo, &ppx) != 0) return -12;
-          if (rs_hip_step_cpl(pg.p, &fo, &oo, &ppx, t0, len) != 0) return -13;
-          return 0;
-        }
-        if (t0 == 1) { /* index 1's air temperature and observation, for the initial profile */
-          RawRowsArgs ra;
-          std::memset(&ra, 0, sizeof(ra));
-          ra.S = S_full;
-          ra.status = ea.status;
-          ra.order = cluster ? ea.order : nullptr;
-          ra.nrows = 2;
-          ra.fld[0] = R_TAIR;
-          ra.fld[1] = R_OBS;
-          ra.out[0] = d_row1.as<double>();
-          ra.out[1] = d_row1.as<double>() + mp;
-          hipLaunchKernelGGL(raw_rows_kernel, dim3((unsigned)(mp / RS_BLOCK), 2), dim3(RS_BLOCK), 0, stream, ra);
-          HOK(hipGetLastError());
-          RsForcing f1;
-          std::memset(&f1, 0, sizeof(f1));
-          f1.tair = f1.vz = f1.rhz = f1.prec = f1.sw = f1.lw = ra.out[0]; /* (only tair and tsurfobs are read) */
-          f1.tsurfobs = ra.out[1];
-          f1.precphase = reinterpret_cast<const int32_t *>(ra.out[0]);
-          f1.hour = d_hour.as<int32_t>();
-          f1.t_stride = mp;
-          if (rs_hip_init_state(pg.p, &f1, &ppx) != 0) return -12;
-        }
-        while (seg > 0 && c.segs[seg].i0 > t0 - 1) --seg; /* (stage 3 starts behind the first window end: back) */
-        while (seg + 1 < c.segs.size() && c.segs[seg].i1 <= t0 - 1) ++seg;
-        rf.seg0 = (int32_t)seg;
-        rf.col = cluster ? ea.order : nullptr;
-        const double *sunrows = skyview ? d_sun.as<double>() + (size_t)(t0 - 1) * RS_SUN_COLS : nullptr;
-        if (rs_step_raw(pg.p, &rf, sunrows, &oo, &ppx, t0, len, cluster) != 0) return -13;
-        ++g_last_raw_launches;
-        return 0;
-      };
-      const int s1_hi = any_on ? std::min(ce_max, L) : L;
-      for (int t0 = 1; t0 <= s1_hi; t0 += TC) {
-        const int len = std::min(TC, s1_hi - t0 + 1);
-        if (int rc = lockstep(t0, len)) return rc;
-        /* the next lock-step chunk: the one behind this, or stage 3's first */
-        const int t_next = (t0 + len <= s1_hi) ? t0 + len : (any_on && ce_min + 1 <= L) ? ce_min + 1 : 0;
-        if (t_next > 0)
-          if (int rc = resort(t_next)) return rc;
-      }
-      if (any_on) {
-        int32_t rounds = 0;
-        if (replay_raw) {
-          while (seg > 0 && c.segs[seg].i0 > r_lo - 1) --seg;
-          while (seg + 1 < c.segs.size() && c.segs[seg].i1 <= r_lo - 1) ++seg;
-          rf.seg0 = (int32_t)seg;
-          rf.col = cluster ? ea.order : nullptr;
-          if (rs_cpl_replay_raw(pg.p, &rf, &oo, &ppx, r_lo, r_hi - r_lo + 1, cluster, &rounds) != 0) return -13;
-        } else {
-          if (int rc = expand_window(r_lo, r_hi - r_lo + 1, fo)) return rc;
-          if (rs_hip_cpl_replay(pg.p, &fo, &oo, &ppx, r_lo, r_hi - r_lo + 1, &rounds) != 0) return -13;
-        }
-        /* every window is behind the plan: stage 3's re-sorts need not move the saved state */
-        if (rs_hip_coupling_windows_closed(pg.p, 1) != 0) return -14;
-        for (int t0 = ce_min + 1; t0 <= L; t0 += TC) {
-          const int len = std::min(TC, L - t0 + 1);
-          if (int rc = lockstep(t0, len)) return rc;
-          if (t0 + len <= L)
-            if (int rc = resort(t0 + len)) return rc;
-        }
-      }
-    } else if (use_raw) {
-      /* no windows: the step kernel's ground wave reads the raw series (rs_step_raw) */
-      rs::RawForcing rf;
-      std::memset(&rf, 0, sizeof(rf));
-      rf.nsrc = S_full.nsrc;
-      for (int k = 0; k < S_full.nsrc; ++k) {
-        for (int f = 0; f < NFLD; ++f) rf.src[k].fld[f] = S_full.src[k].fld[f];
-        rf.src[k].plan = S_full.src[k].plan;
-      }
-      rf.nseg = (int32_t)c.segs.size();
-      rf.segs = T.segs.as<ScanSeg>();
-      rf.np_pad = mp;
-      rf.status = D.status.as<int32_t>();
-      rf.hour = d_hour.as<int32_t>();
-      Dev d_row1;
-      HOK(d_row1.alloc((size_t)2 * mp * sizeof(double)));
-      { /* index 1's air temperature and observation, for the initial profile */
-        RawRowsArgs ra;
-        std::memset(&ra, 0, sizeof(ra));
-        ra.S = S_full;
-        ra.status = ea.status;
-        ra.order = cluster ? ea.order : nullptr;
-        ra.nrows = 2;
-        ra.fld[0] = R_TAIR;
-        ra.fld[1] = R_OBS;
-        ra.out[0] = d_row1.as<double>();
-        ra.out[1] = d_row1.as<double>() + mp;
-        hipLaunchKernelGGL(raw_rows_kernel, dim3((unsigned)(mp / RS_BLOCK), 2), dim3(RS_BLOCK), 0, stream, ra);
-        HOK(hipGetLastError());
-        RsForcing f1;
-        std::memset(&f1, 0, sizeof(f1));
-        f1.tair = f1.vz = f1.rhz = f1.prec = f1.sw = f1.lw = ra.out[0]; /* (only tair and tsurfobs are read) */
-        f1.tsurfobs = ra.out[1];
-        f1.precphase = reinterpret_cast<const int32_t *>(ra.out[0]);
-        f1.hour = d_hour.as<int32_t>();
-        f1.t_stride = mp;
-        if (rs_hip_init_state(pg.p, &f1, cluster ? &pps : &pp) != 0) return -12;
-      }
-      size_t seg = 0;
-      for (int t0 = 1; t0 <= L; t0 += TC) {
-        const int len = std::min(TC, L - t0 + 1);
-        while (seg + 1 < c.segs.size() && c.segs[seg].i1 <= t0 - 1) ++seg;
-        rf.seg0 = (int32_t)seg;
-        rf.col = cluster ? ea.order : nullptr;
-        const double *sunrows = skyview ? d_sun.as<double>() + (size_t)(t0 - 1) * RS_SUN_COLS : nullptr;
-        /* the (decimated) rows of a launch go straight to their point's column of the result */
-        if (rs_step_raw(pg.p, &rf, sunrows, &oo, cluster ? &pps : &pp, t0, len, cluster) != 0) return -13;
-        ++g_last_raw_launches;
-        if (!cluster) continue;
-        if (t0 + len <= L)
-          if (int rc = resort_for(t0 + len, std::min(TC, L - (t0 + len) + 1))) return rc;
-      }
-    } else
-    for (int t0 = 1; t0 <= L; t0 += TC) {
-      const int len = std::min(TC, L - t0 + 1);
-      RsForcing fo;
-      if (int rc = expand_window(t0, len, fo)) return rc;
-      if (!cluster) {
-        if (t0 == 1 && rs_hip_init_state(pg.p, &fo, &pp) != 0) return -12;
-        if (rs_hip_step(pg.p, &fo, &oo, &pp, t0, len) != 0) return -13;
-        continue;
-      }
-      /* this launch's rows go to the launch buffer in slot order, then home */
-      const int64_t r_first = ((int64_t)t0 - 1 + step - 1) / step;
-      const int64_t r_last = ((int64_t)t0 + len - 2) / step;
-      oc.row0 = r_first;
-      if (t0 == 1 && rs_hip_init_state(pg.p, &fo, &pps) != 0) return -12;
-      if (rs_hip_step(pg.p, &fo, &oc, &pps, t0, len) != 0) return -13;
-      if (r_last >= r_first) {
-        hipLaunchKernelGGL(unpermute_rows_kernel, dim3((unsigned)(mp / RS_BLOCK), 6), dim3(RS_BLOCK), 0,
-                           stream, ea.order, (int64_t)m, (const double *)d_outc.as<double>(),
-                           (int64_t)rows_c, ob, (int64_t)n_out, r_first, (int32_t)(r_last - r_first + 1),
-                           (int64_t)mp);
-        HOK(hipGetLastError());
-      }
-      if (t0 + len <= L)
-        if (int rc = resort_for(t0 + len, std::min(TC, L - (t0 + len) + 1))) return rc;
-    }
-    /* everything is enqueued: the decisions go to the caller's arrays while the device works */
-    if (int rc = report_finish(c, st, rep, local, out->status, out->missing_index)) return rc;
-    pt.lap(4);
-    hipLaunchKernelGGL(blank_rejected_kernel, grid1(m), dim3(RS_BLOCK), 0, stream, ob, (int64_t)mp,
-                       (int32_t)n_out, (int64_t)m, (const int32_t *)D.status.as<int32_t>());
-    HOK(hipGetLastError());
-    double *dst[6] = {out->tsurf, out->snow, out->water, out->ice, out->deposit, out->ice2};
-    for (int f = 0; f < 6; ++f) {
-      if (!dst[f]) continue;
-      HOK(transpose((const double *)ob + (size_t)f * os, d_outpt.as<double>(), n_out, m, mp, n_out, stream));
-      HOK(hipMemcpyAsync(dst[f] + (size_t)p0 * n_out, d_outpt.p, (size_t)m * n_out * sizeof(double),
-                         hipMemcpyDeviceToHost, stream));
-    }
-    HOK(hipStreamSynchronize(stream));
-    pt.lap(5);
-    d_phase.release();
-    d_outc.release();
-    d_pp_s.release();
-    d_geo_s.release();
-    d_out.release();
-    d_outpt.release();
-    d_prev.release();
-    pt.lap(7);
-    m_done = m;
-    ++g_last_tiles;
-    Pcur = P; /* the next tile starts at full size again */
-  }
-  pt.report();
-  return 0;
-}

@@ -278,6 +278,13 @@ __device__ __forceinline__ double rs_fmin(double a, double b) {
   asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
   return r;
 }
+/* min(x, 1.0) for an x that is not a NaN: the constant is an operand of the instruction (through rs_fmin it
+ * would be moved into a register pair first) */
+__device__ __forceinline__ double rs_min_one(double x) {
+  double r;
+  asm("v_min_f64 %0, %1, 1.0" : "=v"(r) : "v"(x));
+  return r;
+}
 __device__ __forceinline__ float rs_fmax(float a, float b) { return __builtin_fmaxf(a, b); }
 __device__ __forceinline__ float rs_fmin(float a, float b) { return __builtin_fminf(a, b); }
 __device__ __forceinline__ double rs_fabs(double x) { return __builtin_fabs(x); }

@@ -56,7 +56,9 @@
 #ifndef RS_NO_HCW_TABLE
 #define RS_HCW_TABLE 1 /* layer_vsh: the water polynomials' coefficients from RsConstantsDev::hcw */
 #endif
+#define RS_STAB_UPPER(x) rs_min_one(x) /* bl_iteration: the stability parameter's upper clamp, one v_min_f64 in the stable arm */
 #include "rs_physics_body.inc"
+#undef RS_STAB_UPPER
 #undef RS_FROZEN_TABLE
 #undef RS_HCW_TABLE
 #undef RS_LK

@@ -175,9 +175,19 @@ __device__ __forceinline__ bool bl_iteration(const RS_CONSTS &c, const MathTab &
 #else
   RS_REAL Stab = rs_dvb<IEEE>(stab_num * x.BLCond * v.dT, v.den0 * (UStar * UStar * UStar));
 #endif
+  /* The clamp `if (Stab > 1) Stab = 1` (:80) only ever acts on a Stab that takes the stable arm: Stab > 1 is
+   * Stab > 0, and a NaN fails both tests and goes on unclamped, as it must - the guard of boundary_layer() lives
+   * on it.  RS_STAB_UPPER is that clamp inside the arm (rs_physics.hpp: one v_min_f64 instead of a compare, a
+   * literal and two selects in every pass); a flavour without it clamps in front, as the reference writes it. */
+#ifndef RS_STAB_UPPER
   if (Stab > 1) Stab = 1;
+#endif
   if (Stab > 0) {
+#ifdef RS_STAB_UPPER
+    x.PSIH = R4(4.7) * RS_STAB_UPPER(Stab);
+#else
     x.PSIH = R4(4.7) * Stab;
+#endif
     x.PSIM = x.PSIH;
   } else {
     x.PSIH = R4(-2.0) * rs_log(mt, (R4(1.0) + rs_sq<IEEE>(R4(1.0) - R4(16.0) * Stab)) / R4(2.0));
@@ -296,7 +306,10 @@ __device__ __forceinline__ void boundary_layer(const RS_CONSTS &c, const MathTab
 
 /* Volumetric heat capacity of layer j from its (stale) TmpNw value
  * (src/BalanceModel.f90:215-236). */
-__device__ __forceinline__ RS_REAL layer_vsh(const RS_CONSTS &c, int j, RS_REAL T) {
+/* all_thawed: the caller knows that T >= 0 in every active lane of the wavefront (layer_step's ballot): the
+ * select below would pick the polynomials' product everywhere and is skipped - a real branch, three vector
+ * instructions shorter per layer (a literal and two selects) */
+__device__ __forceinline__ RS_REAL layer_vsh(const RS_CONSTS &c, int j, RS_REAL T, bool all_thawed = false) {
   /* both branches are a dozen flops: evaluate the water polynomials
    * unconditionally and select, so 15 layers cost no branches */
   const RS_REAL tmp2 = T * T;
@@ -311,7 +324,17 @@ __device__ __forceinline__ RS_REAL layer_vsh(const RS_CONSTS &c, int j, RS_REAL 
                     R4(0.11516) * tmp2 - R4(3.4739) * T + R4(4217.2);
 #endif
   /* one select of the product instead of one per factor: 920 * 2100 is exact */
-  const RS_REAL CHWT = (T >= 0) ? RooW * CW : R4(920.0) * R4(2100.0);
+  RS_REAL CHWT = RooW * CW;
+  if (!all_thawed) {
+#ifdef RS_FROZEN_TABLE /* (the callers that ballot) */
+    /* Keeps the arm a branch: left to itself the optimiser turns it back into the two selects it replaces.
+     * Nothing in the language promises that; `tools/asm_attrib.py file.s kernel --check-thawed-skip` fails where
+     * a compiler no longer branches round the select (the attribution workflow of profiles/r07_valu_attribution.txt
+     * runs it). */
+    asm volatile("");
+#endif
+    CHWT = (T >= 0) ? CHWT : R4(920.0) * R4(2100.0);
+  }
   return RS_LK(c, j, dryCap) + RS_LK(c, j, WCont) * CHWT;
 }
 
@@ -915,29 +938,40 @@ __device__ __forceinline__ Fluxes model_step_fluxes_prepped(const RS_CONSTS &c, 
  * G(j-1), out: G(j)).  hs1: where to leave HS(1) (layer 1 only). */
 __device__ __forceinline__ RS_REAL layer_step(const RS_CONSTS &c, int j, RS_REAL tj, RS_REAL tstale,
                                               RS_REAL tnext, RS_REAL &Gprev, RS_REAL *hs1) {
-  RS_REAL capDZ;
-#if defined(RS_EXP_SURFACE_LIGHT) && defined(RS_FROZEN_TABLE)
-  if (j <= 2) {
-    capDZ = RS_LK(c, j, capDZF);
-    if (hs1) *hs1 = c.hs1F;
-  } else
-#endif
 #ifdef RS_FROZEN_TABLE
+  /* capDZ travels NEGATED (ncap = -capDZ: the quotient as it comes out of the division, the frozen table's value
+   * with its sign flipped on the scalar unit) and the update multiplies by -ncap: the sign is an operand modifier
+   * of the multiplication, the same product bit for bit, instead of a vector instruction per thawed layer at the
+   * point where the two arms join. */
+  RS_REAL ncap;
   /* every lane of the wavefront has the layer frozen (NaN compares as frozen in layer_vsh too): the
    * plan's constants (rs_consts_dev.h).  The forecast sort's ground digit lines the points up by frost
-   * depth, so that this is the common case where the ground is frozen at all. */
-  if (__builtin_amdgcn_ballot_w64(tstale >= 0) == 0ull) {
-    capDZ = RS_LK(c, j, capDZF);
+   * depth, so that this is the common case where the ground is frozen at all - and a layer that is not frozen
+   * in every point is mostly thawed in every point, which layer_vsh is told. */
+  const unsigned long long thawed = __builtin_amdgcn_ballot_w64(tstale >= 0);
+#ifdef RS_EXP_SURFACE_LIGHT
+  if (j <= 2) {
+    ncap = -RS_LK(c, j, capDZF);
     if (hs1) *hs1 = c.hs1F;
   } else
 #endif
-  {
-    const RS_REAL vsh = layer_vsh(c, j, tstale);
+  if (thawed == 0ull) {
+    ncap = -RS_LK(c, j, capDZF);
+    if (hs1) *hs1 = c.hs1F;
+  } else {
+    const RS_REAL vsh = layer_vsh(c, j, tstale, thawed == __builtin_amdgcn_ballot_w64(true));
     if (hs1) *hs1 = RS_DIVC(vsh * c.HSfac1, c.twoDT, r_twoDT);
-    capDZ = -rs_div((RS_REAL)1.0, RS_LK(c, j, DyC) * vsh);
+    ncap = rs_div((RS_REAL)1.0, RS_LK(c, j, DyC) * vsh);
   }
   const RS_REAL G = RS_LK(c, j, condDZ) * (tnext - tj);
+  const RS_REAL tn = tj + c.DTSecs * (-ncap * (G - Gprev));
+#else
+  const RS_REAL vsh = layer_vsh(c, j, tstale);
+  if (hs1) *hs1 = RS_DIVC(vsh * c.HSfac1, c.twoDT, r_twoDT);
+  const RS_REAL capDZ = -rs_div((RS_REAL)1.0, RS_LK(c, j, DyC) * vsh);
+  const RS_REAL G = RS_LK(c, j, condDZ) * (tnext - tj);
   const RS_REAL tn = tj + c.DTSecs * (capDZ * (G - Gprev));
+#endif
   Gprev = G;
   return tn;
 }

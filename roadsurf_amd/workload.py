@@ -42,7 +42,7 @@ class SyntheticRun:
     def __init__(self, plan: device.Plan, seed: int, hours: int, chunk: int, point_offset: int = 0,
                  plan_order: bool = True, f32: bool = False, year_month_day=(2024, 1, 10),
                  forecast: bool = True, forecast_alpha: float = 0.5, forecast_mode: int = DEFAULT_FORECAST_MODE,
-                 full: bool = False, initlen: int = 720, depth_stream: bool = False):
+                 full: bool = False, initlen: int = 720, depth_stream: bool = False, resort: bool = True):
         self.plan, self.seed, self.hours = plan, seed, hours
         self.simlen = hours * SPK + 1  # examples/example1/src/InputSettings.cpp:98
         self.chunk = min(chunk, self.simlen)
@@ -64,6 +64,9 @@ class SyntheticRun:
         # previews placed inside the window (profiles/r05_ab_previews_in_window.txt); attributes, not environment
         # knobs, since round 6
         self.precip_bit = True
+        # resort=False: plan order without the re-sort between launches - the order row stays the identity, so the
+        # plan-order kernels (the knot-reading two-wavefront flavour) step wavefronts of unlike neighbours (tests)
+        self.resort = resort
         self.previews_in_window = True
         plan.set_history_score(not (plan_order and forecast))  # nobody reads it then
         dev, npad = plan.device, plan.np_pad
@@ -138,7 +141,7 @@ class SyntheticRun:
     def _resort(self, t_next: int) -> None:
         """Re-sort the slots for the window that starts at index t_next."""
         plan = self.plan
-        if t_next > self.simlen:
+        if t_next > self.simlen or not self.resort:
             return
         if not self.forecast:
             plan.recluster()

@@ -660,6 +660,42 @@ int rs_hip_outputs_by_point(RsPlan *plan, const RsOutputs *src, int32_t nrows, c
                             double *const *dst_device, int64_t dst_rows, int64_t dst_row0, void *stream);
 int rs_hip_plan_reset_order(RsPlan *plan);
 
+/* Per-point forecast summaries, reduced from the output rows on the device (the ABI number stays: every name here
+ * is new, a binding detects them with rs_hip_summary_cols).  What a road-weather consumer derives from a
+ * point's six series is small - the lowest surface temperature and when, whether and when the surface first drops
+ * below freezing and for how long, how much snow, water, ice there is at most and for how long - and none of it
+ * needs the series off the device, or transposed there.  rs_hip_outputs_summary reads the first `nrows` rows of
+ * a window `src` ([row][slot], of any launch and any flavour; on an fp32 plan the members of `src` are float arrays
+ * as everywhere else, widened exactly) and merges them into the accumulator of the caller,
+ *     acc_device[col * npoints_padded + point],   point = order[slot],   double, RS_SUM_COLS columns:
+ *   0       number of valid rows - a row of a point is VALID iff its Tsurf is not exactly -9999.0 (what failed and
+ *           rejected points carry behind their last saved index); only valid rows count below
+ *   1, 2    min Tsurf, time index of it (the smallest index among equals)
+ *   3, 4    max Tsurf, time index of it (the smallest index among equals)
+ *   5       smallest time index with Tsurf < spec.tsurf_below (0 = none)
+ *   6       number of rows with Tsurf < spec.tsurf_below
+ *   7..11   max of Snow, Water, Ice, Deposit, Ice2
+ *   12..16  number of rows with that storage > spec.storage_above[k]
+ * Row r of `src` is the absolute 1-based time index index0 + r*index_step.  A point without valid rows has count 0,
+ * min +inf, max -inf, indices 0, storage maxima -inf, counts 0: that is what rs_hip_summary_reset writes into all
+ * npoints_padded columns.  Every comparison is strict; NaN compares false everywhere and still counts as a valid row.
+ * The accumulator is in POINT order, so re-sorts between the calls do not matter, and the merge - ties to the smaller
+ * index, counts added - makes the result independent of the order in which disjoint row ranges are fed.  Feeding a row
+ * twice counts it twice: documented, not detected.  The definition, in numpy: roadsurf_amd/summary.py.
+ * `order_device` and `stream` as for rs_hip_outputs_by_point: NULL = the plan's current order, on the plan's stream;
+ * a stream of the caller's only with a kept order row.  All six streams are required; t_stride >= npoints.  Columns
+ * of points >= npoints are never touched.  It reads 48 B per point and row (24 B of an fp32 window) and reads and writes
+ * 136 B per point and call: measured cost in profiles/summary_outputs.txt (tools/bench_summary_outputs.py). */
+#define RS_SUM_COLS 17
+typedef struct RsSummarySpec {
+  double tsurf_below;       /* Tsurf strictly below this counts as "below" (0.0: freezing) */
+  double storage_above[5];  /* Snow, Water, Ice, Deposit, Ice2 strictly above this count */
+} RsSummarySpec;
+int32_t rs_hip_summary_cols(void); /* RS_SUM_COLS of the library */
+int rs_hip_summary_reset(RsPlan *plan, double *acc_device, void *stream);
+int rs_hip_outputs_summary(RsPlan *plan, const RsOutputs *src, int32_t nrows, int32_t index0, int32_t index_step,
+                           const int32_t *order_device, const RsSummarySpec *spec, double *acc_device, void *stream);
+
 /* Device timing of the step kernel with HIP events recorded on the plan's
  * stream around every rs_hip_step launch since the last reset.  Returns the
  * summed milliseconds (synchronises on the last event) and the launch count. */
@@ -786,6 +822,20 @@ typedef struct RsDriverOutput {
 int rs_driver_run(const RsDriverInput *in, const InputSettings *settings,
                   const InputParameters *params, LocalParameters *local,
                   const RsDriverOutput *out, int32_t device);
+/* The same with per-point summaries of the kept rows [first_row, last_row] of n_out (the caller passes the forecast
+ * part): RS_SUM_COLS doubles per point as rs_hip_outputs_summary defines them, the time index of kept row r being
+ * r*step + 1.  They are reduced on the device from the tile's result block, behind the blanking of rejected points
+ * (whose summary is the empty one) and behind every coupling replay, and only n_points * RS_SUM_COLS doubles come
+ * back for them.  The six series pointers of `out` may all be NULL: a call for the summaries alone transposes and
+ * downloads no series.  `summary` NULL: rs_driver_run. */
+typedef struct RsDriverSummary {
+  RsSummarySpec spec;
+  int32_t first_row, last_row;
+  double *summary; /* host [n_points][RS_SUM_COLS] */
+} RsDriverSummary;
+int rs_driver_run_summary(const RsDriverInput *in, const InputSettings *settings,
+                          const InputParameters *params, LocalParameters *local,
+                          const RsDriverOutput *out, const RsDriverSummary *summary, int32_t device);
 /* Tiles: a call steps its points in tiles of ROADSURF_HIP_TILE_POINTS (default 524 288).  With
  * coupling the forcing windows of a tile span [first coupling-window start, last window end + 1]
  * of ITS points; a tile whose windows would exceed ROADSURF_HIP_WINDOW_BUDGET_MB (default 24 576)

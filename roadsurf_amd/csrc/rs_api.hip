@@ -156,6 +156,8 @@ int64_t rs_abi_sizeof(int which) {
     case 12: return sizeof(RsRawSource);
     case 13: return sizeof(RsDriverInput);
     case 14: return sizeof(RsDriverOutput);
+    case 15: return sizeof(RsSummarySpec);
+    case 16: return sizeof(RsDriverSummary);
     default: return -1;
   }
 }
@@ -487,6 +489,32 @@ int rs_hip_outputs_by_point(RsPlan *pl, const RsOutputs *src, int32_t nrows, con
   HIP_OK(hipSetDevice(pl->device));
   HIP_OK(rs_cluster_outputs_by_point(in, out, order ? order : pl->order, pl->npoints, src->t_stride, nrows, dst_rows,
                                      dst_row0, stream ? (hipStream_t)stream : pl->stream));
+  return 0;
+}
+
+int32_t rs_hip_summary_cols(void) { return RS_SUM_COLS; }
+
+int rs_hip_summary_reset(RsPlan *pl, double *acc, void *stream) {
+  if (!pl || !acc) return set_err("rs_hip_summary_reset: bad arguments");
+  HIP_OK(hipSetDevice(pl->device));
+  HIP_OK(rs_cluster_summary_reset(acc, pl->np_pad, stream ? (hipStream_t)stream : pl->stream));
+  return 0;
+}
+
+int rs_hip_outputs_summary(RsPlan *pl, const RsOutputs *src, int32_t nrows, int32_t index0, int32_t index_step,
+                           const int32_t *order, const RsSummarySpec *spec, double *acc, void *stream) {
+  if (!pl || !src || !spec || !acc || nrows < 1 || index0 < 1 || index_step < 1 ||
+      (int64_t)index0 + (int64_t)(nrows - 1) * index_step > INT32_MAX)
+    return set_err("rs_hip_outputs_summary: bad arguments (nrows >= 1 rows at the time indices index0 + r*index_step, index0 >= 1, index_step >= 1)");
+  const void *in[6] = {src->tsurf, src->snow, src->water, src->ice, src->deposit, src->ice2};
+  for (int f = 0; f < 6; ++f)
+    if (!in[f]) return set_err("rs_hip_outputs_summary: all six streams are required");
+  if (src->t_stride < pl->npoints) return set_err("rs_hip_outputs_summary: t_stride below the plan's points");
+  if (!order && stream) return set_err("rs_hip_outputs_summary: on a stream of the caller's the order row must be a kept one");
+  if (!order && !rs_hip_plan_order(pl)) return -1;
+  HIP_OK(hipSetDevice(pl->device));
+  HIP_OK(rs_cluster_outputs_summary(in, pl->f32, order ? order : pl->order, pl->npoints, src->t_stride, nrows, index0,
+                                    index_step, *spec, acc, pl->np_pad, stream ? (hipStream_t)stream : pl->stream));
   return 0;
 }
 

@@ -135,6 +135,166 @@ hipError_t rs_cluster_outputs_by_point(const double *const src[6], double *const
   return hipGetLastError();
 }
 
+/* Per-point summaries of the output rows (include/roadsurf.h, rs_hip_outputs_summary; the definition is
+ * roadsurf_amd/summary.py, reduce_series): a sibling of outputs_by_point_kernel that reads the same [row][slot] windows
+ * and keeps RS_SUM_COLS numbers per point instead of the series.  One lane owns a slot and carries its summary in
+ * registers over the rows, every row load a coalesced 512 B per wavefront and stream (256 B of an fp32 window),
+ * SUM_ROWS rows of all six streams in flight per lane.  The four wavefronts of a workgroup share 64 slots and take a
+ * quarter of the rows each - a batch of a few hundred points is a handful of workgroups, and the rows are what
+ * there is to spread - then merge through LDS with the rule that also merges across calls (Sum::merge), and the
+ * first wavefront ends with one read-merge-write of its points' accumulator columns.  A point sits in one slot:
+ * plain loads and stores, no atomics. */
+namespace {
+constexpr int SUM_WAVES = 4, SUM_ROWS = 4;
+
+struct Sum {
+  double v[RS_SUM_COLS]; /* the columns of include/roadsurf.h: everything fp64, indices and counts are exact there */
+  __device__ void clear() {
+#pragma unroll
+    for (int c = 0; c < RS_SUM_COLS; ++c) v[c] = 0.0;
+    v[1] = __builtin_huge_val();
+    v[3] = -__builtin_huge_val();
+#pragma unroll
+    for (int k = 0; k < 5; ++k) v[7 + k] = -__builtin_huge_val();
+  }
+  /* extremes tie to the smaller index; a NaN, and the empty value itself, never wins (every comparison false) */
+  __device__ void lower(double t, double i) {
+    if (t < v[1] || (t == v[1] && i < v[2])) { v[1] = t; v[2] = i; }
+  }
+  __device__ void higher(double t, double i) {
+    if (t > v[3] || (t == v[3] && i < v[4])) { v[3] = t; v[4] = i; }
+  }
+  __device__ void first(double i) { /* i > 0 */
+    if (v[5] == 0.0 || i < v[5]) v[5] = i;
+  }
+  /* one row of the point: its time index, Tsurf and the five storages */
+  __device__ void row(double i, double t, const double s[5], const RsSummarySpec &sp) {
+    if (t == -9999.0) return; /* never saved: behind the last index of a failed point, or a rejected point */
+    v[0] += 1.0;
+    lower(t, i);
+    higher(t, i);
+    if (t < sp.tsurf_below) {
+      first(i);
+      v[6] += 1.0;
+    }
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+      if (s[k] > v[7 + k]) v[7 + k] = s[k];
+      if (s[k] > sp.storage_above[k]) v[12 + k] += 1.0;
+    }
+  }
+  /* the summary of this one's rows and o's together (disjoint rows) */
+  __device__ void merge(const Sum &o) {
+    v[0] += o.v[0];
+    lower(o.v[1], o.v[2]);
+    higher(o.v[3], o.v[4]);
+    if (o.v[5] != 0.0) first(o.v[5]);
+    v[6] += o.v[6];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+      if (o.v[7 + k] > v[7 + k]) v[7 + k] = o.v[7 + k];
+      v[12 + k] += o.v[12 + k];
+    }
+  }
+  __device__ void load(const double *p, int64_t stride) {
+#pragma unroll
+    for (int c = 0; c < RS_SUM_COLS; ++c) v[c] = p[c * stride];
+  }
+  __device__ void store(double *p, int64_t stride) const {
+#pragma unroll
+    for (int c = 0; c < RS_SUM_COLS; ++c) p[c * stride] = v[c];
+  }
+};
+
+struct SummaryArgs {
+  const void *src[6]; /* T[nrows][stride] each: Tsurf, Snow, Water, Ice, Deposit, Ice2 */
+  const int32_t *order; /* column s is point order[s]; NULL: point s (rs_driver_run's result block) */
+  double *acc;          /* [RS_SUM_COLS][np_pad], point order */
+  int64_t npoints, stride, np_pad;
+  int32_t nrows, index0, index_step;
+  RsSummarySpec spec;
+};
+
+template <typename T>
+__global__ void __launch_bounds__(64 * SUM_WAVES) outputs_summary_kernel(const SummaryArgs a) {
+  __shared__ double part[SUM_WAVES - 1][RS_SUM_COLS][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t s = (int64_t)blockIdx.x * 64 + lane;
+  const bool live = s < a.npoints;
+  Sum sum;
+  sum.clear();
+  const int32_t per = (a.nrows + SUM_WAVES - 1) / SUM_WAVES, r_lo = wave * per,
+                r_hi = a.nrows < r_lo + per ? a.nrows : r_lo + per;
+  if (live)
+#pragma unroll 1
+    for (int32_t r0 = r_lo; r0 < r_hi; r0 += SUM_ROWS) {
+      T x[SUM_ROWS][6];
+#pragma unroll
+      for (int q = 0; q < SUM_ROWS; ++q) {
+        const int32_t r = r0 + q < r_hi ? r0 + q : r_hi - 1; /* behind the range: its last row again, not taken */
+#pragma unroll
+        for (int f = 0; f < 6; ++f) x[q][f] = static_cast<const T *>(a.src[f])[(int64_t)r * a.stride + s];
+      }
+#pragma unroll
+      for (int q = 0; q < SUM_ROWS; ++q) {
+        if (r0 + q >= r_hi) break;
+        const double st[5] = {(double)x[q][1], (double)x[q][2], (double)x[q][3], (double)x[q][4], (double)x[q][5]};
+        sum.row((double)a.index0 + (double)(r0 + q) * (double)a.index_step, (double)x[q][0], st, a.spec);
+      }
+    }
+  if (wave > 0) sum.store(&part[wave - 1][0][lane], 64);
+  __syncthreads();
+  if (wave > 0 || !live) return;
+#pragma unroll 1
+  for (int w = 0; w < SUM_WAVES - 1; ++w) {
+    Sum o;
+    o.load(&part[w][0][lane], 64);
+    sum.merge(o);
+  }
+  const int64_t p = a.order ? (int64_t)a.order[s] : s;
+  if (p < 0 || p >= a.npoints) return; /* not an order row of this plan: nothing is written */
+  Sum g;
+  g.load(a.acc + p, a.np_pad);
+  g.merge(sum);
+  g.store(a.acc + p, a.np_pad);
+}
+
+__global__ void __launch_bounds__(RS_BLOCK) summary_reset_kernel(double *acc, int64_t np_pad) {
+  const int64_t p = (int64_t)blockIdx.x * RS_BLOCK + threadIdx.x;
+  if (p >= np_pad) return;
+  Sum e;
+  e.clear();
+  e.store(acc + p, np_pad);
+}
+}  // namespace
+
+hipError_t rs_cluster_summary_reset(double *acc, int64_t np_pad, hipStream_t stream) {
+  hipLaunchKernelGGL(summary_reset_kernel, grid1(np_pad), dim3(RS_BLOCK), 0, stream, acc, np_pad);
+  return hipGetLastError();
+}
+
+hipError_t rs_cluster_outputs_summary(const void *const src[6], bool f32, const int32_t *order, int64_t npoints,
+                                      int64_t src_stride, int32_t nrows, int32_t index0, int32_t index_step,
+                                      const RsSummarySpec &spec, double *acc, int64_t np_pad, hipStream_t stream) {
+  SummaryArgs a;
+  for (int f = 0; f < 6; ++f) a.src[f] = src[f];
+  a.order = order;
+  a.acc = acc;
+  a.npoints = npoints;
+  a.stride = src_stride;
+  a.np_pad = np_pad;
+  a.nrows = nrows;
+  a.index0 = index0;
+  a.index_step = index_step;
+  a.spec = spec;
+  const dim3 grid((unsigned)((npoints + 63) / 64)), block(64 * SUM_WAVES);
+  if (f32)
+    hipLaunchKernelGGL(outputs_summary_kernel<float>, grid, block, 0, stream, a);
+  else
+    hipLaunchKernelGGL(outputs_summary_kernel<double>, grid, block, 0, stream, a);
+  return hipGetLastError();
+}
+
 hipError_t rs_cluster_identity(int32_t *order, int64_t np_pad, hipStream_t stream) {
   hipLaunchKernelGGL(iota_kernel, grid1(np_pad), dim3(RS_BLOCK), 0, stream, order, np_pad);
   return hipGetLastError();

@@ -1388,6 +1388,7 @@ struct Run : Call {
   PhaseTimer &pt;
   WindowLease &win;
   size_t win_bytes; /* of the block `win` holds */
+  const RsDriverSummary *sum; /* NULL: no summaries (rs_driver_run) */
 };
 
 /* tiles the calling thread's last single-device rs_driver_run stepped (tests: the window budget), and how many
@@ -1417,6 +1418,7 @@ struct Tile : TileHead {
   Dev d_phase, d_out, d_outpt;    /* PrecPhase window; the six outputs [n_out][mp]; one of them [m][n_out] */
   Dev d_outc, d_pp_s, d_geo_s;    /* slot order: one launch's output rows, per-point parameters, geometry */
   Dev d_prev, d_row1;             /* preview rows of the forecast key; index 1's rows for the initial profile */
+  Dev d_sum, d_sumpt;             /* the summaries [RS_SUM_COLS][mp], and as the caller holds them [m][RS_SUM_COLS] */
   RsPointParams pp, pps;          /* in point order, in slot order */
   RsOutputs oo, oc;               /* the result [n_out][mp]; one launch's rows in slot order (rows_c) */
   size_t os = 0;                  /* mp * n_out */
@@ -1822,12 +1824,31 @@ struct Tile : TileHead {
     }
     return 0;
   }
+  /* The summaries of the kept rows [first_row, last_row] (rs_driver_run_summary): reduced from the result block, which
+   * is in point order, final (every coupling replay has rewritten its rows) and blanked where read_input rejected the
+   * point; RS_SUM_COLS doubles per point come home for them. */
+  int summaries_home() {
+    const RsDriverSummary &q = *r.sum;
+    HOK(d_sum.alloc((size_t)RS_SUM_COLS * mp * sizeof(double)));
+    HOK(d_sumpt.alloc((size_t)m * RS_SUM_COLS * sizeof(double)));
+    HOK(rs_cluster_summary_reset(d_sum.as<double>(), mp, stream));
+    const void *in[6];
+    for (int f = 0; f < 6; ++f) in[f] = d_out.as<double>() + (size_t)f * os + (size_t)q.first_row * mp;
+    HOK(rs_cluster_outputs_summary(in, false, nullptr, m, mp, q.last_row - q.first_row + 1, q.first_row * R.step + 1,
+                                   R.step, q.spec, d_sum.as<double>(), mp, stream));
+    HOK(transpose((const double *)d_sum.as<double>(), d_sumpt.as<double>(), RS_SUM_COLS, m, mp, RS_SUM_COLS, stream));
+    HOK(hipMemcpyAsync(q.summary + (size_t)p0 * RS_SUM_COLS, d_sumpt.p, (size_t)m * RS_SUM_COLS * sizeof(double),
+                       hipMemcpyDeviceToHost, stream));
+    return 0;
+  }
   /* blank what read_input rejected, then [row][point] -> [point][row] -> the caller's arrays */
   int outputs_home() {
     double *ob = d_out.as<double>();
     hipLaunchKernelGGL(blank_rejected_kernel, grid1(m), dim3(RS_BLOCK), 0, stream, ob, (int64_t)mp,
                        (int32_t)R.n_out, (int64_t)m, (const int32_t *)D.status.as<int32_t>());
     HOK(hipGetLastError());
+    if (r.sum)
+      if (int rc = summaries_home()) return rc;
     double *dst[6] = {r.out->tsurf, r.out->snow, r.out->water, r.out->ice, r.out->deposit, r.out->ice2};
     for (int f = 0; f < 6; ++f) {
       if (!dst[f]) continue;
@@ -1837,7 +1858,7 @@ struct Tile : TileHead {
     }
     HOK(hipStreamSynchronize(stream));
     r.pt.lap(5);
-    for (Dev *d : {&d_phase, &d_outc, &d_pp_s, &d_geo_s, &d_out, &d_outpt, &d_prev}) d->release();
+    for (Dev *d : {&d_phase, &d_outc, &d_pp_s, &d_geo_s, &d_out, &d_outpt, &d_prev, &d_sum, &d_sumpt}) d->release();
     r.pt.lap(7);
     return 0;
   }
@@ -1907,13 +1928,15 @@ int upload_shared_axes(const Call &k, const RunPolicy &R, int64_t pbeg, int64_t 
 
 /* points [pbeg, pend) of the input on one device */
 int driver_run_range(const RsDriverInput *in, const InputSettings *st, const InputParameters *params,
-                     LocalParameters *local, const RsDriverOutput *out, int32_t device, int64_t pbeg,
-                     int64_t pend) {
+                     LocalParameters *local, const RsDriverOutput *out, const RsDriverSummary *sum, int32_t device,
+                     int64_t pbeg, int64_t pend) {
   Common c;
   RunPolicy R;
   RsConstants consts;
   if (int rc = prepare(in, st, c)) return rc;
   if (int rc = check_run_arguments(in, st, params, local, out, c, R, consts)) return rc;
+  if (sum && (!sum->summary || sum->first_row < 0 || sum->last_row < sum->first_row || sum->last_row >= R.n_out))
+    return fail_msg("rs_driver_run_summary: summary is required, with 0 <= first_row <= last_row < n_out", -1);
   if (int rc = check_device(device)) return rc;
   HOK(hipSetDevice(device));
   StreamGuard sg; /* the worker's one stream: uploads, kernels and downloads of its tiles (upload_tile) */
@@ -1946,7 +1969,7 @@ int driver_run_range(const RsDriverInput *in, const InputSettings *st, const Inp
   const int rows0 = R.cpl_chunked ? std::max(R.TC, std::min(c.L, c.cplLen + 2)) : R.TC;
   Run run{call, params, out, R, pbeg, pend,
           rs_bottom_temperature(params, &consts, in->year[0], in->month[0], in->day[0]), ax, pt, win,
-          R.use_raw ? 0 : (size_t)R.nwin * Ppad * rows0 * sizeof(double)};
+          R.use_raw ? 0 : (size_t)R.nwin * Ppad * rows0 * sizeof(double), sum};
   if (run.win_bytes) HOK(win.acquire(run.win_bytes, device));
   pt.lap(6);
 
@@ -2063,10 +2086,18 @@ int rs_driver_last_raw_launches(void) { return g_last_raw_launches; }
  * reference driver's worker pool (examples/example1/src/roadrunner.cpp:423-501). */
 int rs_driver_run(const RsDriverInput *in, const InputSettings *st, const InputParameters *params,
                   LocalParameters *local, const RsDriverOutput *out, int32_t device) {
+  return rs_driver_run_summary(in, st, params, local, out, nullptr, device);
+}
+
+/* ... and with the summaries of the kept rows beside (or instead of) the series: every block fills its points' rows
+ * of the one host array */
+int rs_driver_run_summary(const RsDriverInput *in, const InputSettings *st, const InputParameters *params,
+                          LocalParameters *local, const RsDriverOutput *out, const RsDriverSummary *sum,
+                          int32_t device) {
   if (!in || in->n_points < 1) return fail_msg("rs_driver_run: bad arguments", -1);
   if (device >= 0) {
     rsu::g_last_fanout = 1;
-    return driver_run_range(in, st, params, local, out, device, 0, in->n_points);
+    return driver_run_range(in, st, params, local, out, sum, device, 0, in->n_points);
   }
   /* four blocks per device.  (Six for batches with local horizons were 4 % faster while the horizon table
    * was transposed on the device, tools/experiments/r4_blocks.sh; with the table left in the caller's layout
@@ -2078,7 +2109,7 @@ int rs_driver_run(const RsDriverInput *in, const InputSettings *st, const InputP
   const std::vector<rsu::Shard> shards =
       rsu::make_shards(in->n_points, rsu::device_list(), in->horizons ? 30 : RS_BLOCK_TAPER_PCT_DEFAULT);
   return rsu::fan_out(shards, [&](const rsu::Shard &sh, int) {
-    return driver_run_range(in, st, params, local, out, sh.device, sh.off, sh.off + sh.cnt);
+    return driver_run_range(in, st, params, local, out, sum, sh.device, sh.off, sh.off + sh.cnt);
   });
 }
 

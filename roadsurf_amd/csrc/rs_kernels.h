@@ -172,6 +172,12 @@ hipError_t rs_cluster_identity(int32_t *order, int64_t np_pad, hipStream_t strea
 hipError_t rs_cluster_outputs_by_point(const double *const src[6], double *const dst[6], const int32_t *order,
                                        int64_t npoints, int64_t src_stride, int32_t nrows, int64_t dst_rows,
                                        int64_t dst_row0, hipStream_t stream);
+/* per-point summaries of output rows (rs_hip_outputs_summary): acc[RS_SUM_COLS][np_pad] in point order;
+ * src: six T[nrows][src_stride] windows, T = float with f32; order NULL = column s is point s */
+hipError_t rs_cluster_summary_reset(double *acc, int64_t np_pad, hipStream_t stream);
+hipError_t rs_cluster_outputs_summary(const void *const src[6], bool f32, const int32_t *order, int64_t npoints,
+                                      int64_t src_stride, int32_t nrows, int32_t index0, int32_t index_step,
+                                      const RsSummarySpec &spec, double *acc, int64_t np_pad, hipStream_t stream);
 size_t rs_cluster_scratch_bytes(int64_t npoints);
 hipError_t rs_cluster_sort(const double *state, bool f32, int64_t np_pad, int64_t npoints,
                            uint32_t *scratch, void *tmp, size_t tmp_bytes, hipStream_t stream);

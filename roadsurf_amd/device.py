@@ -296,6 +296,38 @@ class Plan:
                                                  C.c_void_p(stream.cuda_stream) if stream is not None else None),
                   "rs_hip_outputs_by_point")
 
+    def summary_reset(self, acc: torch.Tensor | None = None, stream: torch.cuda.Stream | None = None) -> torch.Tensor:
+        """The empty summary into every column of ``acc``, float64 [RS_SUM_COLS, np_pad] on this device (made
+        here if None) - what ``outputs_summary`` accumulates into (rs_hip_summary_reset)."""
+        if acc is None:
+            acc = torch.empty((lib.RS_SUM_COLS, self.np_pad), dtype=torch.float64, device=self.device)
+        assert acc.dtype == torch.float64 and acc.shape == (lib.RS_SUM_COLS, self.np_pad) and acc.is_contiguous()
+        lib.check(self.L.rs_hip_summary_reset(self._h, C.c_void_p(acc.data_ptr()),
+                                              C.c_void_p(stream.cuda_stream) if stream is not None else None),
+                  "rs_hip_summary_reset")
+        return acc
+
+    def outputs_summary(self, out: "OutputWindow", nrows: int, index0: int, index_step: int, spec, acc: torch.Tensor,
+                        order=None, stream: torch.cuda.Stream | None = None, row: int = 0) -> None:
+        """Rows ``row .. row + nrows - 1`` of the output window, [row][slot], merged into the per-point summaries
+        ``acc`` [RS_SUM_COLS, np_pad] in POINT order (rs_hip_outputs_summary; roadsurf_amd/summary.py defines the
+        columns).  The first of these rows is the absolute 1-based time index ``index0``, the next ``index0 +
+        index_step``; ``spec``: summary.SummarySpec; ``order`` and ``stream`` as for ``outputs_by_point``."""
+        assert acc.dtype == torch.float64 and acc.shape == (lib.RS_SUM_COLS, self.np_pad) and acc.is_contiguous()
+        o = out.struct(0)
+        for n in OUT_FIELDS:
+            setattr(o, n, C.c_void_p(out.tensors[n][row].data_ptr()))
+        sp = lib.summary_spec(spec)
+        lib.check(self.L.rs_hip_outputs_summary(self._h, C.byref(o), int(nrows), int(index0), int(index_step),
+                                                C.c_void_p(order.data_ptr()) if order is not None else None,
+                                                C.byref(sp), C.c_void_p(acc.data_ptr()),
+                                                C.c_void_p(stream.cuda_stream) if stream is not None else None),
+                  "rs_hip_outputs_summary")
+
+    def summary(self, acc: torch.Tensor):
+        """``acc`` as the numpy array [npoints, RS_SUM_COLS] that summary.reduce_series returns (synchronises)."""
+        return acc[:, :self.npoints].T.contiguous().cpu().numpy()
+
     def reset_order(self) -> None:
         lib.check(self.L.rs_hip_plan_reset_order(self._h), "rs_hip_plan_reset_order")
 
@@ -362,10 +394,13 @@ class Plan:
 def run_points(forcing: dict, settings: abi.InputSettings, params: abi.InputParameters,
                local, chunk: int = 0, variant: int = 0, device: int = 0,
                lean_if_possible: bool = True, year_month_day=None, history_score: bool | None = None,
-               precision: int = 64, horizon_index=None):
+               precision: int = 64, horizon_index=None, summary=None):
     """Run host arrays ``forcing[name][n, SimLen]`` (numpy, reference layout) through the
     device-resident API and return outputs ``[n, SimLen]`` as numpy.  Test/bench helper:
-    transposes with torch on the device, windows of ``chunk`` steps (0 = whole series)."""
+    transposes with torch on the device, windows of ``chunk`` steps (0 = whole series).
+    ``summary``: a summary.SummarySpec - every launch's rows are also reduced on the device
+    (``Plan.outputs_summary``) and the result has ``summary`` [n, RS_SUM_COLS]; not with coupling,
+    whose replays rewrite rows that earlier launches wrote."""
     import numpy as np
 
     require_gpu()
@@ -455,6 +490,9 @@ def run_points(forcing: dict, settings: abi.InputSettings, params: abi.InputPara
     else:
         pp = plan.point_params(tb)
     out = OutputWindow.empty(L, npad, dev, dtype=wdt)
+    if summary is not None and coupled:
+        raise ValueError("run_points: no summary with coupling")
+    acc = plan.summary_reset() if summary is not None else None
     plan.init_state(win, pp)
     if coupled and chunk:
         # time-chunked coupling: lock-step chunks up to the last coupling-window end, the replay
@@ -485,9 +523,13 @@ def run_points(forcing: dict, settings: abi.InputSettings, params: abi.InputPara
         while t0 <= L:
             ns = min(chunk, L - t0 + 1)
             plan.step(win, out, pp, t0, ns, window_row=t0 - 1, out_row0=0)
+            if acc is not None:  # the rows this launch wrote: time indices t0 ... t0 + ns - 1
+                plan.outputs_summary(out, ns, t0, 1, summary, acc, row=t0 - 1)
             t0 += ns
     plan.sync()
     res = {k: out.tensors[k][:, :n].T.contiguous().double().cpu().numpy() for k in OUT_FIELDS}
+    if acc is not None:
+        res["summary"] = plan.summary(acc)
     nfail = plan.failed_count()
     plan.close()
     return res, nfail

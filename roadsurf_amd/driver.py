@@ -58,6 +58,11 @@ class RsDriverOutput(C.Structure):
     ]
 
 
+class RsDriverSummary(C.Structure):
+    _fields_ = [("spec", rslib.RsSummarySpec), ("first_row", C.c_int32), ("last_row", C.c_int32),
+                ("summary", abi.c_double_p)]
+
+
 @dataclasses.dataclass
 class RawSource:
     """One data source: ``fields`` name -> [n_points][n_times] float64 (absent name = variable
@@ -87,6 +92,14 @@ def output_rows(settings: abi.InputSettings) -> tuple[int, int]:
     if step < 1:
         raise ValueError("outputStep*60/DTSecs < 1")
     return step, (settings.SimLen + step - 1) // step
+
+
+def forecast_rows(settings: abi.InputSettings, start_time: int, forecast_time: int) -> tuple[int, int]:
+    """(first_row, last_row) of the kept rows at or behind ``forecast_time``: the forecast part of a run, what
+    ``run(..., summary_rows=...)`` is usually given."""
+    step, n_out = output_rows(settings)
+    i = max(0, -(-(int(forecast_time) - int(start_time)) // int(settings.DTSecs)))  # first 0-based index at or behind it
+    return min(-(-i // step), n_out - 1), n_out - 1
 
 
 def make_input(sources, start_time: int, forecast_time: int, cal: dict | None = None,
@@ -174,6 +187,9 @@ def _bind(L):
     P = C.POINTER
     L.rs_driver_run.argtypes = [P(RsDriverInput), P(abi.InputSettings), P(abi.InputParameters),
                                 P(abi.LocalParameters), P(RsDriverOutput), C.c_int32]
+    if hasattr(L, "rs_driver_run_summary"):
+        L.rs_driver_run_summary.argtypes = [P(RsDriverInput), P(abi.InputSettings), P(abi.InputParameters),
+                                            P(abi.LocalParameters), P(RsDriverOutput), P(RsDriverSummary), C.c_int32]
     L.rs_driver_expand.argtypes = [P(RsDriverInput), P(abi.InputSettings), P(abi.LocalParameters),
                                    abi.c_double_p, abi.c_int32_p, abi.c_int32_p, C.c_int32]
     return L
@@ -201,11 +217,16 @@ def read_input(sources, settings: abi.InputSettings, start_time: int, forecast_t
 
 def run(sources, settings: abi.InputSettings, params: abi.InputParameters, start_time: int,
         forecast_time: int, local=None, cal: dict | None = None,
-        horizons: np.ndarray | None = None, device: int = 0, out: dict | None = None) -> dict:
+        horizons: np.ndarray | None = None, device: int = 0, out: dict | None = None,
+        summary=None, summary_rows: tuple[int, int] | None = None, series: bool = True) -> dict:
     """read_input + runsimulation + save_output's decimation for all points.  Returns the six
     outputs as [n][n_out] arrays plus ``status``, ``missing_index``, ``local`` and ``step``.
     ``device`` < 0 fans the points out over ROADSURF_HIP_DEVICES; ``out`` = a result dict of an
-    earlier call with the same shapes, whose arrays are written again (no fresh allocation)."""
+    earlier call with the same shapes, whose arrays are written again (no fresh allocation).
+    ``summary`` = a summary.SummarySpec: the result also has ``summary``, float64 [n][RS_SUM_COLS], the per-point
+    summaries (roadsurf_amd/summary.py) of the kept rows ``summary_rows`` = (first_row, last_row) - default all
+    of them, ``forecast_rows`` gives the forecast part - reduced on the device (rs_driver_run_summary);
+    ``series=False`` then leaves the six series out of the result: nothing but the summaries is downloaded."""
     L = _bind(rslib.load())
     if cal is None:
         cal = calendar(start_time, settings.SimLen, int(settings.DTSecs))
@@ -213,20 +234,33 @@ def run(sources, settings: abi.InputSettings, params: abi.InputParameters, start
     n = inp.n_points
     step, n_out = output_rows(settings)
     larr = _locals(n, local)
-    if out is not None and out["tsurf"].shape == (n, n_out):
+    if not series and summary is None:
+        raise ValueError("series=False needs a summary")
+    if out is not None and series and out["tsurf"].shape == (n, n_out):
         res = {k: out[k] for k in OUT_FIELDS + ("status", "missing_index")}
     else:
-        res = {k: np.full((n, n_out), np.nan) for k in OUT_FIELDS}
+        res = {k: np.full((n, n_out), np.nan) for k in OUT_FIELDS} if series else {}
         res["status"] = np.empty(n, np.int32)
         res["missing_index"] = np.empty(n, np.int32)
     out = RsDriverOutput()
     out.n_out = n_out
-    for k in OUT_FIELDS:
-        setattr(out, k, res[k].ctypes.data_as(abi.c_double_p))
+    if series:  # (a NULL series pointer = not wanted)
+        for k in OUT_FIELDS:
+            setattr(out, k, res[k].ctypes.data_as(abi.c_double_p))
     out.status = res["status"].ctypes.data_as(abi.c_int32_p)
     out.missing_index = res["missing_index"].ctypes.data_as(abi.c_int32_p)
-    rslib.check(L.rs_driver_run(C.byref(inp), C.byref(settings), C.byref(params), larr,
-                                C.byref(out), device), "rs_driver_run")
+    if summary is None:
+        rslib.check(L.rs_driver_run(C.byref(inp), C.byref(settings), C.byref(params), larr,
+                                    C.byref(out), device), "rs_driver_run")
+    else:
+        if not hasattr(L, "rs_driver_run_summary") or L.rs_hip_summary_cols() != rslib.RS_SUM_COLS:
+            raise RuntimeError("this libroadsurf_hip.so has no summaries (rs_hip_summary_cols)")
+        first, last = (0, n_out - 1) if summary_rows is None else summary_rows
+        res["summary"] = np.full((n, rslib.RS_SUM_COLS), np.nan)
+        q = RsDriverSummary(rslib.summary_spec(summary), int(first), int(last),
+                            res["summary"].ctypes.data_as(abi.c_double_p))
+        rslib.check(L.rs_driver_run_summary(C.byref(inp), C.byref(settings), C.byref(params), larr,
+                                            C.byref(out), C.byref(q), device), "rs_driver_run_summary")
     del keep
     res["local"] = larr
     res["step"] = step

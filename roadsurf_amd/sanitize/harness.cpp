@@ -6,7 +6,7 @@
 //            limited to ROADSURF_HIP_COALESCE_MAX callers per batch (set by the test: 5 < threads)
 //   phase 2  threads that come and go (thread-local caches adopted by later threads, rs_host.hip CallerCache)
 //   phase 3  four concurrent runsimulation_batch calls of different sizes (arena / plan bookkeeping)
-//   phase 4  rs_driver_run from two threads (its shards, segment table and per-block worker threads)
+//   phase 4  rs_driver_run and rs_driver_run_summary from two threads (shards, segment table, per-block worker threads)
 // usage: harness [threads=64] [points=640]      exit code 0 and "sanitize harness ok" when every call returned
 #include <atomic>
 #include <cmath>
@@ -153,7 +153,16 @@ void driver_call(int n, int hours, bool coupling) {
   out.n_out = n_out;
   out.tsurf = o[0].data(); out.snow = o[1].data(); out.water = o[2].data(); out.ice = o[3].data(); out.deposit = o[4].data();
   out.ice2 = o[5].data(); out.status = status.data(); out.missing_index = missing.data();
-  const int rc = rs_driver_run(&in, &s, &p, local.data(), &out, -1);
+  /* the coupled call also asks for the per-point summaries of the second half of its rows: every block's worker fills
+   * its points' rows of the one host array */
+  std::vector<double> sums((size_t)n * RS_SUM_COLS, -1.0);
+  RsDriverSummary q;
+  std::memset(&q, 0, sizeof(q));
+  q.first_row = n_out / 2;
+  q.last_row = n_out - 1;
+  q.summary = sums.data();
+  const int rc = coupling ? rs_driver_run_summary(&in, &s, &p, local.data(), &out, &q, -1)
+                          : rs_driver_run(&in, &s, &p, local.data(), &out, -1);
   if (rc != 0) {
     fprintf(stderr, "rs_driver_run(%d points) -> %d: %s\n", n, rc, rs_last_error());
     g_errors++;

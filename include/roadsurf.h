@@ -273,11 +273,21 @@ double rs_bottom_temperature(const InputParameters *inputParam,
  *   carried state:      state[v * npoints_padded + p]
  * so a wavefront (64 consecutive points) reads/writes 512 contiguous bytes
  * per field per time step.
+ *
+ * Columns beyond npoints.  The kernels launch whole wavefronts over npoints_padded columns; the arrays are
+ * the caller's.  Arrays that need `npoints` elements: every array of RsPointParams and every row of a
+ * forcing or output window (t_stride >= npoints; the last row needs no more than npoints either).  Arrays
+ * whose rows have `npoints_padded` columns: the knots ([knot][RS_KNOT_FIELDS][npoints_padded]), the
+ * [360][npoints_padded] layout of `horizons`, the preview rows of RsPreview, a kept order row, a summary
+ * accumulator.  The CONTENT of columns beyond npoints is never interpreted, whatever it is (NaN, a
+ * neighbour's values, values CheckValues would reject), and nothing is ever written there - with the one
+ * exception of the pad columns of the plan's own state block (tests/test_hip_padding.py).
  * ---------------------------------------------------------------------- */
 
 typedef struct RsPlan RsPlan; /* opaque */
 
-/* One step-resolution forcing window resident on the device (device pointers).
+/* One step-resolution forcing window resident on the device (device pointers): rows of t_stride >= npoints
+ * elements, of which the first npoints are read (never written; rs_hip_expand_forcing writes those and no others).
  * Index t_local = 0 corresponds to absolute (1-based, reference) time index
  * `t0`.  Optional streams may be NULL:
  *   tsurfobs NULL -> all missing (-9999.9);  depth NULL -> all missing;
@@ -299,6 +309,7 @@ typedef struct RsForcing {
   const double *sun;
 } RsForcing;
 
+/* Output window: rows of t_stride >= npoints elements; only the first npoints of a row are ever written. */
 typedef struct RsOutputs {
   double *tsurf, *snow, *water, *ice, *deposit, *ice2;
   int64_t t_stride;
@@ -309,7 +320,7 @@ typedef struct RsOutputs {
                        row r - row0 */
 } RsOutputs;
 
-/* Per-point parameters (device pointers, [npoints]). */
+/* Per-point parameters (device pointers, [npoints] each: no kernel reads element npoints or beyond). */
 typedef struct RsPointParams {
   const double *tbottom;  /* Tmp(NLayers+1), src/Initialization.f90:267 */
   const int32_t *initlen; /* LocalParameters.InitLenI */
@@ -458,7 +469,9 @@ typedef struct RsSynthSpec {
                              point order[p] (plan-order windows, see rs_hip_recluster) */
 } RsSynthSpec;
 
-/* Number of doubles per point and knot in a knot buffer. */
+/* Number of doubles per point and knot in a knot buffer.  A knot buffer is [nknots][RS_KNOT_FIELDS][npoints_padded]:
+ * the row stride is the plan's; columns beyond npoints may hold anything and are never written by a consumer
+ * (rs_hip_synth_knots itself fills live columns only). */
 #define RS_KNOT_FIELDS 9
 /* The same generator on the host, in the layout the reference driver hands runsimulation: per-point
  * [n][simlen] series (InputPointers' eleven f64 arrays + PrecPhase) and the hour of every index (the shared

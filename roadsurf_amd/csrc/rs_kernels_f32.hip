@@ -695,14 +695,16 @@ __device__ __forceinline__ void x2d_ground(X2Mail &mail, const rs::StepArgs &a) 
   static_assert(!SKY || (FULL && SRC == X2_WINDOW), "sky view: the FULL feature set, from a forcing window");
   KernArgs ka = (KernArgs)__builtin_amdgcn_kernarg_segment_ptr();
   const uint32_t lane = threadIdx.x & 63u;
-  const int64_t p = 2 * ((int64_t)blockIdx.x * 64 + lane); /* < np_pad: every array below has np_pad columns */
+  /* p < np_pad.  The plan's own arrays (state block, order row) and the knots have np_pad columns; the caller's
+   * RsPointParams arrays have npoints elements (include/roadsurf.h) and are read for live points only. */
+  const int64_t p = 2 * ((int64_t)blockIdx.x * 64 + lane);
   const bool liveX = p < a.npoints, liveY = p + 1 < a.npoints;
   const int64_t np = a.np_pad;
   const float *st = reinterpret_cast<const float *>(a.state);
   f2 T[13]; /* Tmp(3..15) */
 #pragma unroll
   for (int j = 3; j <= 15; ++j) T[j - 3] = *reinterpret_cast<const f2 *>(st + (int64_t)(RS_ST_TMP0 + j - 1) * np + p);
-  const f2 tbot = f2{(float)ka->pp.tbottom[p], (float)ka->pp.tbottom[p + 1]};
+  const f2 tbot = f2{liveX ? (float)ka->pp.tbottom[p] : 0.f, liveY ? (float)ka->pp.tbottom[p + 1] : 0.f};
   const int32_t nsteps = ka->nsteps, t0 = ka->t0;
   rs::MathTab mt{nullptr, nullptr, nullptr};
   constexpr int NK = FULL ? 7 : 6; /* tair, vz, rhz, prec, sw, lw [, tdew] */
@@ -716,16 +718,16 @@ __device__ __forceinline__ void x2d_ground(X2Mail &mail, const rs::StepArgs &a) 
   f2 relax_dt = S2(0.f), relax_dv = S2(0.f), relax_dr = S2(0.f), tairR = S2(0.f), vzR = S2(0.f), rhR = S2(0.f);
   f2 obs_next = S2(-9999.9f); /* the observation forced at the index the mailbox is being filled for */
   if (FULL) {
-    if (ka->pp.initlen) initlen = i2{ka->pp.initlen[p], ka->pp.initlen[p + 1]};
+    if (ka->pp.initlen) initlen = i2{liveX ? ka->pp.initlen[p] : 0, liveY ? ka->pp.initlen[p + 1] : 0};
     if (consts_of(ka).use_relaxation && ka->pp.tair_relax) {
       /* the targets through REAL(4), src/InputOutput.f90:19-26 */
-      tairR = f2{(float)ka->pp.tair_relax[p], (float)ka->pp.tair_relax[p + 1]};
-      vzR = f2{(float)ka->pp.vz_relax[p], (float)ka->pp.vz_relax[p + 1]};
-      rhR = f2{(float)ka->pp.rh_relax[p], (float)ka->pp.rh_relax[p + 1]};
+      tairR = f2{liveX ? (float)ka->pp.tair_relax[p] : 0.f, liveY ? (float)ka->pp.tair_relax[p + 1] : 0.f};
+      vzR = f2{liveX ? (float)ka->pp.vz_relax[p] : 0.f, liveY ? (float)ka->pp.vz_relax[p + 1] : 0.f};
+      rhR = f2{liveX ? (float)ka->pp.rh_relax[p] : 0.f, liveY ? (float)ka->pp.rh_relax[p + 1] : 0.f};
       auto valid = [](float t, float v, float r) {
         return !(t < -100.0f || t > 100.0f || v < 0.0f || v > 100.0f || r < 0.0f || r > 110.f);
       };
-      relax = b2{valid(tairR.x, vzR.x, rhR.x), valid(tairR.y, vzR.y, rhR.y)};
+      relax = b2{liveX && valid(tairR.x, vzR.x, rhR.x), liveY && valid(tairR.y, vzR.y, rhR.y)};
       relax_dt = tairR - *reinterpret_cast<const f2 *>(st + (int64_t)RS_ST_TAIR_END * np + p);
       relax_dv = vzR - *reinterpret_cast<const f2 *>(st + (int64_t)RS_ST_VZ_END * np + p);
       relax_dr = rhR - *reinterpret_cast<const f2 *>(st + (int64_t)RS_ST_RH_END * np + p);
@@ -754,8 +756,8 @@ __device__ __forceinline__ void x2d_ground(X2Mail &mail, const rs::StepArgs &a) 
   }
   int64_t kcolx = p, kcoly = p + 1;
   if (SRC == X2_KNOTS && ka->knot_gather) {
-    kcolx = ka->knot_gather[p];
-    kcoly = ka->knot_gather[p + 1];
+    if (liveX) kcolx = ka->knot_gather[p]; /* a dead component keeps its own column */
+    if (liveY) kcoly = ka->knot_gather[p + 1];
   }
   const bool fvec = SRC == X2_WINDOW && !(ka->f.t_stride & 1) && liveY;
   /* the forcing's share of index `in` -> mailbox buffer `buf` */

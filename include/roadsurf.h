@@ -709,6 +709,55 @@ int rs_hip_summary_reset(RsPlan *plan, double *acc_device, void *stream);
 int rs_hip_outputs_summary(RsPlan *plan, const RsOutputs *src, int32_t nrows, int32_t index0, int32_t index_step,
                            const int32_t *order_device, const RsSummarySpec *spec, double *acc_device, void *stream);
 
+/* Per-group time series, reduced from the output rows on the device: the other axis - per row, over a set of points
+ * (the ABI number stays: every name here is new, a binding detects them with rs_hip_group_cols).  Every point has a
+ * group id, group_device[point] (int32, POINT order): a district of a road network, or the station whose ensemble
+ * members the points are.  An id outside [0, ngroups) belongs to no group and is ignored.  rs_hip_outputs_groups
+ * reads the first `nrows` rows of a window `src` ([row][slot], of any launch and any flavour; float arrays on an fp32
+ * plan, widened exactly) and merges row r into row acc_row0 + r of the accumulator of the caller,
+ *     acc_device[((acc_row0 + r) * ngroups + g) * cols + col],   g = group[order[slot]],   double,
+ * cols = rs_hip_group_cols(spec) = RS_GRP_COLS + (nedges ? nedges + 1 : 0):
+ *   0       number of VALID points of g at that row - valid iff Tsurf is not exactly -9999.0; only these count below
+ *   1, 2    min Tsurf, max Tsurf (+inf / -inf when there is none; a NaN never wins)
+ *   3       number of points with Tsurf < spec.thresholds.tsurf_below
+ *   4..8    number of points with Snow, Water, Ice, Deposit, Ice2 > spec.thresholds.storage_above[k]
+ *   9..13   max of Snow, Water, Ice, Deposit, Ice2 (-inf when none; a NaN never wins)
+ *   14..    histogram of Tsurf over spec.edges[nedges] (strictly increasing, nedges <= RS_GRP_MAX_EDGES): nedges + 1
+ *           bins, a valid non-NaN Tsurf falls into bin j = number of edges <= Tsurf (a value equal to an edge lies in
+ *           the upper bin, a NaN in no bin).  nedges = 0: no bins.
+ * Every comparison is strict; NaN compares false everywhere and still counts in column 0.  There are no sums and no
+ * means, on purpose: every column is a count (exact in fp64), a minimum or a maximum, so the merge of two cells is
+ * exact, commutative and associative, and the result does not depend on the order in which points, launches, tiles,
+ * plans or devices contribute - which is what lets the device use atomics and still equal the definition
+ * (roadsurf_amd/groups.py, reduce_groups) bit for bit.  Medians and percentiles come from the histogram.  Several
+ * plans may merge into one accumulator on the same device; feeding a point twice counts it twice (documented, not
+ * detected).  rs_hip_group_reset writes the empty cell (counts 0, min +inf, maxima -inf) into all acc_rows rows.
+ * A call is refused unless 0 <= acc_row0 and acc_row0 + nrows <= acc_rows; nothing outside rows [acc_row0, acc_row0 +
+ * nrows) is written.  `order_device` and `stream` as for rs_hip_outputs_summary: NULL = the plan's current order, on
+ * the plan's stream; a stream of the caller's only with a kept order row.  All six streams are required; t_stride >=
+ * npoints; columns of `src` at or beyond npoints are never read as points, and group_device is read at [0, npoints)
+ * only.  The call changes no value and not how the plan steps.
+ * Two kernels, chosen by the host from ngroups * cols alone (rs_hip_group_path): up to RS_GRP_LDS_CELLS doubles per row
+ * (districts) a workgroup keeps the cells of a block of rows in LDS, updates them with LDS atomics over many blocks of
+ * slots and flushes its non-empty cells with one global atomic each; beyond that (ensembles) lanes update the global
+ * cells directly.  fp64 add, min and max atomics are single instructions on gfx950 in LDS and in device memory; the
+ * accumulator must be ordinary (coarse-grained) device memory.  It reads 48 B per point and row (24 B of an fp32
+ * window); tools/bench_group_outputs.py measures the cost (its output is kept as profiles/group_outputs.txt). */
+#define RS_GRP_COLS 14
+#define RS_GRP_MAX_EDGES 31
+#define RS_GRP_LDS_CELLS 8192 /* ngroups * cols up to this: the LDS kernel (64 KiB of a CU's 160 KiB per workgroup) */
+typedef struct RsGroupSpec {
+  RsSummarySpec thresholds;
+  int32_t ngroups, nedges;
+  double edges[RS_GRP_MAX_EDGES];
+} RsGroupSpec;
+int32_t rs_hip_group_cols(const RsGroupSpec *spec); /* RS_GRP_COLS + (nedges ? nedges + 1 : 0); <0: bad spec */
+int32_t rs_hip_group_path(const RsGroupSpec *spec); /* 1: cells in LDS; 2: global cells directly; <0: bad spec */
+int rs_hip_group_reset(RsPlan *plan, double *acc_device, int64_t acc_rows, const RsGroupSpec *spec, void *stream);
+int rs_hip_outputs_groups(RsPlan *plan, const RsOutputs *src, int32_t nrows, const int32_t *group_device,
+                          const int32_t *order_device, const RsGroupSpec *spec, double *acc_device, int64_t acc_rows,
+                          int64_t acc_row0, void *stream);
+
 /* Device timing of the step kernel with HIP events recorded on the plan's
  * stream around every rs_hip_step launch since the last reset.  Returns the
  * summed milliseconds (synchronises on the last event) and the launch count. */
@@ -849,6 +898,24 @@ typedef struct RsDriverSummary {
 int rs_driver_run_summary(const RsDriverInput *in, const InputSettings *settings,
                           const InputParameters *params, LocalParameters *local,
                           const RsDriverOutput *out, const RsDriverSummary *summary, int32_t device);
+/* ... and with per-group series of the kept rows [first_row, last_row] (rs_hip_outputs_groups defines the cells):
+ * group[n_points] gives every point's group, and series[r - first_row][g][col] is the cell of kept row r.  They are
+ * reduced where the summaries are - from the tile's result block, behind the blanking of rejected points (whose rows
+ * are -9999.0 and count nowhere) and behind every coupling replay.  A block of points keeps one accumulator on its
+ * device across its tiles, and a tile's slice of `group` goes up with the tile; with device < 0 every block of the
+ * fan-out reduces its own and the host merges them by the rule of the definition.  Only rows x ngroups x cols doubles
+ * come home for them; the six series pointers of `out` may all be NULL.  `summary` may be NULL; `groups` NULL:
+ * rs_driver_run_summary. */
+typedef struct RsDriverGroups {
+  RsGroupSpec spec;
+  const int32_t *group; /* host [n_points] */
+  int32_t first_row, last_row;
+  double *series; /* host [last_row - first_row + 1][ngroups][cols] */
+} RsDriverGroups;
+int rs_driver_run_groups(const RsDriverInput *in, const InputSettings *settings,
+                         const InputParameters *params, LocalParameters *local,
+                         const RsDriverOutput *out, const RsDriverSummary *summary, const RsDriverGroups *groups,
+                         int32_t device);
 /* Tiles: a call steps its points in tiles of ROADSURF_HIP_TILE_POINTS (default 524 288).  With
  * coupling the forcing windows of a tile span [first coupling-window start, last window end + 1]
  * of ITS points; a tile whose windows would exceed ROADSURF_HIP_WINDOW_BUDGET_MB (default 24 576)

@@ -158,6 +158,8 @@ int64_t rs_abi_sizeof(int which) {
     case 14: return sizeof(RsDriverOutput);
     case 15: return sizeof(RsSummarySpec);
     case 16: return sizeof(RsDriverSummary);
+    case 17: return sizeof(RsGroupSpec);
+    case 18: return sizeof(RsDriverGroups);
     default: return -1;
   }
 }
@@ -515,6 +517,41 @@ int rs_hip_outputs_summary(RsPlan *pl, const RsOutputs *src, int32_t nrows, int3
   HIP_OK(hipSetDevice(pl->device));
   HIP_OK(rs_cluster_outputs_summary(in, pl->f32, order ? order : pl->order, pl->npoints, src->t_stride, nrows, index0,
                                     index_step, *spec, acc, pl->np_pad, stream ? (hipStream_t)stream : pl->stream));
+  return 0;
+}
+
+int32_t rs_hip_group_cols(const RsGroupSpec *spec) { return rs_cluster_group_cols(spec); }
+int32_t rs_hip_group_path(const RsGroupSpec *spec) { return rs_cluster_group_path(spec); }
+
+static const char *const GROUP_SPEC_MSG =
+    ": bad spec (ngroups >= 1, 0 <= nedges <= RS_GRP_MAX_EDGES, edges strictly increasing)";
+
+int rs_hip_group_reset(RsPlan *pl, double *acc, int64_t acc_rows, const RsGroupSpec *spec, void *stream) {
+  if (!pl || !acc || !spec || acc_rows < 1) return set_err("rs_hip_group_reset: bad arguments");
+  if (rs_cluster_group_cols(spec) < 0) return set_err("rs_hip_group_reset%s", GROUP_SPEC_MSG);
+  HIP_OK(hipSetDevice(pl->device));
+  HIP_OK(rs_cluster_group_reset(acc, acc_rows, *spec, stream ? (hipStream_t)stream : pl->stream));
+  return 0;
+}
+
+int rs_hip_outputs_groups(RsPlan *pl, const RsOutputs *src, int32_t nrows, const int32_t *group, const int32_t *order,
+                          const RsGroupSpec *spec, double *acc, int64_t acc_rows, int64_t acc_row0, void *stream) {
+  if (!pl || !src || !group || !spec || !acc || nrows < 1)
+    return set_err("rs_hip_outputs_groups: bad arguments (nrows >= 1 rows, a group row, a spec and an accumulator)");
+  const int32_t cols = rs_cluster_group_cols(spec);
+  if (cols < 0) return set_err("rs_hip_outputs_groups%s", GROUP_SPEC_MSG);
+  if (acc_row0 < 0 || acc_rows < 1 || acc_row0 > acc_rows - nrows)
+    return set_err("rs_hip_outputs_groups: rows [acc_row0, acc_row0 + nrows) outside the accumulator's acc_rows");
+  const void *in[6] = {src->tsurf, src->snow, src->water, src->ice, src->deposit, src->ice2};
+  for (int f = 0; f < 6; ++f)
+    if (!in[f]) return set_err("rs_hip_outputs_groups: all six streams are required");
+  if (src->t_stride < pl->npoints) return set_err("rs_hip_outputs_groups: t_stride below the plan's points");
+  if (!order && stream) return set_err("rs_hip_outputs_groups: on a stream of the caller's the order row must be a kept one");
+  if (!order && !rs_hip_plan_order(pl)) return -1;
+  HIP_OK(hipSetDevice(pl->device));
+  HIP_OK(rs_cluster_outputs_groups(in, pl->f32, order ? order : pl->order, group, pl->npoints, src->t_stride, nrows,
+                                   *spec, acc + acc_row0 * spec->ngroups * cols,
+                                   stream ? (hipStream_t)stream : pl->stream));
   return 0;
 }
 

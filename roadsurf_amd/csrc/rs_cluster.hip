@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
+#include <algorithm>
+
 #include "rs_kernels.h"
 #include "rs_state.h"
 
@@ -292,6 +294,206 @@ hipError_t rs_cluster_outputs_summary(const void *const src[6], bool f32, const 
     hipLaunchKernelGGL(outputs_summary_kernel<float>, grid, block, 0, stream, a);
   else
     hipLaunchKernelGGL(outputs_summary_kernel<double>, grid, block, 0, stream, a);
+  return hipGetLastError();
+}
+
+/* Per-group time series of the output rows (include/roadsurf.h, rs_hip_outputs_groups; the definition is
+ * roadsurf_amd/groups.py, reduce_groups): the second sibling, reducing over the slots of a row instead of the rows of
+ * a slot.  Many slots fold into one cell acc[row][group][col], so the cells are updated with atomics - every column is
+ * a count, a minimum or a maximum, whose fp64 atomics are exact and order-free, and lanes filter NaN before the
+ * atomic.  A lane owns a slot, gathers its group id once and keeps it over the rows it reads, GRP_ROWS rows of the six
+ * streams in flight, every row load a coalesced 512 B per wavefront and stream.
+ *   groups_lds_kernel     ngroups * cols <= RS_GRP_LDS_CELLS.  A workgroup takes a block of rows_per_block rows
+ *                         (blockIdx.y) and every gridDim.x-th block of 256 slots, keeps rows x ngroups x cols cells in
+ *                         LDS, updates them with LDS atomics - the extremes behind a plain read of the cell, which can
+ *                         only be staler, that is less extreme, than the cell: an update it skips would not have
+ *                         changed it - and ends by flushing its non-empty cells with global atomics, consecutive lanes
+ *                         on consecutive doubles: a global cell is hit once per workgroup, not once per point.
+ *   groups_global_kernel  more cells than that: lanes update the global cells directly. */
+namespace {
+constexpr int GRP_THREADS = 256, GRP_ROWS = 4;
+
+struct GroupArgs {
+  const void *src[6];   /* T[nrows][stride] each: Tsurf, Snow, Water, Ice, Deposit, Ice2 */
+  const int32_t *order; /* column s is point order[s]; NULL: point s (rs_driver_run's result block) */
+  const int32_t *group; /* [npoints], point order */
+  double *acc;          /* [nrows][ngroups][cols]: row acc_row0 of the caller's accumulator */
+  int64_t npoints, stride;
+  int32_t nrows, ngroups, cols, nedges, rows_per_block;
+  RsSummarySpec th;
+  double edges[RS_GRP_MAX_EDGES];
+};
+
+/* the empty value of column c: counts 0, min +inf, maxima -inf */
+__device__ __forceinline__ double grp_empty(int c) {
+  return c == 1 ? __builtin_huge_val() : (c == 2 || (c >= 9 && c < RS_GRP_COLS)) ? -__builtin_huge_val() : 0.0;
+}
+
+/* the group of slot s, or -1: no point, or a point of no group */
+__device__ __forceinline__ int32_t grp_of_slot(const GroupArgs &a, int64_t s) {
+  if (s >= a.npoints) return -1;
+  const int64_t p = a.order ? (int64_t)a.order[s] : s;
+  if (p < 0 || p >= a.npoints) return -1; /* not an order row of this plan */
+  const int32_t g = a.group[p];
+  return g >= 0 && g < a.ngroups ? g : -1;
+}
+
+/* One point's row into its cell `c`, in LDS (SCOPE workgroup, PEEK) or in device memory (SCOPE agent). */
+template <int SCOPE, bool PEEK>
+__device__ __forceinline__ void grp_update(double *c, double t, const double s[5], const GroupArgs &a) {
+  if (t == -9999.0) return; /* never saved: behind the last index of a failed point, or a rejected point */
+  __hip_atomic_fetch_add(c + 0, 1.0, __ATOMIC_RELAXED, SCOPE);
+  /* a NaN fails every comparison here and so never reaches a min or max atomic */
+  if (PEEK ? t < __hip_atomic_load(c + 1, __ATOMIC_RELAXED, SCOPE) : t == t)
+    __hip_atomic_fetch_min(c + 1, t, __ATOMIC_RELAXED, SCOPE);
+  if (PEEK ? t > __hip_atomic_load(c + 2, __ATOMIC_RELAXED, SCOPE) : t == t)
+    __hip_atomic_fetch_max(c + 2, t, __ATOMIC_RELAXED, SCOPE);
+  if (t < a.th.tsurf_below) __hip_atomic_fetch_add(c + 3, 1.0, __ATOMIC_RELAXED, SCOPE);
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    if (s[k] > a.th.storage_above[k]) __hip_atomic_fetch_add(c + 4 + k, 1.0, __ATOMIC_RELAXED, SCOPE);
+    if (PEEK ? s[k] > __hip_atomic_load(c + 9 + k, __ATOMIC_RELAXED, SCOPE) : s[k] == s[k])
+      __hip_atomic_fetch_max(c + 9 + k, s[k], __ATOMIC_RELAXED, SCOPE);
+  }
+  if (a.nedges > 0 && t == t) {
+    int j = 0;
+    for (int e = 0; e < a.nedges; ++e) j += a.edges[e] <= t ? 1 : 0;
+    __hip_atomic_fetch_add(c + RS_GRP_COLS + j, 1.0, __ATOMIC_RELAXED, SCOPE);
+  }
+}
+
+/* rows [r_lo, r_hi) of slot s into the cells cell0 + (r - r_lo) * row_cells */
+template <typename T, int SCOPE, bool PEEK>
+__device__ __forceinline__ void grp_rows(const GroupArgs &a, int64_t s, int32_t r_lo, int32_t r_hi, double *cell0,
+                                         int64_t row_cells) {
+#pragma unroll 1
+  for (int32_t r0 = r_lo; r0 < r_hi; r0 += GRP_ROWS) {
+    T x[GRP_ROWS][6];
+#pragma unroll
+    for (int q = 0; q < GRP_ROWS; ++q) {
+      const int32_t r = r0 + q < r_hi ? r0 + q : r_hi - 1; /* behind the range: its last row again, not taken */
+#pragma unroll
+      for (int f = 0; f < 6; ++f) x[q][f] = static_cast<const T *>(a.src[f])[(int64_t)r * a.stride + s];
+    }
+#pragma unroll
+    for (int q = 0; q < GRP_ROWS; ++q) {
+      if (r0 + q >= r_hi) break;
+      const double st[5] = {(double)x[q][1], (double)x[q][2], (double)x[q][3], (double)x[q][4], (double)x[q][5]};
+      grp_update<SCOPE, PEEK>(cell0 + (int64_t)(r0 + q - r_lo) * row_cells, (double)x[q][0], st, a);
+    }
+  }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(GRP_THREADS) groups_lds_kernel(const GroupArgs a) {
+  extern __shared__ double grp_tab[]; /* [rows of the block][ngroups][cols] */
+  const int32_t r_lo = (int32_t)blockIdx.y * a.rows_per_block,
+                r_hi = a.nrows < r_lo + a.rows_per_block ? a.nrows : r_lo + a.rows_per_block;
+  const int32_t row_cells = a.ngroups * a.cols, n_tab = (r_hi - r_lo) * row_cells;
+  for (int32_t i = threadIdx.x; i < n_tab; i += GRP_THREADS) grp_tab[i] = grp_empty(i % a.cols);
+  __syncthreads();
+#pragma unroll 1
+  for (int64_t s = (int64_t)blockIdx.x * GRP_THREADS + threadIdx.x; s < a.npoints;
+       s += (int64_t)gridDim.x * GRP_THREADS) {
+    const int32_t g = grp_of_slot(a, s);
+    if (g < 0) continue;
+    grp_rows<T, __HIP_MEMORY_SCOPE_WORKGROUP, true>(a, s, r_lo, r_hi, grp_tab + g * a.cols, row_cells);
+  }
+  __syncthreads();
+  /* the flush: cells with a point, and in them only the columns that say something */
+  double *dst = a.acc + (int64_t)r_lo * row_cells;
+  for (int32_t i = threadIdx.x; i < n_tab; i += GRP_THREADS) {
+    const int32_t c = i % a.cols;
+    if (grp_tab[i - c] == 0.0) continue;
+    const double v = grp_tab[i];
+    if (v == grp_empty(c)) continue;
+    if (c == 1)
+      __hip_atomic_fetch_min(dst + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else if (c == 2 || (c >= 9 && c < RS_GRP_COLS))
+      __hip_atomic_fetch_max(dst + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else
+      __hip_atomic_fetch_add(dst + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(GRP_THREADS) groups_global_kernel(const GroupArgs a) {
+  const int64_t s = (int64_t)blockIdx.x * GRP_THREADS + threadIdx.x;
+  const int32_t g = grp_of_slot(a, s);
+  if (g < 0) return;
+  const int64_t row_cells = (int64_t)a.ngroups * a.cols;
+  grp_rows<T, __HIP_MEMORY_SCOPE_AGENT, false>(a, s, 0, a.nrows, a.acc + (int64_t)g * a.cols, row_cells);
+}
+
+__global__ void __launch_bounds__(RS_BLOCK) group_reset_kernel(double *acc, int64_t n, int32_t cols) {
+  const int64_t i = (int64_t)blockIdx.x * RS_BLOCK + threadIdx.x;
+  if (i < n) acc[i] = grp_empty((int)(i % cols));
+}
+}  // namespace
+
+int32_t rs_cluster_group_cols(const RsGroupSpec *sp) {
+  if (!sp || sp->ngroups < 1 || sp->nedges < 0 || sp->nedges > RS_GRP_MAX_EDGES) return -1;
+  for (int e = 0; e < sp->nedges; ++e)
+    if (sp->edges[e] != sp->edges[e] || (e > 0 && !(sp->edges[e] > sp->edges[e - 1]))) return -1;
+  return RS_GRP_COLS + (sp->nedges ? sp->nedges + 1 : 0);
+}
+
+/* the one place that chooses the kernel: a row of cells fits the workgroup's LDS, or it does not */
+int32_t rs_cluster_group_path(const RsGroupSpec *sp) {
+  const int32_t cols = rs_cluster_group_cols(sp);
+  if (cols < 0) return -1;
+  return (int64_t)sp->ngroups * cols <= RS_GRP_LDS_CELLS ? 1 : 2;
+}
+
+hipError_t rs_cluster_group_reset(double *acc, int64_t acc_rows, const RsGroupSpec &spec, hipStream_t stream) {
+  const int32_t cols = rs_cluster_group_cols(&spec);
+  if (cols < 0 || acc_rows < 1) return hipErrorInvalidValue;
+  const int64_t n = acc_rows * spec.ngroups * cols;
+  hipLaunchKernelGGL(group_reset_kernel, grid1(n), dim3(RS_BLOCK), 0, stream, acc, n, cols);
+  return hipGetLastError();
+}
+
+hipError_t rs_cluster_outputs_groups(const void *const src[6], bool f32, const int32_t *order, const int32_t *group,
+                                     int64_t npoints, int64_t src_stride, int32_t nrows, const RsGroupSpec &spec,
+                                     double *acc_row0, hipStream_t stream) {
+  const int32_t path = rs_cluster_group_path(&spec);
+  if (path < 0 || nrows < 1 || npoints < 1) return hipErrorInvalidValue;
+  GroupArgs a;
+  for (int f = 0; f < 6; ++f) a.src[f] = src[f];
+  a.order = order;
+  a.group = group;
+  a.acc = acc_row0;
+  a.npoints = npoints;
+  a.stride = src_stride;
+  a.nrows = nrows;
+  a.ngroups = spec.ngroups;
+  a.cols = rs_cluster_group_cols(&spec);
+  a.nedges = spec.nedges;
+  a.th = spec.thresholds;
+  for (int e = 0; e < RS_GRP_MAX_EDGES; ++e) a.edges[e] = e < spec.nedges ? spec.edges[e] : 0.0;
+  const int64_t slot_blocks = (npoints + GRP_THREADS - 1) / GRP_THREADS;
+  if (path == 1) {
+    /* as many rows per workgroup as are in flight per lane, fewer where the cells of that many exceed the LDS budget;
+     * about a thousand workgroups in all, each looping over its share of the slot blocks */
+    const int32_t row_cells = spec.ngroups * a.cols;
+    a.rows_per_block = std::max(1, std::min({GRP_ROWS, RS_GRP_LDS_CELLS / row_cells, nrows}));
+    const int64_t row_blocks = (nrows + a.rows_per_block - 1) / a.rows_per_block;
+    if (row_blocks > 65535) return hipErrorInvalidValue; /* (the callers feed such windows in pieces) */
+    const dim3 grid((unsigned)std::min<int64_t>(slot_blocks, std::max<int64_t>(1, 1024 / row_blocks)),
+                    (unsigned)row_blocks);
+    const size_t lds = (size_t)a.rows_per_block * row_cells * sizeof(double);
+    if (f32)
+      hipLaunchKernelGGL(groups_lds_kernel<float>, grid, dim3(GRP_THREADS), lds, stream, a);
+    else
+      hipLaunchKernelGGL(groups_lds_kernel<double>, grid, dim3(GRP_THREADS), lds, stream, a);
+  } else {
+    a.rows_per_block = nrows;
+    const dim3 grid((unsigned)slot_blocks);
+    if (f32)
+      hipLaunchKernelGGL(groups_global_kernel<float>, grid, dim3(GRP_THREADS), 0, stream, a);
+    else
+      hipLaunchKernelGGL(groups_global_kernel<double>, grid, dim3(GRP_THREADS), 0, stream, a);
+  }
   return hipGetLastError();
 }
 

@@ -1389,6 +1389,8 @@ struct Run : Call {
   WindowLease &win;
   size_t win_bytes; /* of the block `win` holds */
   const RsDriverSummary *sum; /* NULL: no summaries (rs_driver_run) */
+  const RsDriverGroups *grp;  /* NULL: no group series */
+  double *grp_acc;            /* device [rows][ngroups][cols]: this block's cells, merged into by every tile */
 };
 
 /* tiles the calling thread's last single-device rs_driver_run stepped (tests: the window budget), and how many
@@ -1419,6 +1421,7 @@ struct Tile : TileHead {
   Dev d_outc, d_pp_s, d_geo_s;    /* slot order: one launch's output rows, per-point parameters, geometry */
   Dev d_prev, d_row1;             /* preview rows of the forecast key; index 1's rows for the initial profile */
   Dev d_sum, d_sumpt;             /* the summaries [RS_SUM_COLS][mp], and as the caller holds them [m][RS_SUM_COLS] */
+  Dev d_gid;                      /* the tile's slice of RsDriverGroups::group */
   RsPointParams pp, pps;          /* in point order, in slot order */
   RsOutputs oo, oc;               /* the result [n_out][mp]; one launch's rows in slot order (rows_c) */
   size_t os = 0;                  /* mp * n_out */
@@ -1841,6 +1844,18 @@ struct Tile : TileHead {
                        hipMemcpyDeviceToHost, stream));
     return 0;
   }
+  /* The group series of the kept rows [first_row, last_row] (rs_driver_run_groups), from the same final, blanked
+   * result block: the tile's points merge into the block's accumulator, which comes home behind the last tile. */
+  int groups_home() {
+    const RsDriverGroups &q = *r.grp;
+    HOK(d_gid.alloc((size_t)m * sizeof(int32_t)));
+    HOK(hipMemcpyAsync(d_gid.p, q.group + p0, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    const void *in[6];
+    for (int f = 0; f < 6; ++f) in[f] = d_out.as<double>() + (size_t)f * os + (size_t)q.first_row * mp;
+    HOK(rs_cluster_outputs_groups(in, false, nullptr, d_gid.as<int32_t>(), m, mp, q.last_row - q.first_row + 1, q.spec,
+                                  r.grp_acc, stream));
+    return 0;
+  }
   /* blank what read_input rejected, then [row][point] -> [point][row] -> the caller's arrays */
   int outputs_home() {
     double *ob = d_out.as<double>();
@@ -1849,6 +1864,8 @@ struct Tile : TileHead {
     HOK(hipGetLastError());
     if (r.sum)
       if (int rc = summaries_home()) return rc;
+    if (r.grp)
+      if (int rc = groups_home()) return rc;
     double *dst[6] = {r.out->tsurf, r.out->snow, r.out->water, r.out->ice, r.out->deposit, r.out->ice2};
     for (int f = 0; f < 6; ++f) {
       if (!dst[f]) continue;
@@ -1858,7 +1875,7 @@ struct Tile : TileHead {
     }
     HOK(hipStreamSynchronize(stream));
     r.pt.lap(5);
-    for (Dev *d : {&d_phase, &d_outc, &d_pp_s, &d_geo_s, &d_out, &d_outpt, &d_prev, &d_sum, &d_sumpt}) d->release();
+    for (Dev *d : {&d_phase, &d_outc, &d_pp_s, &d_geo_s, &d_out, &d_outpt, &d_prev, &d_sum, &d_sumpt, &d_gid}) d->release();
     r.pt.lap(7);
     return 0;
   }
@@ -1926,10 +1943,34 @@ int upload_shared_axes(const Call &k, const RunPolicy &R, int64_t pbeg, int64_t 
   return 0;
 }
 
+/* a and b merged into a, cells of `cols` numbers each: counts add, extremes are the extremes of the two
+ * (roadsurf_amd/groups.py, merge) */
+void merge_group_cells(double *a, const double *b, size_t ncells, int cols) {
+  for (size_t i = 0; i < ncells; ++i, a += cols, b += cols)
+    for (int c = 0; c < cols; ++c) {
+      if (c == 1)
+        a[c] = b[c] < a[c] ? b[c] : a[c];
+      else if (c == 2 || (c >= 9 && c < RS_GRP_COLS))
+        a[c] = b[c] > a[c] ? b[c] : a[c];
+      else
+        a[c] += b[c];
+    }
+}
+std::mutex g_group_merge; /* the blocks of a fan-out merge into the caller's one array */
+
+int check_groups(const RsDriverGroups *grp, int n_out) {
+  if (!grp) return 0;
+  if (rs_cluster_group_cols(&grp->spec) < 0)
+    return fail_msg("rs_driver_run_groups: bad spec (ngroups >= 1, nedges <= RS_GRP_MAX_EDGES, edges strictly increasing)", -1);
+  if (!grp->group || !grp->series || grp->first_row < 0 || grp->last_row < grp->first_row || grp->last_row >= n_out)
+    return fail_msg("rs_driver_run_groups: group and series are required, with 0 <= first_row <= last_row < n_out", -1);
+  return 0;
+}
+
 /* points [pbeg, pend) of the input on one device */
 int driver_run_range(const RsDriverInput *in, const InputSettings *st, const InputParameters *params,
-                     LocalParameters *local, const RsDriverOutput *out, const RsDriverSummary *sum, int32_t device,
-                     int64_t pbeg, int64_t pend) {
+                     LocalParameters *local, const RsDriverOutput *out, const RsDriverSummary *sum,
+                     const RsDriverGroups *grp, int32_t device, int64_t pbeg, int64_t pend) {
   Common c;
   RunPolicy R;
   RsConstants consts;
@@ -1937,11 +1978,19 @@ int driver_run_range(const RsDriverInput *in, const InputSettings *st, const Inp
   if (int rc = check_run_arguments(in, st, params, local, out, c, R, consts)) return rc;
   if (sum && (!sum->summary || sum->first_row < 0 || sum->last_row < sum->first_row || sum->last_row >= R.n_out))
     return fail_msg("rs_driver_run_summary: summary is required, with 0 <= first_row <= last_row < n_out", -1);
+  if (int rc = check_groups(grp, R.n_out)) return rc;
   if (int rc = check_device(device)) return rc;
   HOK(hipSetDevice(device));
   StreamGuard sg; /* the worker's one stream: uploads, kernels and downloads of its tiles (upload_tile) */
   HOK(hipStreamCreate(&sg.s));
   const hipStream_t stream = sg.s;
+  Dev d_grp; /* this block's group cells, kept across its tiles (its own allocation: the arena is the tiles') */
+  const size_t grp_cells = grp ? (size_t)(grp->last_row - grp->first_row + 1) * grp->spec.ngroups : 0;
+  const int grp_cols = grp ? rs_cluster_group_cols(&grp->spec) : 0;
+  if (grp) {
+    HOK(d_grp.alloc(grp_cells * grp_cols * sizeof(double)));
+    HOK(rs_cluster_group_reset(d_grp.as<double>(), grp->last_row - grp->first_row + 1, grp->spec, stream));
+  }
   make_run_policy(st, consts, c, local, pbeg, pend, R);
   const Call call{in, st, c, consts, device, stream, local, out->status, out->missing_index};
 
@@ -1969,7 +2018,7 @@ int driver_run_range(const RsDriverInput *in, const InputSettings *st, const Inp
   const int rows0 = R.cpl_chunked ? std::max(R.TC, std::min(c.L, c.cplLen + 2)) : R.TC;
   Run run{call, params, out, R, pbeg, pend,
           rs_bottom_temperature(params, &consts, in->year[0], in->month[0], in->day[0]), ax, pt, win,
-          R.use_raw ? 0 : (size_t)R.nwin * Ppad * rows0 * sizeof(double), sum};
+          R.use_raw ? 0 : (size_t)R.nwin * Ppad * rows0 * sizeof(double), sum, grp, d_grp.as<double>()};
   if (run.win_bytes) HOK(win.acquire(run.win_bytes, device));
   pt.lap(6);
 
@@ -2004,6 +2053,13 @@ int driver_run_range(const RsDriverInput *in, const InputSettings *st, const Inp
     p0 += m;
     ++g_last_tiles;
     Pcur = R.P; /* the next tile starts at full size again */
+  }
+  if (grp) { /* (every tile ended with a synchronisation: the accumulator is final) */
+    std::vector<double> part(grp_cells * grp_cols);
+    HOK(hipMemcpyAsync(part.data(), d_grp.p, part.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HOK(hipStreamSynchronize(stream));
+    std::lock_guard<std::mutex> lk(g_group_merge);
+    merge_group_cells(grp->series, part.data(), grp_cells, grp_cols);
   }
   pt.report();
   return 0;
@@ -2094,10 +2150,27 @@ int rs_driver_run(const RsDriverInput *in, const InputSettings *st, const InputP
 int rs_driver_run_summary(const RsDriverInput *in, const InputSettings *st, const InputParameters *params,
                           LocalParameters *local, const RsDriverOutput *out, const RsDriverSummary *sum,
                           int32_t device) {
+  return rs_driver_run_groups(in, st, params, local, out, sum, nullptr, device);
+}
+
+/* ... and with the group series of the kept rows: every block reduces its points into cells of its own on its device,
+ * and merges them into the caller's array when its last tile is home */
+int rs_driver_run_groups(const RsDriverInput *in, const InputSettings *st, const InputParameters *params,
+                         LocalParameters *local, const RsDriverOutput *out, const RsDriverSummary *sum,
+                         const RsDriverGroups *grp, int32_t device) {
   if (!in || in->n_points < 1) return fail_msg("rs_driver_run: bad arguments", -1);
+  if (grp) {
+    if (!out) return fail_msg("rs_driver_run: bad arguments", -1);
+    if (int rc = check_groups(grp, out->n_out)) return rc;
+    const int cols = rs_cluster_group_cols(&grp->spec);
+    const size_t ncells = (size_t)(grp->last_row - grp->first_row + 1) * grp->spec.ngroups;
+    for (size_t i = 0; i < ncells; ++i) /* the empty cell: what merge_group_cells starts from */
+      for (int c = 0; c < cols; ++c)
+        grp->series[i * cols + c] = c == 1 ? HUGE_VAL : (c == 2 || (c >= 9 && c < RS_GRP_COLS)) ? -HUGE_VAL : 0.0;
+  }
   if (device >= 0) {
     rsu::g_last_fanout = 1;
-    return driver_run_range(in, st, params, local, out, sum, device, 0, in->n_points);
+    return driver_run_range(in, st, params, local, out, sum, grp, device, 0, in->n_points);
   }
   /* four blocks per device.  (Six for batches with local horizons were 4 % faster while the horizon table
    * was transposed on the device, tools/experiments/r4_blocks.sh; with the table left in the caller's layout
@@ -2109,7 +2182,7 @@ int rs_driver_run_summary(const RsDriverInput *in, const InputSettings *st, cons
   const std::vector<rsu::Shard> shards =
       rsu::make_shards(in->n_points, rsu::device_list(), in->horizons ? 30 : RS_BLOCK_TAPER_PCT_DEFAULT);
   return rsu::fan_out(shards, [&](const rsu::Shard &sh, int) {
-    return driver_run_range(in, st, params, local, out, sum, sh.device, sh.off, sh.off + sh.cnt);
+    return driver_run_range(in, st, params, local, out, sum, grp, sh.device, sh.off, sh.off + sh.cnt);
   });
 }
 

@@ -178,6 +178,15 @@ hipError_t rs_cluster_summary_reset(double *acc, int64_t np_pad, hipStream_t str
 hipError_t rs_cluster_outputs_summary(const void *const src[6], bool f32, const int32_t *order, int64_t npoints,
                                       int64_t src_stride, int32_t nrows, int32_t index0, int32_t index_step,
                                       const RsSummarySpec &spec, double *acc, int64_t np_pad, hipStream_t stream);
+/* per-group series of output rows (rs_hip_outputs_groups): acc_row0[nrows][ngroups][cols] is the caller's accumulator
+ * from its row acc_row0 on; group[npoints] in point order; src and order as above.  rs_cluster_group_cols checks the
+ * spec (<0: bad), rs_cluster_group_path chooses the kernel (1: cells in LDS, 2: global cells directly) */
+int32_t rs_cluster_group_cols(const RsGroupSpec *spec);
+int32_t rs_cluster_group_path(const RsGroupSpec *spec);
+hipError_t rs_cluster_group_reset(double *acc, int64_t acc_rows, const RsGroupSpec &spec, hipStream_t stream);
+hipError_t rs_cluster_outputs_groups(const void *const src[6], bool f32, const int32_t *order, const int32_t *group,
+                                     int64_t npoints, int64_t src_stride, int32_t nrows, const RsGroupSpec &spec,
+                                     double *acc_row0, hipStream_t stream);
 size_t rs_cluster_scratch_bytes(int64_t npoints);
 hipError_t rs_cluster_sort(const double *state, bool f32, int64_t np_pad, int64_t npoints,
                            uint32_t *scratch, void *tmp, size_t tmp_bytes, hipStream_t stream);

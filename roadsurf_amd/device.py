@@ -328,6 +328,45 @@ class Plan:
         """``acc`` as the numpy array [npoints, RS_SUM_COLS] that summary.reduce_series returns (synchronises)."""
         return acc[:, :self.npoints].T.contiguous().cpu().numpy()
 
+    def groups_reset(self, nrows: int, spec, acc: torch.Tensor | None = None,
+                     stream: torch.cuda.Stream | None = None) -> torch.Tensor:
+        """The empty cell into every cell of ``acc``, float64 [nrows, ngroups, cols] on this device (made here if
+        None) - what ``outputs_groups`` accumulates into (rs_hip_group_reset); ``spec``: groups.GroupSpec."""
+        sp = lib.group_spec(spec)
+        shape = (int(nrows), int(sp.ngroups), lib.group_cols(sp))
+        if acc is None:
+            acc = torch.empty(shape, dtype=torch.float64, device=self.device)
+        assert acc.dtype == torch.float64 and acc.shape == shape and acc.is_contiguous()
+        lib.check(self.L.rs_hip_group_reset(self._h, C.c_void_p(acc.data_ptr()), int(nrows), C.byref(sp),
+                                            C.c_void_p(stream.cuda_stream) if stream is not None else None),
+                  "rs_hip_group_reset")
+        return acc
+
+    def outputs_groups(self, out: "OutputWindow", nrows: int, group: torch.Tensor, spec, acc: torch.Tensor,
+                       acc_row0: int, order=None, stream: torch.cuda.Stream | None = None, row: int = 0) -> None:
+        """Rows ``row .. row + nrows - 1`` of the output window, [row][slot], merged into rows ``acc_row0 ..`` of the
+        per-group series ``acc`` [rows, ngroups, cols] (rs_hip_outputs_groups; roadsurf_amd/groups.py defines the
+        cells).  ``group``: int32 [npoints] on this device, every point's group in POINT order; ``spec``:
+        groups.GroupSpec; ``order`` and ``stream`` as for ``outputs_by_point``."""
+        assert acc.dtype == torch.float64 and acc.dim() == 3 and acc.is_contiguous()
+        assert group.dtype == torch.int32 and group.numel() >= self.npoints and group.is_contiguous()
+        o = out.struct(0)
+        for n in OUT_FIELDS:
+            setattr(o, n, C.c_void_p(out.tensors[n][row].data_ptr()))
+        sp = lib.group_spec(spec)
+        lib.check(self.L.rs_hip_outputs_groups(self._h, C.byref(o), int(nrows), C.c_void_p(group.data_ptr()),
+                                               C.c_void_p(order.data_ptr()) if order is not None else None,
+                                               C.byref(sp), C.c_void_p(acc.data_ptr()), int(acc.shape[0]),
+                                               int(acc_row0),
+                                               C.c_void_p(stream.cuda_stream) if stream is not None else None),
+                  "rs_hip_outputs_groups")
+
+    def groups(self, acc: torch.Tensor, spec=None):
+        """``acc`` as the numpy array [rows, ngroups, cols] that groups.reduce_groups returns (synchronises)."""
+        a = acc.cpu().numpy()
+        assert spec is None or a.shape[1:] == (int(spec.ngroups), lib.group_cols(spec))
+        return a
+
     def reset_order(self) -> None:
         lib.check(self.L.rs_hip_plan_reset_order(self._h), "rs_hip_plan_reset_order")
 
@@ -394,13 +433,15 @@ class Plan:
 def run_points(forcing: dict, settings: abi.InputSettings, params: abi.InputParameters,
                local, chunk: int = 0, variant: int = 0, device: int = 0,
                lean_if_possible: bool = True, year_month_day=None, history_score: bool | None = None,
-               precision: int = 64, horizon_index=None, summary=None):
+               precision: int = 64, horizon_index=None, summary=None, groups=None):
     """Run host arrays ``forcing[name][n, SimLen]`` (numpy, reference layout) through the
     device-resident API and return outputs ``[n, SimLen]`` as numpy.  Test/bench helper:
     transposes with torch on the device, windows of ``chunk`` steps (0 = whole series).
     ``summary``: a summary.SummarySpec - every launch's rows are also reduced on the device
     (``Plan.outputs_summary``) and the result has ``summary`` [n, RS_SUM_COLS]; not with coupling,
-    whose replays rewrite rows that earlier launches wrote."""
+    whose replays rewrite rows that earlier launches wrote.  ``groups``: (groups.GroupSpec, group ids int32 [n]) -
+    every launch's rows are also reduced over the points of each group (``Plan.outputs_groups``) and the result
+    has ``groups`` [SimLen, ngroups, cols], row r being time index r + 1; not with coupling either."""
     import numpy as np
 
     require_gpu()
@@ -493,6 +534,13 @@ def run_points(forcing: dict, settings: abi.InputSettings, params: abi.InputPara
     if summary is not None and coupled:
         raise ValueError("run_points: no summary with coupling")
     acc = plan.summary_reset() if summary is not None else None
+    if groups is not None and coupled:
+        raise ValueError("run_points: no groups with coupling")
+    gacc = gid = None
+    if groups is not None:
+        gid = torch.from_numpy(np.ascontiguousarray(groups[1], dtype=np.int32)).to(dev)
+        assert gid.shape == (n,)
+        gacc = plan.groups_reset(L, groups[0])
     plan.init_state(win, pp)
     if coupled and chunk:
         # time-chunked coupling: lock-step chunks up to the last coupling-window end, the replay
@@ -525,11 +573,15 @@ def run_points(forcing: dict, settings: abi.InputSettings, params: abi.InputPara
             plan.step(win, out, pp, t0, ns, window_row=t0 - 1, out_row0=0)
             if acc is not None:  # the rows this launch wrote: time indices t0 ... t0 + ns - 1
                 plan.outputs_summary(out, ns, t0, 1, summary, acc, row=t0 - 1)
+            if gacc is not None:
+                plan.outputs_groups(out, ns, gid, groups[0], gacc, t0 - 1, row=t0 - 1)
             t0 += ns
     plan.sync()
     res = {k: out.tensors[k][:, :n].T.contiguous().double().cpu().numpy() for k in OUT_FIELDS}
     if acc is not None:
         res["summary"] = plan.summary(acc)
+    if gacc is not None:
+        res["groups"] = plan.groups(gacc, groups[0])
     nfail = plan.failed_count()
     plan.close()
     return res, nfail

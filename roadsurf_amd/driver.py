@@ -63,6 +63,11 @@ class RsDriverSummary(C.Structure):
                 ("summary", abi.c_double_p)]
 
 
+class RsDriverGroups(C.Structure):
+    _fields_ = [("spec", rslib.RsGroupSpec), ("group", abi.c_int32_p), ("first_row", C.c_int32),
+                ("last_row", C.c_int32), ("series", abi.c_double_p)]
+
+
 @dataclasses.dataclass
 class RawSource:
     """One data source: ``fields`` name -> [n_points][n_times] float64 (absent name = variable
@@ -190,6 +195,10 @@ def _bind(L):
     if hasattr(L, "rs_driver_run_summary"):
         L.rs_driver_run_summary.argtypes = [P(RsDriverInput), P(abi.InputSettings), P(abi.InputParameters),
                                             P(abi.LocalParameters), P(RsDriverOutput), P(RsDriverSummary), C.c_int32]
+    if hasattr(L, "rs_driver_run_groups"):
+        L.rs_driver_run_groups.argtypes = [P(RsDriverInput), P(abi.InputSettings), P(abi.InputParameters),
+                                           P(abi.LocalParameters), P(RsDriverOutput), P(RsDriverSummary),
+                                           P(RsDriverGroups), C.c_int32]
     L.rs_driver_expand.argtypes = [P(RsDriverInput), P(abi.InputSettings), P(abi.LocalParameters),
                                    abi.c_double_p, abi.c_int32_p, abi.c_int32_p, C.c_int32]
     return L
@@ -218,7 +227,8 @@ def read_input(sources, settings: abi.InputSettings, start_time: int, forecast_t
 def run(sources, settings: abi.InputSettings, params: abi.InputParameters, start_time: int,
         forecast_time: int, local=None, cal: dict | None = None,
         horizons: np.ndarray | None = None, device: int = 0, out: dict | None = None,
-        summary=None, summary_rows: tuple[int, int] | None = None, series: bool = True) -> dict:
+        summary=None, summary_rows: tuple[int, int] | None = None, series: bool = True,
+        groups=None, group_of=None, group_rows: tuple[int, int] | None = None) -> dict:
     """read_input + runsimulation + save_output's decimation for all points.  Returns the six
     outputs as [n][n_out] arrays plus ``status``, ``missing_index``, ``local`` and ``step``.
     ``device`` < 0 fans the points out over ROADSURF_HIP_DEVICES; ``out`` = a result dict of an
@@ -226,7 +236,11 @@ def run(sources, settings: abi.InputSettings, params: abi.InputParameters, start
     ``summary`` = a summary.SummarySpec: the result also has ``summary``, float64 [n][RS_SUM_COLS], the per-point
     summaries (roadsurf_amd/summary.py) of the kept rows ``summary_rows`` = (first_row, last_row) - default all
     of them, ``forecast_rows`` gives the forecast part - reduced on the device (rs_driver_run_summary);
-    ``series=False`` then leaves the six series out of the result: nothing but the summaries is downloaded."""
+    ``series=False`` then leaves the six series out of the result: nothing but the summaries is downloaded.
+    ``groups`` = a groups.GroupSpec with ``group_of`` = every point's group id, int32 [n]: the result also has
+    ``groups``, float64 [rows][ngroups][cols], the per-group series (roadsurf_amd/groups.py) of the kept rows
+    ``group_rows`` = (first_row, last_row), default all of them (rs_driver_run_groups); counts as a summary for
+    ``series=False``."""
     L = _bind(rslib.load())
     if cal is None:
         cal = calendar(start_time, settings.SimLen, int(settings.DTSecs))
@@ -234,8 +248,8 @@ def run(sources, settings: abi.InputSettings, params: abi.InputParameters, start
     n = inp.n_points
     step, n_out = output_rows(settings)
     larr = _locals(n, local)
-    if not series and summary is None:
-        raise ValueError("series=False needs a summary")
+    if not series and summary is None and groups is None:
+        raise ValueError("series=False needs a summary or groups")
     if out is not None and series and out["tsurf"].shape == (n, n_out):
         res = {k: out[k] for k in OUT_FIELDS + ("status", "missing_index")}
     else:
@@ -249,16 +263,31 @@ def run(sources, settings: abi.InputSettings, params: abi.InputParameters, start
             setattr(out, k, res[k].ctypes.data_as(abi.c_double_p))
     out.status = res["status"].ctypes.data_as(abi.c_int32_p)
     out.missing_index = res["missing_index"].ctypes.data_as(abi.c_int32_p)
-    if summary is None:
-        rslib.check(L.rs_driver_run(C.byref(inp), C.byref(settings), C.byref(params), larr,
-                                    C.byref(out), device), "rs_driver_run")
-    else:
+    q = g = None
+    if summary is not None:
         if not hasattr(L, "rs_driver_run_summary") or L.rs_hip_summary_cols() != rslib.RS_SUM_COLS:
             raise RuntimeError("this libroadsurf_hip.so has no summaries (rs_hip_summary_cols)")
         first, last = (0, n_out - 1) if summary_rows is None else summary_rows
         res["summary"] = np.full((n, rslib.RS_SUM_COLS), np.nan)
         q = RsDriverSummary(rslib.summary_spec(summary), int(first), int(last),
                             res["summary"].ctypes.data_as(abi.c_double_p))
+    if groups is not None:
+        if not hasattr(L, "rs_driver_run_groups"):
+            raise RuntimeError("this libroadsurf_hip.so has no group series (rs_driver_run_groups)")
+        gfirst, glast = (0, n_out - 1) if group_rows is None else (int(group_rows[0]), int(group_rows[1]))
+        gid = np.ascontiguousarray(group_of, dtype=np.int32)
+        if gid.shape != (n,):
+            raise ValueError("group_of: one group id per point")
+        res["groups"] = np.full((max(glast - gfirst + 1, 1), int(groups.ngroups), rslib.group_cols(groups)), np.nan)
+        g = RsDriverGroups(rslib.group_spec(groups), gid.ctypes.data_as(abi.c_int32_p), gfirst, glast,
+                           res["groups"].ctypes.data_as(abi.c_double_p))
+        rslib.check(L.rs_driver_run_groups(C.byref(inp), C.byref(settings), C.byref(params), larr, C.byref(out),
+                                           C.byref(q) if q is not None else None, C.byref(g), device),
+                    "rs_driver_run_groups")
+    elif summary is None:
+        rslib.check(L.rs_driver_run(C.byref(inp), C.byref(settings), C.byref(params), larr,
+                                    C.byref(out), device), "rs_driver_run")
+    else:
         rslib.check(L.rs_driver_run_summary(C.byref(inp), C.byref(settings), C.byref(params), larr,
                                             C.byref(out), C.byref(q), device), "rs_driver_run_summary")
     del keep

@@ -93,6 +93,15 @@ class RsSummarySpec(C.Structure):
     _fields_ = [("tsurf_below", C.c_double), ("storage_above", C.c_double * 5)]
 
 
+RS_GRP_COLS = 14
+RS_GRP_MAX_EDGES = 31
+
+
+class RsGroupSpec(C.Structure):
+    _fields_ = [("thresholds", RsSummarySpec), ("ngroups", C.c_int32), ("nedges", C.c_int32),
+                ("edges", C.c_double * RS_GRP_MAX_EDGES)]
+
+
 class RsSynthSpec(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("point_offset", C.c_int64),
                 ("steps_per_knot", C.c_int32), ("start_hour", C.c_int32), ("order", C.c_void_p)]
@@ -107,8 +116,8 @@ EXPORTS = (
     "rs_hip_plan_npoints", "rs_hip_plan_npoints_padded", "rs_hip_plan_state_bytes",
     "rs_hip_init_state", "rs_hip_step", "rs_hip_step_cpl", "rs_hip_cpl_replay", "rs_hip_set_output_by_point", "rs_hip_state_download", "rs_hip_state_upload",
     "rs_hip_failed_count", "rs_hip_clock_probe", "rs_hip_first_failed_index", "rs_hip_set_diagnostics", "rs_hip_diagnostics", "rs_hip_sync", "rs_hip_synth_knots", "rs_hip_expand_forcing", "rs_hip_expand_forcing_ordered", "rs_hip_step_knots", "rs_hip_expand_forcing_on",
-    "rs_hip_plan_order", "rs_hip_recluster", "rs_hip_recluster_forecast", "rs_hip_set_history_score", "rs_hip_coupling_windows_closed", "rs_hip_set_writeback", "rs_hip_plan_order_copy", "rs_hip_outputs_by_point", "rs_hip_summary_cols", "rs_hip_summary_reset", "rs_hip_outputs_summary", "rs_hip_plan_reset_order", "rs_hip_set_variant", "rs_hip_set_precision", "rs_hip_test_math", "rs_hip_division_mode", "rs_hip_div_mismatch_count", "rs_hip_div_special_count", "rs_hip_div_samples", "rs_hip_timing_reset", "rs_hip_timing_step_ms", "rs_hip_timing_intervals",
-    "rs_host_run_batch", "rs_last_fanout", "rs_driver_run", "rs_driver_run_summary", "rs_driver_last_tiles", "rs_driver_last_raw_launches", "rs_hip_bl_stats", "rs_compat_begin", "rs_compat_step", "rs_compat_replay", "rs_compat_failed_index", "rs_compat_last_state", "rs_compat_outputs", "rs_compat_end", "rs_driver_expand", "rs_driver_release_cache", "rs_abi_version", "rs_abi_sizeof", "rs_fortran_sizeof",
+    "rs_hip_plan_order", "rs_hip_recluster", "rs_hip_recluster_forecast", "rs_hip_set_history_score", "rs_hip_coupling_windows_closed", "rs_hip_set_writeback", "rs_hip_plan_order_copy", "rs_hip_outputs_by_point", "rs_hip_summary_cols", "rs_hip_summary_reset", "rs_hip_outputs_summary", "rs_hip_group_cols", "rs_hip_group_path", "rs_hip_group_reset", "rs_hip_outputs_groups", "rs_hip_plan_reset_order", "rs_hip_set_variant", "rs_hip_set_precision", "rs_hip_test_math", "rs_hip_division_mode", "rs_hip_div_mismatch_count", "rs_hip_div_special_count", "rs_hip_div_samples", "rs_hip_timing_reset", "rs_hip_timing_step_ms", "rs_hip_timing_intervals",
+    "rs_host_run_batch", "rs_last_fanout", "rs_driver_run", "rs_driver_run_summary", "rs_driver_run_groups", "rs_driver_last_tiles", "rs_driver_last_raw_launches", "rs_hip_bl_stats", "rs_compat_begin", "rs_compat_step", "rs_compat_replay", "rs_compat_failed_index", "rs_compat_last_state", "rs_compat_outputs", "rs_compat_end", "rs_driver_expand", "rs_driver_release_cache", "rs_abi_version", "rs_abi_sizeof", "rs_fortran_sizeof",
 )
 
 _lib = None
@@ -205,6 +214,14 @@ def load() -> C.CDLL:
         L.rs_hip_summary_reset.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.rs_hip_outputs_summary.argtypes = [C.c_void_p, P(RsOutputs), C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                              P(RsSummarySpec), C.c_void_p, C.c_void_p]
+    if hasattr(L, "rs_hip_group_cols"):  # ... nor for the group series
+        L.rs_hip_group_cols.restype = C.c_int32
+        L.rs_hip_group_cols.argtypes = [P(RsGroupSpec)]
+        L.rs_hip_group_path.restype = C.c_int32
+        L.rs_hip_group_path.argtypes = [P(RsGroupSpec)]
+        L.rs_hip_group_reset.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, P(RsGroupSpec), C.c_void_p]
+        L.rs_hip_outputs_groups.argtypes = [C.c_void_p, P(RsOutputs), C.c_int32, C.c_void_p, C.c_void_p, P(RsGroupSpec),
+                                            C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
     L.rs_hip_plan_reset_order.argtypes = [C.c_void_p]
     L.rs_hip_set_variant.argtypes = [C.c_void_p, C.c_int32]
     L.rs_hip_set_precision.argtypes = [C.c_void_p, C.c_int32]
@@ -241,6 +258,38 @@ def summary_spec(spec) -> RsSummarySpec:
     if len(above) != 5:
         raise ValueError("storage_above: five thresholds (snow, water, ice, deposit, ice2)")
     return RsSummarySpec(float(spec.tsurf_below), (C.c_double * 5)(*above))
+
+
+def group_spec(spec) -> RsGroupSpec:
+    """RsGroupSpec of anything with ``thresholds``, ``ngroups`` and ``edges`` (groups.GroupSpec).  More edges than
+    the struct holds are cut to that many and their number kept: the library refuses the spec."""
+    if isinstance(spec, RsGroupSpec):
+        return spec
+    edges = [float(x) for x in spec.edges]
+    g = RsGroupSpec()
+    g.thresholds = summary_spec(spec.thresholds)
+    g.ngroups = int(spec.ngroups)
+    g.nedges = len(edges)
+    for i, e in enumerate(edges[:RS_GRP_MAX_EDGES]):
+        g.edges[i] = e
+    return g
+
+
+def group_cols(spec) -> int:
+    """Numbers per cell of this spec as the library counts them (rs_hip_group_cols); raises on a spec it refuses."""
+    L = load()
+    if not hasattr(L, "rs_hip_group_cols"):
+        raise RuntimeError("this libroadsurf_hip.so has no group series (rs_hip_group_cols)")
+    n = L.rs_hip_group_cols(C.byref(group_spec(spec)))
+    if n < 0:
+        raise RuntimeError("rs_hip_group_cols: bad spec (ngroups >= 1, at most RS_GRP_MAX_EDGES edges, strictly increasing)")
+    return n
+
+
+def group_path(spec) -> str:
+    """Which kernel the host chooses for this spec (rs_hip_group_path): "lds" or "global"."""
+    group_cols(spec)
+    return {1: "lds", 2: "global"}[load().rs_hip_group_path(C.byref(group_spec(spec)))]
 
 
 def last_error() -> str:

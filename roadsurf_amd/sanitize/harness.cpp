@@ -6,7 +6,9 @@
 //            limited to ROADSURF_HIP_COALESCE_MAX callers per batch (set by the test: 5 < threads)
 //   phase 2  threads that come and go (thread-local caches adopted by later threads, rs_host.hip CallerCache)
 //   phase 3  four concurrent runsimulation_batch calls of different sizes (arena / plan bookkeeping)
-//   phase 4  rs_driver_run and rs_driver_run_summary from two threads (shards, segment table, per-block worker threads)
+//   phase 4  rs_driver_run_groups, which rs_driver_run and rs_driver_run_summary are calls of, with and without the
+//            summaries from two threads (shards, segment table, per-block worker threads, the blocks' merge into the
+//            one array of group series)
 // usage: harness [threads=64] [points=640]      exit code 0 and "sanitize harness ok" when every call returned
 #include <atomic>
 #include <cmath>
@@ -161,8 +163,28 @@ void driver_call(int n, int hours, bool coupling) {
   q.first_row = n_out / 2;
   q.last_row = n_out - 1;
   q.summary = sums.data();
-  const int rc = coupling ? rs_driver_run_summary(&in, &s, &p, local.data(), &out, &q, -1)
-                          : rs_driver_run(&in, &s, &p, local.data(), &out, -1);
+  /* ... and both calls for the group series of the same rows, three groups with bins: every block's worker merges its
+   * cells into the one host array */
+  RsDriverGroups g;
+  std::memset(&g, 0, sizeof(g));
+  g.spec.ngroups = 3;
+  g.spec.nedges = 2;
+  g.spec.edges[0] = -1.0;
+  g.spec.edges[1] = 1.0;
+  std::vector<int32_t> gid(n);
+  for (int k = 0; k < n; ++k) gid[k] = k % 4 - 1; /* -1: no group */
+  const int32_t gcols = rs_hip_group_cols(&g.spec);
+  if (gcols != RS_GRP_COLS + 3) {
+    fprintf(stderr, "rs_hip_group_cols -> %d\n", gcols);
+    g_errors++;
+    return;
+  }
+  std::vector<double> cells((size_t)(n_out - n_out / 2) * 3 * gcols, -1.0);
+  g.group = gid.data();
+  g.first_row = n_out / 2;
+  g.last_row = n_out - 1;
+  g.series = cells.data();
+  const int rc = rs_driver_run_groups(&in, &s, &p, local.data(), &out, coupling ? &q : nullptr, &g, -1);
   if (rc != 0) {
     fprintf(stderr, "rs_driver_run(%d points) -> %d: %s\n", n, rc, rs_last_error());
     g_errors++;

@@ -758,6 +758,36 @@ int rs_hip_outputs_groups(RsPlan *plan, const RsOutputs *src, int32_t nrows, con
                           const int32_t *order_device, const RsGroupSpec *spec, double *acc_device, int64_t acc_rows,
                           int64_t acc_row0, void *stream);
 
+/* Gridded fields gathered to points on the device (the ABI number stays: every name here is new, a binding detects
+ * them with rs_hip_grid_max_stencil).  A weather model delivers fields [time][node]; every kernel here reads series
+ * [time][point].  Each point has a stencil of `stencil` nodes, node_device[point * stencil + k] (int32) with weights
+ * weight_device[point * stencil + k] - bilinear, nearest neighbour, a mask, an unstructured mesh: projections are the
+ * caller's business - and rs_hip_gather_nodes writes, for every row r < nrows and slot s < npoints,
+ *     dst_device[r * dst_stride + s] = w0 * a0 + w1 * a1 + ...,   ak = src_device[r * src_stride + node k],
+ * point = order[s], by these rules (the definition, in numpy: roadsurf_amd/grid.py, gather_nodes):
+ *   - a term whose weight is exactly 0.0 does not exist: its node is not looked at, whatever it holds (NaN, a missing
+ *     value, an index out of range);
+ *   - a value is PRESENT iff it is > present_above (the reference's own test, `> -100.0`; a NaN is absent).  If any
+ *     existing term is absent, or its node lies outside [0, n_nodes), or no term exists, the result is missing_value;
+ *   - else the existing terms are added in stencil order, every product and every sum rounded on its own (no fused
+ *     multiply-add): one node with weight 1.0 gives the node's bits, -0.0 included.
+ * An out-of-range node under a non-zero weight yields missing_value: the index is compared before anything is loaded
+ * through it, so no argument makes the kernel read outside `src`.  Columns of `dst` at or beyond npoints are never
+ * written; node_device and weight_device are read at points [0, npoints) only.  src_stride >= n_nodes, dst_stride >=
+ * npoints, 1 <= stencil <= RS_GRID_MAX_STENCIL.  `order_device` and `stream` as for rs_hip_outputs_summary: NULL = the
+ * plan's current order (slot = point on a plan that was never re-sorted), on the plan's stream; a stream of the
+ * caller's only with a kept order row.  One point per lane, the stencil in registers, rows in the loop: the reads are
+ * scattered (neighbours along a road share nodes, the caches serve most of them), the writes whole lines, all offsets
+ * 64-bit.  A row of the hourly knots a layer-1 caller keeps resident, [RS_KNOT_FIELDS][npoints_padded], is exactly a
+ * `dst`.  rs_driver_run_grid uses it for sources that arrive as fields; tools/bench_grid_source.py measures it (its
+ * output is kept as profiles/grid_source.txt). */
+#define RS_GRID_MAX_STENCIL 4
+int32_t rs_hip_grid_max_stencil(void); /* RS_GRID_MAX_STENCIL of the library */
+int rs_hip_gather_nodes(RsPlan *plan, const double *src_device, int32_t nrows, int64_t n_nodes, int64_t src_stride,
+                        const int32_t *node_device, const double *weight_device, int32_t stencil,
+                        const int32_t *order_device, double present_above, double missing_value,
+                        double *dst_device, int64_t dst_stride, void *stream);
+
 /* Device timing of the step kernel with HIP events recorded on the plan's
  * stream around every rs_hip_step launch since the last reset.  Returns the
  * summed milliseconds (synchronises on the last event) and the launch count. */
@@ -916,6 +946,29 @@ int rs_driver_run_groups(const RsDriverInput *in, const InputSettings *settings,
                          const InputParameters *params, LocalParameters *local,
                          const RsDriverOutput *out, const RsDriverSummary *summary, const RsDriverGroups *groups,
                          int32_t device);
+/* ... and with sources that arrive as the weather model delivers them: fields [n_times][n_nodes] plus one stencil per
+ * point (rs_hip_gather_nodes defines the gather; its presence threshold is the reference's own, `> -100.0`, for lw_net
+ * `> -1000.0`, and its missing value -9999.9).  grids[s] != NULL makes source s a gridded one: in->sources[s] then
+ * supplies n_times, times and is_observation only - a shared time axis, every field pointer and `lengths` NULL - and
+ * the call computes exactly what it computes when the caller gathers every field to the points on the host
+ * (roadsurf_amd/grid.py, to_raw_source) and passes the result per point.  The fields of a gridded source go to every
+ * device of the call ONCE, before its blocks start (the blocks of a fan-out that share a device share the copy; it is
+ * freed when the call returns), a tile uploads its slice of `node` and `weight` instead of field rows, and the raw
+ * columns [n_times][point] are filled by the gather kernel instead of a transpose; everything behind them runs as it
+ * does for per-point sources.  Before any device work the host checks every gridded source - stencil in
+ * 1..RS_GRID_MAX_STENCIL, finite weights, every node under a non-zero weight inside [0, n_nodes) - and refuses the
+ * call with the first offending point named.  `grids` NULL, or all its entries NULL: rs_driver_run_groups. */
+typedef struct RsGridSource {
+  int64_t n_nodes;
+  const double *tair, *rhz, *tdew, *vz, *prec, *lw_net, *lw, *sw, *sw_dir, *tsurfobs; /* host [n_times][n_nodes]; NULL = absent */
+  int32_t stencil;      /* 1..RS_GRID_MAX_STENCIL */
+  const int32_t *node;  /* host [n_points][stencil] */
+  const double *weight; /* host [n_points][stencil] */
+} RsGridSource;
+int rs_driver_run_grid(const RsDriverInput *in, const RsGridSource *const *grids /* [n_sources] */,
+                       const InputSettings *settings, const InputParameters *params, LocalParameters *local,
+                       const RsDriverOutput *out, const RsDriverSummary *summary, const RsDriverGroups *groups,
+                       int32_t device);
 /* Tiles: a call steps its points in tiles of ROADSURF_HIP_TILE_POINTS (default 524 288).  With
  * coupling the forcing windows of a tile span [first coupling-window start, last window end + 1]
  * of ITS points; a tile whose windows would exceed ROADSURF_HIP_WINDOW_BUDGET_MB (default 24 576)
@@ -936,6 +989,10 @@ void rs_driver_release_cache(void);
 int rs_driver_expand(const RsDriverInput *in, const InputSettings *settings,
                      LocalParameters *local, double *merged, int32_t *status,
                      int32_t *missing_index, int32_t device);
+/* ... with gridded sources, as rs_driver_run_grid takes them */
+int rs_driver_expand_grid(const RsDriverInput *in, const RsGridSource *const *grids, const InputSettings *settings,
+                          LocalParameters *local, double *merged, int32_t *status, int32_t *missing_index,
+                          int32_t device);
 
 /* ------------------------------------------------------------------------
  * Layer 5: the device side of `module RoadSurf`'s per-step procedures

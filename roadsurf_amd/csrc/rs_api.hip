@@ -555,6 +555,25 @@ int rs_hip_outputs_groups(RsPlan *pl, const RsOutputs *src, int32_t nrows, const
   return 0;
 }
 
+int32_t rs_hip_grid_max_stencil(void) { return RS_GRID_MAX_STENCIL; }
+
+int rs_hip_gather_nodes(RsPlan *pl, const double *src, int32_t nrows, int64_t n_nodes, int64_t src_stride,
+                        const int32_t *node, const double *weight, int32_t stencil, const int32_t *order,
+                        double present_above, double missing_value, double *dst, int64_t dst_stride, void *stream) {
+  if (!pl || !src || !node || !weight || !dst || nrows < 1 || n_nodes < 1)
+    return set_err("rs_hip_gather_nodes: bad arguments (nrows >= 1 rows of n_nodes >= 1 nodes, a stencil and a destination)");
+  if (stencil < 1 || stencil > RS_GRID_MAX_STENCIL)
+    return set_err("rs_hip_gather_nodes: stencil outside 1..RS_GRID_MAX_STENCIL");
+  if (src_stride < n_nodes) return set_err("rs_hip_gather_nodes: src_stride below n_nodes");
+  if (dst_stride < pl->npoints) return set_err("rs_hip_gather_nodes: dst_stride below the plan's points");
+  if (!order && stream) return set_err("rs_hip_gather_nodes: on a stream of the caller's the order row must be a kept one");
+  if (!order && !rs_hip_plan_order(pl)) return -1;
+  HIP_OK(hipSetDevice(pl->device));
+  HIP_OK(rs_grid_gather(src, nrows, n_nodes, src_stride, node, weight, stencil, order ? order : pl->order, present_above,
+                        missing_value, dst, dst_stride, pl->npoints, stream ? (hipStream_t)stream : pl->stream));
+  return 0;
+}
+
 int rs_hip_plan_reset_order(RsPlan *pl) {
   if (!pl) return set_err("rs_hip_plan_reset_order: null plan");
   pl->wave_tab_valid = false;

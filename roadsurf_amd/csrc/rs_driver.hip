@@ -624,6 +624,12 @@ __global__ void __launch_bounds__(RS_BLOCK) fill_f64_kernel(double *x, int64_t n
   if (i < n) x[i] = v;
 }
 
+/* columns [m, mp) of row blockIdx.x of x[rows][mp] */
+__global__ void __launch_bounds__(RS_BLOCK) fill_pad_kernel(double *x, int64_t m, int64_t mp, double v) {
+  double *row = x + (int64_t)blockIdx.x * mp;
+  for (int64_t c = m + threadIdx.x; c < mp; c += RS_BLOCK) row[c] = v;
+}
+
 void launch_expand_raw(bool any_pp, int64_t mp, const ExpandRawArgs &ea, hipStream_t stream) {
   const dim3 g((unsigned)(mp / RS_BLOCK), NFLD), b(RS_BLOCK);
   if (any_pp)
@@ -707,7 +713,37 @@ const double *raw_field(const RsRawSource &s, int fld) {
   }
 }
 
+const double *grid_field(const RsGridSource &g, int fld) {
+  switch (fld) {
+    case R_TAIR: return g.tair;
+    case R_TDEW: return g.tdew;
+    case R_VZ: return g.vz;
+    case R_RHZ: return g.rhz;
+    case R_PREC: return g.prec;
+    case R_SW: return g.sw;
+    case R_LW: return g.lw;
+    case R_SWDIR: return g.sw_dir;
+    case R_LWNET: return g.lw_net;
+    default: return g.tsurfobs;
+  }
+}
+
+/* The fields of a call's gridded sources on one device, [n_times][n_nodes] as the caller holds them: uploaded once
+ * before the blocks start, shared by the blocks of a fan-out on that device, freed when the call returns. */
+struct GridDevice {
+  int device = 0;
+  Dev fld[RS_MAX_SOURCES][NFLD];
+  ~GridDevice() { (void)hipSetDevice(device); }
+};
+/* A call's gridded sources as one block of it sees them (NULL: the call has none) */
+struct GridView {
+  const RsGridSource *const *grids; /* [n_sources], NULL entry = per-point source */
+  const GridDevice *dev;            /* the block's device */
+};
+
 struct Common {
+  const RsGridSource *grid[RS_MAX_SOURCES] = {};         /* non-NULL: source s arrives as fields (RsGridSource) */
+  const double *grid_dev[RS_MAX_SOURCES][NFLD] = {};     /* ... and its fields on this block's device */
   int n = 0, nsrc = 0, L = 0, DT = 0;
   int default_initlen = 0, cplLen = 0;
   std::vector<int64_t> simtime;
@@ -716,7 +752,7 @@ struct Common {
   std::vector<std::vector<int32_t>> active_prefix; /* [source][i]: plan entries != K_NONE among indices < i */
 };
 
-int prepare(const RsDriverInput *in, const InputSettings *st, Common &c) {
+int prepare(const RsDriverInput *in, const InputSettings *st, Common &c, const GridView *gv = nullptr) {
   if (!in || !st || in->n_points < 1 || in->n_sources < 1 || in->n_sources > RS_MAX_SOURCES ||
       !in->sources)
     return fail_msg("rs_driver: bad arguments (n_points >= 1, 1 <= n_sources <= RS_MAX_SOURCES)", -1);
@@ -733,6 +769,10 @@ int prepare(const RsDriverInput *in, const InputSettings *st, Common &c) {
   /* roadrunner.cpp:263: static_cast<int>(coupling_minutes * 60 / DTSecs) */
   c.cplLen = (int)((double)(st->coupling_minutes * 60) / st->DTSecs);
   c.plans.resize(c.nsrc);
+  for (int s = 0; s < c.nsrc && gv; ++s) {
+    if (!(c.grid[s] = gv->grids[s])) continue;
+    for (int f = 0; f < NFLD; ++f) c.grid_dev[s][f] = gv->dev->fld[s][f].as<double>();
+  }
   for (int s = 0; s < c.nsrc; ++s) {
     const RsRawSource &rs = in->sources[s];
     if (rs.n_times < 0 || (rs.n_times > 0 && !rs.times))
@@ -783,6 +823,7 @@ struct TileRaw {
   Dev stage; /* landing block of the H2D copies ... */
   size_t off[RS_MAX_SOURCES][NFLD + 1] = {}; /* ... byte offset of (source, field) in it; NFLD: the times */
   bool has[RS_MAX_SOURCES][NFLD + 1] = {};
+  size_t off_node[RS_MAX_SOURCES] = {}, off_weight[RS_MAX_SOURCES] = {}; /* a gridded source: the tile's stencils */
   Dev segs;  /* Common::segs */
   SrcSet S{};
 };
@@ -871,12 +912,26 @@ int upload_finish(const RsDriverInput *in, const Common &c, int64_t p0, int m, i
       const bool h = T.has[s][f];
       d.fld[f] = nullptr;
       /* Tdew and RH can be completed from each other: both exist if either does */
-      const bool derived = (f == R_TDEW && rs.rhz && rs.tair) || (f == R_RHZ && rs.tdew && rs.tair);
+      const bool derived = (f == R_TDEW && T.has[s][R_RHZ] && T.has[s][R_TAIR]) ||
+                           (f == R_RHZ && T.has[s][R_TDEW] && T.has[s][R_TAIR]);
       if ((!h && !derived) || rs.n_times == 0) continue;
       const size_t ne = (size_t)rs.n_times * mp;
       HOK(T.fld[s][f].alloc(ne * sizeof(double)));
       double *dst = T.fld[s][f].as<double>();
-      if (h) {
+      if (h && c.grid[s]) {
+        /* the field stays as it arrived, [n_times][n_nodes]: the tile's columns are gathered from it (rs_grid.hip);
+         * the live columns hold what grid.py's to_raw_source defines, the pad columns the missing value */
+        const RsGridSource &g = *c.grid[s];
+        HOK(rs_grid_gather(c.grid_dev[s][f], rs.n_times, g.n_nodes, g.n_nodes,
+                           reinterpret_cast<const int32_t *>(base + T.off_node[s]),
+                           reinterpret_cast<const double *>(base + T.off_weight[s]), g.stencil, nullptr, rs::raw_threshold(f),
+                           -9999.9, dst, mp, m, stream));
+        if (mp > m) {
+          hipLaunchKernelGGL(fill_pad_kernel, dim3((unsigned)rs.n_times), dim3(RS_BLOCK), 0, stream, dst, (int64_t)m, mp,
+                             -9999.9);
+          HOK(hipGetLastError());
+        }
+      } else if (h) {
         HOK(transpose(reinterpret_cast<const double *>(base + T.off[s][f]), dst, m, rs.n_times, rs.n_times,
                       mp, stream));
       } else {
@@ -914,6 +969,14 @@ int upload_tile(const RsDriverInput *in, const Common &c, int32_t device, int64_
     const RsRawSource &rs = in->sources[s];
     if (rs.n_times < 1) continue;
     const size_t piece = ((size_t)m * rs.n_times * sizeof(double) + 255) & ~(size_t)255;
+    if (const RsGridSource *g = c.grid[s]) { /* the fields are on the device already: the tile's slice of the stencils */
+      T.off_node[s] = total;
+      total += ((size_t)m * g->stencil * sizeof(int32_t) + 255) & ~(size_t)255;
+      T.off_weight[s] = total;
+      total += ((size_t)m * g->stencil * sizeof(double) + 255) & ~(size_t)255;
+      for (int f = 0; f < NFLD; ++f) T.has[s][f] = grid_field(*g, f) != nullptr;
+      continue;
+    }
     if (rs.times_per_point) {
       T.off[s][NFLD] = total;
       T.has[s][NFLD] = true;
@@ -930,6 +993,14 @@ int upload_tile(const RsDriverInput *in, const Common &c, int32_t device, int64_
   char *base = T.stage.as<char>();
   for (int s = 0; s < c.nsrc; ++s) {
     const RsRawSource &rs = in->sources[s];
+    if (const RsGridSource *g = c.grid[s]) {
+      if (rs.n_times < 1) continue;
+      HOK(hipMemcpyAsync(base + T.off_node[s], g->node + (size_t)p0 * g->stencil, (size_t)m * g->stencil * sizeof(int32_t),
+                         hipMemcpyHostToDevice, stream));
+      HOK(hipMemcpyAsync(base + T.off_weight[s], g->weight + (size_t)p0 * g->stencil,
+                         (size_t)m * g->stencil * sizeof(double), hipMemcpyHostToDevice, stream));
+      continue;
+    }
     if (T.has[s][NFLD])
       HOK(hipMemcpyAsync(base + T.off[s][NFLD], rs.times + (size_t)p0 * rs.n_times,
                          (size_t)m * rs.n_times * sizeof(int64_t), hipMemcpyHostToDevice, stream));
@@ -1967,14 +2038,115 @@ int check_groups(const RsDriverGroups *grp, int n_out) {
   return 0;
 }
 
+/* ---- gridded sources (RsGridSource): checked on the host, their fields resident once per device of the call */
+
+bool any_grid(const RsDriverInput *in, const RsGridSource *const *grids) {
+  if (!grids || !in || !in->sources || in->n_sources < 1 || in->n_sources > RS_MAX_SOURCES) return false;
+  for (int s = 0; s < in->n_sources; ++s)
+    if (grids[s]) return true;
+  return false;
+}
+
+/* before any device work: what a gridded source must be, and a scan of its n_points x stencil nodes and weights */
+int check_grids(const RsDriverInput *in, const RsGridSource *const *grids) {
+  char b[200];
+  for (int s = 0; s < in->n_sources; ++s) {
+    const RsGridSource *g = grids[s];
+    if (!g) continue;
+    const RsRawSource &rs = in->sources[s];
+    if (rs.times_per_point || rs.lengths) {
+      snprintf(b, sizeof(b), "rs_driver: gridded source %d needs a time axis shared by all points (times_per_point = 0, lengths NULL)", s);
+      return fail_msg(b, -1);
+    }
+    for (int f = 0; f < NFLD; ++f)
+      if (raw_field(rs, f)) {
+        snprintf(b, sizeof(b), "rs_driver: gridded source %d: the field pointers of its RsRawSource must be NULL (the fields are the RsGridSource's)", s);
+        return fail_msg(b, -1);
+      }
+    if (g->stencil < 1 || g->stencil > RS_GRID_MAX_STENCIL) {
+      snprintf(b, sizeof(b), "rs_driver: gridded source %d: stencil %d outside 1..%d", s, g->stencil, RS_GRID_MAX_STENCIL);
+      return fail_msg(b, -1);
+    }
+    if (g->n_nodes < 1 || !g->node || !g->weight) {
+      snprintf(b, sizeof(b), "rs_driver: gridded source %d: n_nodes >= 1, node and weight are required", s);
+      return fail_msg(b, -1);
+    }
+    const int st = g->stencil;
+    for (int64_t p = 0; p < in->n_points; ++p)
+      for (int k = 0; k < st; ++k) {
+        const double w = g->weight[p * st + k];
+        const int64_t nd = g->node[p * st + k];
+        if (!std::isfinite(w)) {
+          snprintf(b, sizeof(b), "rs_driver: gridded source %d: weight %d of point %lld is not finite", s, k, (long long)p);
+          return fail_msg(b, -1);
+        }
+        if (w != 0.0 && (nd < 0 || nd >= g->n_nodes)) {
+          snprintf(b, sizeof(b), "rs_driver: gridded source %d: node %d of point %lld (%lld) outside [0, n_nodes = %lld) under a non-zero weight",
+                   s, k, (long long)p, (long long)nd, (long long)g->n_nodes);
+          return fail_msg(b, -1);
+        }
+      }
+  }
+  return 0;
+}
+
+/* The calling thread's part: every gridded source's fields to every distinct device of the call, each device's in
+ * its turn on the link (copy_gate), before the blocks start. */
+struct GridUploads {
+  std::vector<GridDevice *> devs;
+  ~GridUploads() {
+    for (GridDevice *d : devs) delete d;
+  }
+  const GridDevice *find(int device) const {
+    for (const GridDevice *d : devs)
+      if (d->device == device) return d;
+    return nullptr;
+  }
+};
+
+int upload_grids(const RsDriverInput *in, const RsGridSource *const *grids, const std::vector<int> &devices,
+                 GridUploads &G) {
+  for (int device : devices) {
+    if (G.find(device)) continue;
+    if (int rc = check_device(device)) return rc;
+    HOK(hipSetDevice(device));
+    GridDevice *d = new GridDevice;
+    d->device = device;
+    G.devs.push_back(d);
+    StreamGuard sg;
+    HOK(hipStreamCreate(&sg.s));
+    const double tg0 = PhaseTimer::now();
+    std::lock_guard<std::mutex> turn(rsu::copy_gate(device));
+    size_t bytes = 0;
+    for (int s = 0; s < in->n_sources; ++s) {
+      const RsGridSource *g = grids[s];
+      if (!g || in->sources[s].n_times < 1) continue;
+      const size_t nb = (size_t)in->sources[s].n_times * (size_t)g->n_nodes * sizeof(double);
+      for (int f = 0; f < NFLD; ++f) {
+        const double *h = grid_field(*g, f);
+        if (!h) continue;
+        HOK(d->fld[s][f].alloc(nb));
+        HOK(hipMemcpyAsync(d->fld[s][f].p, h, nb, hipMemcpyHostToDevice, sg.s));
+        bytes += nb;
+      }
+    }
+    HOK(hipStreamSynchronize(sg.s));
+    if (getenv("ROADSURF_HIP_DRIVER_TIMING"))
+      fprintf(stderr, "rs_driver_run grid fields: %.1f MB to device %d in %.1f ms\n", 1e-6 * (double)bytes, device,
+              1e3 * (PhaseTimer::now() - tg0));
+  }
+  return 0;
+}
+
 /* points [pbeg, pend) of the input on one device */
 int driver_run_range(const RsDriverInput *in, const InputSettings *st, const InputParameters *params,
                      LocalParameters *local, const RsDriverOutput *out, const RsDriverSummary *sum,
-                     const RsDriverGroups *grp, int32_t device, int64_t pbeg, int64_t pend) {
+                     const RsDriverGroups *grp, int32_t device, int64_t pbeg, int64_t pend,
+                     const GridView *gv = nullptr) {
   Common c;
   RunPolicy R;
   RsConstants consts;
-  if (int rc = prepare(in, st, c)) return rc;
+  if (int rc = prepare(in, st, c, gv)) return rc;
   if (int rc = check_run_arguments(in, st, params, local, out, c, R, consts)) return rc;
   if (sum && (!sum->summary || sum->first_row < 0 || sum->last_row < sum->first_row || sum->last_row >= R.n_out))
     return fail_msg("rs_driver_run_summary: summary is required, with 0 <= first_row <= last_row < n_out", -1);
@@ -2065,14 +2237,19 @@ int driver_run_range(const RsDriverInput *in, const InputSettings *st, const Inp
   return 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-int rs_driver_expand(const RsDriverInput *in, const InputSettings *st, LocalParameters *local,
-                     double *merged, int32_t *status, int32_t *missing_index, int32_t device) {
+/* the input side alone (rs_driver_expand, rs_driver_expand_grid) */
+int driver_expand(const RsDriverInput *in, const RsGridSource *const *grids, const InputSettings *st,
+                  LocalParameters *local, double *merged, int32_t *status, int32_t *missing_index, int32_t device) {
+  GridUploads G; /* (declared first: freed when every stream of the call is gone) */
+  GridView gv{grids, nullptr};
+  const bool gridded = any_grid(in, grids);
+  if (gridded) {
+    if (int rc = check_grids(in, grids)) return rc;
+    if (int rc = upload_grids(in, grids, std::vector<int>{device}, G)) return rc;
+    gv.dev = G.find(device);
+  }
   Common c;
-  if (int rc = prepare(in, st, c)) return rc;
+  if (int rc = prepare(in, st, c, gridded ? &gv : nullptr)) return rc;
   if (!merged) return fail_msg("rs_driver_expand: merged is required", -1);
   if (int rc = check_device(device)) return rc;
   HOK(hipSetDevice(device));
@@ -2119,6 +2296,69 @@ int rs_driver_expand(const RsDriverInput *in, const InputSettings *st, LocalPara
   return 0;
 }
 
+/* rs_driver_run and its kin: one device, or the fan-out */
+int driver_run(const RsDriverInput *in, const RsGridSource *const *grids, const InputSettings *st,
+               const InputParameters *params, LocalParameters *local, const RsDriverOutput *out,
+               const RsDriverSummary *sum, const RsDriverGroups *grp, int32_t device) {
+  if (!in || in->n_points < 1) return fail_msg("rs_driver_run: bad arguments", -1);
+  if (grp) {
+    if (!out) return fail_msg("rs_driver_run: bad arguments", -1);
+    if (int rc = check_groups(grp, out->n_out)) return rc;
+    const int cols = rs_cluster_group_cols(&grp->spec);
+    const size_t ncells = (size_t)(grp->last_row - grp->first_row + 1) * grp->spec.ngroups;
+    for (size_t i = 0; i < ncells; ++i) /* the empty cell: what merge_group_cells starts from */
+      for (int c = 0; c < cols; ++c)
+        grp->series[i * cols + c] = c == 1 ? HUGE_VAL : (c == 2 || (c >= 9 && c < RS_GRP_COLS)) ? -HUGE_VAL : 0.0;
+  }
+  const bool gridded = any_grid(in, grids);
+  if (gridded)
+    if (int rc = check_grids(in, grids)) return rc;
+  GridUploads G;
+  GridView gv{grids, nullptr};
+  if (device >= 0) {
+    if (gridded) {
+      if (int rc = upload_grids(in, grids, std::vector<int>{device}, G)) return rc;
+      gv.dev = G.find(device);
+    }
+    rsu::g_last_fanout = 1;
+    return driver_run_range(in, st, params, local, out, sum, grp, device, 0, in->n_points, gridded ? &gv : nullptr);
+  }
+  /* four blocks per device.  (Six for batches with local horizons were 4 % faster while the horizon table
+   * was transposed on the device, tools/experiments/r4_blocks.sh; with the table left in the caller's layout
+   * - RsPointParams::horizons_by_point - four and six are level: 1.047e10 / 1.046e10 over three alternating
+   * runs each.) */
+  /* With local horizons a block uploads twice the bytes, the blocks start 38 instead of 19 ms apart and - of equal
+   * size - end that far apart too: there the blocks shrink, the last to 70 % of the first (+1.4 % over three
+   * tapers, profiles/r05_ab_block_taper.txt; without horizons equal blocks are as good). */
+  const std::vector<rsu::Shard> shards =
+      rsu::make_shards(in->n_points, rsu::device_list(), in->horizons ? 30 : RS_BLOCK_TAPER_PCT_DEFAULT);
+  if (gridded) {
+    std::vector<int> devices;
+    for (const rsu::Shard &sh : shards) devices.push_back(sh.device);
+    if (int rc = upload_grids(in, grids, devices, G)) return rc;
+  }
+  return rsu::fan_out(shards, [&](const rsu::Shard &sh, int) {
+    const GridView v{grids, G.find(sh.device)};
+    return driver_run_range(in, st, params, local, out, sum, grp, sh.device, sh.off, sh.off + sh.cnt,
+                            gridded ? &v : nullptr);
+  });
+}
+
+}  // namespace
+
+extern "C" {
+
+int rs_driver_expand(const RsDriverInput *in, const InputSettings *st, LocalParameters *local,
+                     double *merged, int32_t *status, int32_t *missing_index, int32_t device) {
+  return driver_expand(in, nullptr, st, local, merged, status, missing_index, device);
+}
+
+int rs_driver_expand_grid(const RsDriverInput *in, const RsGridSource *const *grids, const InputSettings *st,
+                          LocalParameters *local, double *merged, int32_t *status, int32_t *missing_index,
+                          int32_t device) {
+  return driver_expand(in, grids, st, local, merged, status, missing_index, device);
+}
+
 void rs_driver_release_cache(void) {
   for (int d = 0; d < 128; ++d) {
     WindowCache &c = d < 64 ? g_wincache[d] : g_arenacache[d - 64];
@@ -2158,32 +2398,15 @@ int rs_driver_run_summary(const RsDriverInput *in, const InputSettings *st, cons
 int rs_driver_run_groups(const RsDriverInput *in, const InputSettings *st, const InputParameters *params,
                          LocalParameters *local, const RsDriverOutput *out, const RsDriverSummary *sum,
                          const RsDriverGroups *grp, int32_t device) {
-  if (!in || in->n_points < 1) return fail_msg("rs_driver_run: bad arguments", -1);
-  if (grp) {
-    if (!out) return fail_msg("rs_driver_run: bad arguments", -1);
-    if (int rc = check_groups(grp, out->n_out)) return rc;
-    const int cols = rs_cluster_group_cols(&grp->spec);
-    const size_t ncells = (size_t)(grp->last_row - grp->first_row + 1) * grp->spec.ngroups;
-    for (size_t i = 0; i < ncells; ++i) /* the empty cell: what merge_group_cells starts from */
-      for (int c = 0; c < cols; ++c)
-        grp->series[i * cols + c] = c == 1 ? HUGE_VAL : (c == 2 || (c >= 9 && c < RS_GRP_COLS)) ? -HUGE_VAL : 0.0;
-  }
-  if (device >= 0) {
-    rsu::g_last_fanout = 1;
-    return driver_run_range(in, st, params, local, out, sum, grp, device, 0, in->n_points);
-  }
-  /* four blocks per device.  (Six for batches with local horizons were 4 % faster while the horizon table
-   * was transposed on the device, tools/experiments/r4_blocks.sh; with the table left in the caller's layout
-   * - RsPointParams::horizons_by_point - four and six are level: 1.047e10 / 1.046e10 over three alternating
-   * runs each.) */
-  /* With local horizons a block uploads twice the bytes, the blocks start 38 instead of 19 ms apart and - of equal
-   * size - end that far apart too: there the blocks shrink, the last to 70 % of the first (+1.4 % over three
-   * tapers, profiles/r05_ab_block_taper.txt; without horizons equal blocks are as good). */
-  const std::vector<rsu::Shard> shards =
-      rsu::make_shards(in->n_points, rsu::device_list(), in->horizons ? 30 : RS_BLOCK_TAPER_PCT_DEFAULT);
-  return rsu::fan_out(shards, [&](const rsu::Shard &sh, int) {
-    return driver_run_range(in, st, params, local, out, sum, grp, sh.device, sh.off, sh.off + sh.cnt);
-  });
+  return driver_run(in, nullptr, st, params, local, out, sum, grp, device);
+}
+
+/* ... and with sources that arrive as fields: the calling thread checks them and puts their fields on every device of
+ * the call before the blocks start */
+int rs_driver_run_grid(const RsDriverInput *in, const RsGridSource *const *grids, const InputSettings *st,
+                       const InputParameters *params, LocalParameters *local, const RsDriverOutput *out,
+                       const RsDriverSummary *sum, const RsDriverGroups *grp, int32_t device) {
+  return driver_run(in, grids, st, params, local, out, sum, grp, device);
 }
 
 } /* extern "C" */

@@ -187,6 +187,11 @@ hipError_t rs_cluster_group_reset(double *acc, int64_t acc_rows, const RsGroupSp
 hipError_t rs_cluster_outputs_groups(const void *const src[6], bool f32, const int32_t *order, const int32_t *group,
                                      int64_t npoints, int64_t src_stride, int32_t nrows, const RsGroupSpec &spec,
                                      double *acc_row0, hipStream_t stream);
+/* gridded fields gathered to points (rs_grid.hip, rs_hip_gather_nodes): dst[r][slot] for r < nrows, slot < npoints;
+ * node / weight [point][stencil]; order NULL = column s is point s */
+hipError_t rs_grid_gather(const double *src, int32_t nrows, int64_t n_nodes, int64_t src_stride, const int32_t *node,
+                          const double *weight, int32_t stencil, const int32_t *order, double present_above,
+                          double missing, double *dst, int64_t dst_stride, int64_t npoints, hipStream_t stream);
 size_t rs_cluster_scratch_bytes(int64_t npoints);
 hipError_t rs_cluster_sort(const double *state, bool f32, int64_t np_pad, int64_t npoints,
                            uint32_t *scratch, void *tmp, size_t tmp_bytes, hipStream_t stream);

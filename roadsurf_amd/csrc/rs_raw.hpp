@@ -60,7 +60,7 @@ struct RawForcing {
 /* examples/example1/src/InputData.cpp:5-26: every series starts out missing */
 __device__ __forceinline__ double raw_miss() { return -9999.9; }
 /* JsonSource.cpp:92-111,323-345: `> -100.0`, except LW_net `> -1000.0` */
-__device__ __forceinline__ double raw_threshold(int fld) { return fld == RAW_LWNET ? -1000.0 : -100.0; }
+__host__ __device__ __forceinline__ double raw_threshold(int fld) { return fld == RAW_LWNET ? -1000.0 : -100.0; }
 
 /* A shared-axis plan entry, read as constant memory (address space 4): one scalar load of the
  * 32-byte entry.  Through a generic pointer the compiler loads the two doubles with a VECTOR load

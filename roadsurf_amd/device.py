@@ -367,6 +367,27 @@ class Plan:
         assert spec is None or a.shape[1:] == (int(spec.ngroups), lib.group_cols(spec))
         return a
 
+    def gather_nodes(self, src: torch.Tensor, node: torch.Tensor, weight: torch.Tensor, dst: torch.Tensor,
+                     present_above: float, missing: float = -9999.9, n_nodes: int | None = None, order=None,
+                     stream: torch.cuda.Stream | None = None) -> None:
+        """Fields gathered to this plan's points (rs_hip_gather_nodes; roadsurf_amd/grid.py gather_nodes defines the
+        values): ``src`` float64 [nrows, src_stride] holding ``n_nodes`` (default all) nodes per row, ``node`` int32 /
+        ``weight`` float64 [>= npoints, stencil], ``dst`` float64 [nrows, dst_stride >= npoints] whose columns
+        [0, npoints) are written in slot order; ``order`` and ``stream`` as for ``outputs_by_point``."""
+        if not hasattr(self.L, "rs_hip_grid_max_stencil"):
+            raise RuntimeError("this libroadsurf_hip.so has no gridded sources (rs_hip_grid_max_stencil)")
+        assert src.dtype == torch.float64 and src.dim() == 2 and src.stride(1) == 1
+        assert dst.dtype == torch.float64 and dst.dim() == 2 and dst.stride(1) == 1 and dst.shape[0] == src.shape[0]
+        assert node.dtype == torch.int32 and weight.dtype == torch.float64 and node.dim() == 2
+        assert node.shape == weight.shape and node.shape[0] >= self.npoints and node.is_contiguous() and weight.is_contiguous()
+        lib.check(self.L.rs_hip_gather_nodes(self._h, C.c_void_p(src.data_ptr()), int(src.shape[0]),
+                                             int(src.shape[1] if n_nodes is None else n_nodes), int(src.stride(0)),
+                                             C.c_void_p(node.data_ptr()), C.c_void_p(weight.data_ptr()),
+                                             int(node.shape[1]), C.c_void_p(order.data_ptr()) if order is not None else None,
+                                             float(present_above), float(missing), C.c_void_p(dst.data_ptr()),
+                                             int(dst.stride(0)), C.c_void_p(stream.cuda_stream) if stream is not None else None),
+                  "rs_hip_gather_nodes")
+
     def reset_order(self) -> None:
         lib.check(self.L.rs_hip_plan_reset_order(self._h), "rs_hip_plan_reset_order")
 

@@ -19,6 +19,7 @@ import time as _time
 import numpy as np
 
 from . import abi
+from . import grid as rsgrid
 from . import lib as rslib
 
 RS_MAX_SOURCES = 4
@@ -68,6 +69,11 @@ class RsDriverGroups(C.Structure):
                 ("last_row", C.c_int32), ("series", abi.c_double_p)]
 
 
+class RsGridSource(C.Structure):
+    _fields_ = [("n_nodes", C.c_int64)] + [(n, abi.c_double_p) for n in RAW_FIELDS] + [
+        ("stencil", C.c_int32), ("node", abi.c_int32_p), ("weight", abi.c_double_p)]
+
+
 @dataclasses.dataclass
 class RawSource:
     """One data source: ``fields`` name -> [n_points][n_times] float64 (absent name = variable
@@ -108,12 +114,12 @@ def forecast_rows(settings: abi.InputSettings, start_time: int, forecast_time: i
 
 
 def make_input(sources, start_time: int, forecast_time: int, cal: dict | None = None,
-               horizons: np.ndarray | None = None):
-    """Build the C struct.  Returns (RsDriverInput, keepalive list)."""
+               horizons: np.ndarray | None = None, n_points: int | None = None):
+    """Build the C struct.  Returns (RsDriverInput, keepalive list).  ``n_points``: the number of points where it is
+    known beforehand (``make_grid_input``: a source without fields of its own does not tell)."""
     if not 1 <= len(sources) <= RS_MAX_SOURCES:
         raise ValueError(f"1..{RS_MAX_SOURCES} sources")
     keep = []
-    n_points = None
     arr = (RsRawSource * len(sources))()
     for k, s in enumerate(sources):
         t = np.ascontiguousarray(s.times, np.int64)
@@ -171,6 +177,40 @@ def make_input(sources, start_time: int, forecast_time: int, cal: dict | None = 
     return inp, keep
 
 
+def make_grid_input(sources, start_time: int, forecast_time: int, cal: dict | None = None,
+                    horizons: np.ndarray | None = None):
+    """``make_input`` for a list that may hold ``grid.GridSource`` entries among the ``RawSource`` ones.  Returns
+    (RsDriverInput, grids, keepalive list): ``grids`` is the ``RsGridSource *[n_sources]`` rs_driver_run_grid takes
+    (NULL entry = per-point source), or None when no source is gridded.  A gridded source's RsRawSource carries
+    its time axis and is_observation only."""
+    gridded = [isinstance(s, rsgrid.GridSource) for s in sources]
+    if not any(gridded):
+        inp, keep = make_input(sources, start_time, forecast_time, cal, horizons)
+        return inp, None, keep
+    n_points = {s.n_points for s, g in zip(sources, gridded) if g}
+    if len(n_points) != 1:
+        raise ValueError("all sources must hold the same points")
+    plain = [RawSource(s.times, {}, s.is_observation) if g else s for s, g in zip(sources, gridded)]
+    inp, keep = make_input(plain, start_time, forecast_time, cal, horizons, n_points=n_points.pop())
+    structs = (RsGridSource * len(sources))()
+    grids = (C.POINTER(RsGridSource) * len(sources))()
+    for k, (s, g) in enumerate(zip(sources, gridded)):
+        if not g:
+            continue
+        for name, a in s.fields.items():
+            if name not in RAW_FIELDS:
+                raise KeyError(name)
+            setattr(structs[k], name, a.ctypes.data_as(abi.c_double_p))
+        structs[k].n_nodes = s.n_nodes
+        structs[k].stencil = s.node.shape[1]
+        structs[k].node = s.node.ctypes.data_as(abi.c_int32_p)
+        structs[k].weight = s.weight.ctypes.data_as(abi.c_double_p)
+        grids[k] = C.pointer(structs[k])
+        keep.append(s)
+    keep.append(structs)
+    return inp, grids, keep
+
+
 def _locals(n: int, local) -> C.Array:
     """LocalParameters[n]: None -> defaults, one struct -> replicated, a list, or a ready
     ctypes array (used as is: it is also where the decisions are written back)."""
@@ -201,24 +241,44 @@ def _bind(L):
                                            P(RsDriverGroups), C.c_int32]
     L.rs_driver_expand.argtypes = [P(RsDriverInput), P(abi.InputSettings), P(abi.LocalParameters),
                                    abi.c_double_p, abi.c_int32_p, abi.c_int32_p, C.c_int32]
+    if hasattr(L, "rs_driver_run_grid"):
+        L.rs_driver_run_grid.argtypes = [P(RsDriverInput), P(P(RsGridSource)), P(abi.InputSettings),
+                                         P(abi.InputParameters), P(abi.LocalParameters), P(RsDriverOutput),
+                                         P(RsDriverSummary), P(RsDriverGroups), C.c_int32]
+        L.rs_driver_expand_grid.argtypes = [P(RsDriverInput), P(P(RsGridSource)), P(abi.InputSettings),
+                                            P(abi.LocalParameters), abi.c_double_p, abi.c_int32_p, abi.c_int32_p,
+                                            C.c_int32]
     return L
+
+
+def _need_grids(L) -> None:
+    if not hasattr(L, "rs_driver_run_grid") or L.rs_hip_grid_max_stencil() != rsgrid.MAX_STENCIL:
+        raise RuntimeError("this libroadsurf_hip.so has no gridded sources (rs_hip_grid_max_stencil)")
 
 
 def read_input(sources, settings: abi.InputSettings, start_time: int, forecast_time: int,
                local=None, device: int = 0) -> dict:
     """What ``read_input`` (roadrunner.cpp:156-278) produces for every point, computed on the
-    GPU: ``merged`` name -> [n][SimLen], ``status``, ``missing_index``, ``local``."""
+    GPU: ``merged`` name -> [n][SimLen], ``status``, ``missing_index``, ``local``.  ``sources`` may hold
+    ``grid.GridSource`` entries (rs_driver_expand_grid)."""
     L = _bind(rslib.load())
-    inp, keep = make_input(sources, start_time, forecast_time)
+    inp, grids, keep = make_grid_input(sources, start_time, forecast_time)
     n, simlen = inp.n_points, settings.SimLen
     larr = _locals(n, local)
     merged = np.empty((len(MERGED_FIELDS), n, simlen), np.float64)
     status = np.empty(n, np.int32)
     mi = np.empty(n, np.int32)
-    rslib.check(L.rs_driver_expand(C.byref(inp), C.byref(settings), larr,
-                                   merged.ctypes.data_as(abi.c_double_p),
-                                   status.ctypes.data_as(abi.c_int32_p),
-                                   mi.ctypes.data_as(abi.c_int32_p), device), "rs_driver_expand")
+    if grids is not None:
+        _need_grids(L)
+        rslib.check(L.rs_driver_expand_grid(C.byref(inp), grids, C.byref(settings), larr,
+                                            merged.ctypes.data_as(abi.c_double_p),
+                                            status.ctypes.data_as(abi.c_int32_p),
+                                            mi.ctypes.data_as(abi.c_int32_p), device), "rs_driver_expand_grid")
+    else:
+        rslib.check(L.rs_driver_expand(C.byref(inp), C.byref(settings), larr,
+                                       merged.ctypes.data_as(abi.c_double_p),
+                                       status.ctypes.data_as(abi.c_int32_p),
+                                       mi.ctypes.data_as(abi.c_int32_p), device), "rs_driver_expand")
     del keep
     return {"merged": {k: merged[i] for i, k in enumerate(MERGED_FIELDS)}, "status": status,
             "missing_index": mi, "local": larr}
@@ -240,11 +300,16 @@ def run(sources, settings: abi.InputSettings, params: abi.InputParameters, start
     ``groups`` = a groups.GroupSpec with ``group_of`` = every point's group id, int32 [n]: the result also has
     ``groups``, float64 [rows][ngroups][cols], the per-group series (roadsurf_amd/groups.py) of the kept rows
     ``group_rows`` = (first_row, last_row), default all of them (rs_driver_run_groups); counts as a summary for
-    ``series=False``."""
+    ``series=False``.
+    ``sources`` may hold ``grid.GridSource`` entries, mixed with ``RawSource`` ones: their fields go to the device
+    as they are and are gathered to the points there (rs_driver_run_grid); the result is that of the same call on
+    ``grid.to_raw_source`` of them."""
     L = _bind(rslib.load())
     if cal is None:
         cal = calendar(start_time, settings.SimLen, int(settings.DTSecs))
-    inp, keep = make_input(sources, start_time, forecast_time, cal, horizons)
+    inp, grids, keep = make_grid_input(sources, start_time, forecast_time, cal, horizons)
+    if grids is not None:
+        _need_grids(L)
     n = inp.n_points
     step, n_out = output_rows(settings)
     larr = _locals(n, local)
@@ -281,6 +346,11 @@ def run(sources, settings: abi.InputSettings, params: abi.InputParameters, start
         res["groups"] = np.full((max(glast - gfirst + 1, 1), int(groups.ngroups), rslib.group_cols(groups)), np.nan)
         g = RsDriverGroups(rslib.group_spec(groups), gid.ctypes.data_as(abi.c_int32_p), gfirst, glast,
                            res["groups"].ctypes.data_as(abi.c_double_p))
+    if grids is not None:
+        rslib.check(L.rs_driver_run_grid(C.byref(inp), grids, C.byref(settings), C.byref(params), larr, C.byref(out),
+                                         C.byref(q) if q is not None else None,
+                                         C.byref(g) if g is not None else None, device), "rs_driver_run_grid")
+    elif groups is not None:
         rslib.check(L.rs_driver_run_groups(C.byref(inp), C.byref(settings), C.byref(params), larr, C.byref(out),
                                            C.byref(q) if q is not None else None, C.byref(g), device),
                     "rs_driver_run_groups")

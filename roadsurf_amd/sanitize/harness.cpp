@@ -106,8 +106,10 @@ void batch_call(const Group &g, int n) {
 
 /* rs_driver_run: an hourly forecast on a shared axis + 10-minute observations on per-point axes (the shape of
  * examples/example1's two JSON files), `n` points, relaxation (and coupling) on: the host side cuts shards over
- * ROADSURF_HIP_DEVICES, builds the segment table of the raw times and runs one worker thread per block */
-void driver_call(int n, int hours, bool coupling) {
+ * ROADSURF_HIP_DEVICES, builds the segment table of the raw times and runs one worker thread per block.
+ * `gridded`: the forecast goes in as fields with two-node stencils (rs_driver_run_grid): the calling thread checks
+ * the stencils and uploads the fields once per device, the blocks' tiles upload their slices of the stencils */
+void driver_call(int n, int hours, bool coupling, bool gridded = false) {
   const int L = hours * 120 + 1, nf = hours + 1, no = 6 * 3 + 1; /* observations over the first three hours */
   const int64_t t0 = 1704844800; /* 2024-01-10 00:00 UTC */
   std::vector<int64_t> tf(nf), to((size_t)n * no);
@@ -133,6 +135,21 @@ void driver_call(int n, int hours, bool coupling) {
   src[1].n_times = no; src[1].is_observation = 1; src[1].times = to.data(); src[1].times_per_point = 1;
   src[1].lengths = olen.data();
   src[1].tair = o_tair.data(); src[1].rhz = o_rh.data(); src[1].vz = o_vz.data(); src[1].tsurfobs = o_ts.data();
+  RsGridSource grid;
+  std::memset(&grid, 0, sizeof(grid));
+  std::vector<int32_t> node((size_t)n * 2);
+  std::vector<double> weight((size_t)n * 2);
+  const RsGridSource *grids[2] = {gridded ? &grid : nullptr, nullptr};
+  if (gridded) { /* the same arrays read as [nf][n_nodes = n] */
+    grid.n_nodes = n; grid.stencil = 2; grid.node = node.data(); grid.weight = weight.data();
+    grid.tair = src[0].tair; grid.rhz = src[0].rhz; grid.vz = src[0].vz; grid.prec = src[0].prec;
+    grid.sw = src[0].sw; grid.lw = src[0].lw; grid.sw_dir = src[0].sw_dir; grid.lw_net = src[0].lw_net;
+    src[0].tair = src[0].rhz = src[0].vz = src[0].prec = src[0].sw = src[0].lw = src[0].sw_dir = src[0].lw_net = nullptr;
+    for (int p = 0; p < n; ++p) {
+      node[(size_t)p * 2] = p; node[(size_t)p * 2 + 1] = (p % 5) ? (p + 1) % n : -1; /* (-1 under a zero weight) */
+      weight[(size_t)p * 2] = (p % 5) ? 0.75 : 1.0; weight[(size_t)p * 2 + 1] = (p % 5) ? 0.25 : 0.0;
+    }
+  }
   std::vector<int32_t> yy(L, 2024), mo(L, 1), dd(L, 10), hh(L), mi(L), ss(L);
   for (int t = 0; t < L; ++t) { hh[t] = (t / 120) % 24; mi[t] = (t / 2) % 60; ss[t] = (t % 2) * 30; }
   RsDriverInput in;
@@ -184,7 +201,7 @@ void driver_call(int n, int hours, bool coupling) {
   g.first_row = n_out / 2;
   g.last_row = n_out - 1;
   g.series = cells.data();
-  const int rc = rs_driver_run_groups(&in, &s, &p, local.data(), &out, coupling ? &q : nullptr, &g, -1);
+  const int rc = rs_driver_run_grid(&in, gridded ? grids : nullptr, &s, &p, local.data(), &out, coupling ? &q : nullptr, &g, -1);
   if (rc != 0) {
     fprintf(stderr, "rs_driver_run(%d points) -> %d: %s\n", n, rc, rs_last_error());
     g_errors++;
@@ -224,6 +241,7 @@ int main(int argc, char **argv) {
     std::vector<std::thread> th;
     th.emplace_back([] { driver_call(9000, 6, false); });
     th.emplace_back([] { driver_call(700, 5, true); });
+    th.emplace_back([] { driver_call(5000, 4, false, true); });
     for (auto &x : th) x.join();
   }
   printf("phase 4: concurrent rs_driver_run calls done\n");

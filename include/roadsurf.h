@@ -969,6 +969,39 @@ int rs_driver_run_grid(const RsDriverInput *in, const RsGridSource *const *grids
                        const InputSettings *settings, const InputParameters *params, LocalParameters *local,
                        const RsDriverOutput *out, const RsDriverSummary *summary, const RsDriverGroups *groups,
                        int32_t device);
+/* ... and with the INPUTS the model saw at the kept rows, and the dew-point deficit there (the ABI number stays: every
+ * name here is new, a binding detects them with rs_driver_kept_fields).  The reference's operational program stores,
+ * per point and output time, the surface temperature, the air temperature, the dew point and their difference, the
+ * hoar-frost and condensation indicator (examples/example2/src/QueryDataTools.cpp:285-296, 323-347); these are the
+ * merged, interpolated, Tdew / RH-completed series read_input hands to runsimulation, which no other call returns
+ * short of rs_driver_expand's [10][n_points][SimLen] download.  The definition, in numpy: roadsurf_amd/kept.py.
+ *   merged[f][p][r]  equals, bit for bit, rs_driver_expand's merged[f][p][r * step] of the same call (step =
+ *                    outputStep*60/DTSecs, kept row r = 0-based simulation index r * step, roadrunner.cpp:303): the
+ *                    values read_input returns, for EVERY point - a rejected point's rows are not blanked - with
+ *                    TSurfObs blanked to -9999.9 inside a point's coupling window (roadrunner.cpp:266-273).  They
+ *                    predate runsimulation's in-place edits of its inputs: VZ(1), the clamp of SW_dir to SW, the
+ *                    sky-view correction of SW, SW_dir and LW are NOT in them.
+ *   deficit[p][r]    = Tsurf[p][r] - tdew[p][r], one fp64 subtraction, where both operands are not NaN and > -9000
+ *                    (-9000.0 itself is missing here: calc_difference's rule, not read_input's), else exactly -9999.0.
+ *                    Tsurf is the FINAL kept row - behind every coupling replay and behind the blanking of rejected
+ *                    points, whose deficit therefore reads -9999.0 throughout; tdew is the kept merged value, whether
+ *                    or not merged[1] was asked for.
+ * The six outputs, the summaries, the group series, status, missing_index and `local` of a call do not depend on
+ * `kept`; the six series pointers of `out` may all be NULL.  A tile makes the wanted variables one at a time from its
+ * raw columns and plans, which stay on the device for the whole tile, into ONE extra [n_out][points] buffer (0.2 GB for
+ * 524 288 points and 49 rows), on the tile's stream, behind its time loop; columns at or beyond the tile's points are
+ * never sent to the host.  With device < 0 every block writes its own points' rows.  `kept` NULL, or all its eleven
+ * pointers NULL: rs_driver_run_grid.  tools/bench_kept_rows.py measures the cost (profiles/kept_rows.txt). */
+typedef struct RsDriverKept {
+  double *merged[10]; /* host [n_points][n_out] each, order of rs_driver_expand's `merged`
+                         (tair, tdew, VZ, Rhz, prec, SW, LW, SW_dir, LW_net, TSurfObs); NULL = not wanted */
+  double *deficit;    /* host [n_points][n_out] or NULL */
+} RsDriverKept;
+int32_t rs_driver_kept_fields(void); /* 10: the length of RsDriverKept::merged in the library */
+int rs_driver_run_kept(const RsDriverInput *in, const RsGridSource *const *grids /* [n_sources] or NULL */,
+                       const InputSettings *settings, const InputParameters *params, LocalParameters *local,
+                       const RsDriverOutput *out, const RsDriverSummary *summary, const RsDriverGroups *groups,
+                       const RsDriverKept *kept, int32_t device);
 /* Tiles: a call steps its points in tiles of ROADSURF_HIP_TILE_POINTS (default 524 288).  With
  * coupling the forcing windows of a tile span [first coupling-window start, last window end + 1]
  * of ITS points; a tile whose windows would exceed ROADSURF_HIP_WINDOW_BUDGET_MB (default 24 576)

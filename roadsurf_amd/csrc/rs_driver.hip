@@ -14,6 +14,8 @@
  *                              [t][point] windows the step kernels read
  *     step kernel              (layers 1-3), outputs decimated in the kernel
  *   outputs [row][point] --transpose--> [point][row] --D2H--> caller
+ *   kept_rows_kernel           on request (rs_driver_run_kept): the merged series at the kept rows, from the raw
+ *                              series and plans that are still there, and deficit_kernel over them and the result
  *
  * JsonSource::interpolate walks the raw and the simulation time axes together; which raw
  * interval a simulation index falls into, and whether it copies or interpolates there,
@@ -552,6 +554,77 @@ __global__ void __launch_bounds__(RS_BLOCK) raw_rows_kernel(const RawRowsArgs A)
   double v = merged_one(A.S, fld, p, A.idx[y], mask);
   if (A.status && A.status[p] != 0 && fld == R_TAIR) v = miss_r(); /* a rejected point: as expand_raw_kernel */
   A.out[y][slot] = v;
+}
+
+/* The merged series at the KEPT rows - 0-based simulation index r * step for kept row r, save_output's decimation
+ * (roadrunner.cpp:303) - as read_input returns them (rs_driver_run_kept): bit for bit what expand_raw_kernel writes at
+ * those indices for the test hook, which passes no status - a rejected point keeps its values.  One point per lane,
+ * variable y of the launch's list in blockIdx.y, rows in the loop: stores are whole lines of out[row][np_pad].
+ * Shared time axes: merged_one at each kept index - the plan entry one scalar load, the two raw ends coalesced across
+ * the lanes.  Per-point axes: ONE sequential walk over [0, SimLen) from initial_positions() that stores at the kept
+ * indices only; never from SrcDev::prp, which pp_advance_kernel moves during the time loop (the result must not depend
+ * on when this runs), and never by merged_at, whose replay from index 0 per row would be quadratic. */
+struct KeptRowsArgs {
+  SrcSet S;
+  int32_t nfld;
+  int32_t fld[NFLD];     /* the launch's variables */
+  double *out[NFLD];     /* [n_out][stride] each */
+  const int32_t *cpl_hi; /* [np_pad] or nullptr, as ExpandRawArgs */
+  int32_t cplLen;
+  int32_t step, n_out;   /* (n_out - 1) * step < SimLen */
+  int64_t stride;
+};
+template <bool PP>
+__global__ void __launch_bounds__(RS_BLOCK) kept_rows_kernel(const KeptRowsArgs A) {
+  __builtin_amdgcn_s_setprio(3); /* on a block's way out: waited for, beside other blocks' step kernels */
+  const int64_t p = (int64_t)blockIdx.x * RS_BLOCK + threadIdx.x;
+  const int y = blockIdx.y;
+  if (p >= A.S.npoints || y >= A.nfld) return;
+  const int fld = A.fld[y];
+  double *out = A.out[y] + p;
+  /* roadrunner.cpp:266-273: no road temperature input inside the coupling window (as expand_raw_kernel) */
+  int32_t clr_lo = 0, clr_hi = -1;
+  if (fld == R_OBS && A.cpl_hi) {
+    clr_hi = A.cpl_hi[p];
+    clr_lo = clr_hi - A.cplLen; /* exclusive */
+    if (clr_hi < 0) clr_lo = clr_hi;
+  }
+  const int32_t step = A.step;
+  const int64_t stride = A.stride;
+  if (!PP) {
+    for (int32_t r = 0; r < A.n_out; ++r) {
+      const int32_t i = r * step;
+      uint32_t mask;
+      double v = merged_one(A.S, fld, p, i, mask);
+      if (i > clr_lo && i <= clr_hi) v = miss_r();
+      out[(int64_t)r * stride] = v;
+    }
+  } else {
+    int32_t rp0[RS_MAX_SOURCES];
+    initial_positions(A.S, p, rp0);
+    int32_t next = 0, r = 0; /* the next kept index and its row */
+    walk_field<true>(A.S, fld, p, 0, A.S.simlen, rp0, [&](int32_t i, double v, uint32_t) {
+      if (i != next) return;
+      if (i > clr_lo && i <= clr_hi) v = miss_r();
+      out[(int64_t)r * stride] = v;
+      next += step;
+      ++r;
+    });
+  }
+}
+
+/* The dew-point deficit of the kept rows, in place over the kept dew point: x[r][p] = tsurf[r][p] - x[r][p] where both
+ * are not NaN and > -9000, else -9999.0 (roadsurf_amd/kept.py, dew_point_deficit).  tsurf: the final result rows. */
+__global__ void __launch_bounds__(RS_BLOCK) deficit_kernel(const double *__restrict__ tsurf, double *x, int64_t stride,
+                                                           int32_t nrows, int64_t npoints) {
+  __builtin_amdgcn_s_setprio(3); /* on a block's way out: waited for, beside other blocks' step kernels */
+  const int64_t p = (int64_t)blockIdx.x * RS_BLOCK + threadIdx.x;
+  if (p >= npoints) return;
+  for (int32_t r = 0; r < nrows; ++r) {
+    const int64_t k = (int64_t)r * stride + p;
+    const double a = tsurf[k], b = x[k];
+    x[k] = (a > -9000.0 && b > -9000.0) ? a - b : -9999.0; /* (a NaN compares false) */
+  }
 }
 
 /* Per-point walks: position at simulation index 0 ... */
@@ -1316,6 +1389,7 @@ struct RunPolicy {
   bool small_block = false;
   bool want_cluster = false; /* plan order, if the tile has more than one launch (TilePolicy::cluster) */
   bool timing = false;       /* ROADSURF_HIP_DRIVER_TIMING */
+  bool kept = false;         /* the call wants kept input rows or the deficit (rs_driver_run_kept): one more [n_out][mp] */
   int P = 0;                 /* points per tile */
   int TC = 0;                /* indices per launch */
   int nwin = 0;              /* forcing windows of a tile (SW_dir / LW_net only with sky view) */
@@ -1462,6 +1536,7 @@ struct Run : Call {
   const RsDriverSummary *sum; /* NULL: no summaries (rs_driver_run) */
   const RsDriverGroups *grp;  /* NULL: no group series */
   double *grp_acc;            /* device [rows][ngroups][cols]: this block's cells, merged into by every tile */
+  const RsDriverKept *kept;   /* NULL: no kept input rows, no deficit */
 };
 
 /* tiles the calling thread's last single-device rs_driver_run stepped (tests: the window budget), and how many
@@ -1493,6 +1568,7 @@ struct Tile : TileHead {
   Dev d_prev, d_row1;             /* preview rows of the forecast key; index 1's rows for the initial profile */
   Dev d_sum, d_sumpt;             /* the summaries [RS_SUM_COLS][mp], and as the caller holds them [m][RS_SUM_COLS] */
   Dev d_gid;                      /* the tile's slice of RsDriverGroups::group */
+  Dev d_kept;                     /* one variable's kept rows [n_out][mp], then the deficit (rs_driver_run_kept) */
   RsPointParams pp, pps;          /* in point order, in slot order */
   RsOutputs oo, oc;               /* the result [n_out][mp]; one launch's rows in slot order (rows_c) */
   size_t os = 0;                  /* mp * n_out */
@@ -1927,6 +2003,51 @@ struct Tile : TileHead {
                                   r.grp_acc, stream));
     return 0;
   }
+  /* d_kept [n_out][mp] -> [point][row] -> the tile's rows of a host array [n_points][n_out] */
+  int kept_block_home(double *host) {
+    HOK(transpose((const double *)d_kept.as<double>(), d_outpt.as<double>(), R.n_out, m, mp, R.n_out, stream));
+    HOK(hipMemcpyAsync(host + (size_t)p0 * R.n_out, d_outpt.p, (size_t)m * R.n_out * sizeof(double), hipMemcpyDeviceToHost,
+                       stream));
+    return 0;
+  }
+  /* The inputs at the kept rows and the dew-point deficit (rs_driver_run_kept): the wanted variables one at a time from
+   * the tile's raw columns and plans through the one buffer - the dew point first, which the deficit then replaces in
+   * place, reading the final, blanked surface temperature rows of the result block. */
+  int kept_home() {
+    const RsDriverKept &q = *r.kept;
+    HOK(d_kept.alloc(os * sizeof(double)));
+    KeptRowsArgs ka;
+    std::memset(&ka, 0, sizeof(ka));
+    ka.S = T.S;
+    ka.nfld = 1;
+    ka.out[0] = d_kept.as<double>();
+    ka.cpl_hi = R.coupled ? D.cpl_hi.as<int32_t>() : nullptr;
+    ka.cplLen = c.cplLen;
+    ka.step = R.step;
+    ka.n_out = R.n_out;
+    ka.stride = mp;
+    const int turn[NFLD] = {R_TDEW, R_TAIR, R_VZ, R_RHZ, R_PREC, R_SW, R_LW, R_SWDIR, R_LWNET, R_OBS};
+    for (int k = 0; k < NFLD; ++k) {
+      const int f = turn[k];
+      if (!q.merged[f] && !(f == R_TDEW && q.deficit)) continue;
+      ka.fld[0] = f;
+      const dim3 g((unsigned)(mp / RS_BLOCK), 1), b(RS_BLOCK);
+      if (T.any_pp)
+        hipLaunchKernelGGL(kept_rows_kernel<true>, g, b, 0, stream, ka);
+      else
+        hipLaunchKernelGGL(kept_rows_kernel<false>, g, b, 0, stream, ka);
+      HOK(hipGetLastError());
+      if (q.merged[f])
+        if (int rc = kept_block_home(q.merged[f])) return rc;
+      if (f == R_TDEW && q.deficit) {
+        hipLaunchKernelGGL(deficit_kernel, grid1(m), dim3(RS_BLOCK), 0, stream, (const double *)d_out.as<double>(),
+                           d_kept.as<double>(), (int64_t)mp, (int32_t)R.n_out, (int64_t)m);
+        HOK(hipGetLastError());
+        if (int rc = kept_block_home(q.deficit)) return rc;
+      }
+    }
+    return 0;
+  }
   /* blank what read_input rejected, then [row][point] -> [point][row] -> the caller's arrays */
   int outputs_home() {
     double *ob = d_out.as<double>();
@@ -1937,6 +2058,8 @@ struct Tile : TileHead {
       if (int rc = summaries_home()) return rc;
     if (r.grp)
       if (int rc = groups_home()) return rc;
+    if (r.kept)
+      if (int rc = kept_home()) return rc;
     double *dst[6] = {r.out->tsurf, r.out->snow, r.out->water, r.out->ice, r.out->deposit, r.out->ice2};
     for (int f = 0; f < 6; ++f) {
       if (!dst[f]) continue;
@@ -1946,7 +2069,7 @@ struct Tile : TileHead {
     }
     HOK(hipStreamSynchronize(stream));
     r.pt.lap(5);
-    for (Dev *d : {&d_phase, &d_outc, &d_pp_s, &d_geo_s, &d_out, &d_outpt, &d_prev, &d_sum, &d_sumpt, &d_gid}) d->release();
+    for (Dev *d : {&d_phase, &d_outc, &d_pp_s, &d_geo_s, &d_out, &d_outpt, &d_prev, &d_sum, &d_sumpt, &d_gid, &d_kept}) d->release();
     r.pt.lap(7);
     return 0;
   }
@@ -1992,6 +2115,7 @@ size_t arena_estimate(const RsDriverInput *in, const Common &c, const RunPolicy 
                 + 6 * mpx * (TC / R.step + 2) * 8      /* one launch's rows in slot order */
                 + 6 * mpx * 8 + L * 40;                /* previews, hour, sun */
   if (R.skyview) need += 2 * (size_t)360 * mpx * 8 + 8 * mpx * 8;
+  if (R.kept) need += mpx * (size_t)R.n_out * 8; /* one variable's kept rows */
   need += mpx * ((size_t)2 * RS_NSTATE * 8 + 64) + ((size_t)16 << 20); /* the tile's plan: two state blocks, order rows, sort scratch */
   need += need / 16 + ((size_t)64 << 10) * 64; /* alignment of ~60 pieces, slack */
   return need;
@@ -2141,7 +2265,7 @@ int upload_grids(const RsDriverInput *in, const RsGridSource *const *grids, cons
 /* points [pbeg, pend) of the input on one device */
 int driver_run_range(const RsDriverInput *in, const InputSettings *st, const InputParameters *params,
                      LocalParameters *local, const RsDriverOutput *out, const RsDriverSummary *sum,
-                     const RsDriverGroups *grp, int32_t device, int64_t pbeg, int64_t pend,
+                     const RsDriverGroups *grp, const RsDriverKept *kept, int32_t device, int64_t pbeg, int64_t pend,
                      const GridView *gv = nullptr) {
   Common c;
   RunPolicy R;
@@ -2164,6 +2288,7 @@ int driver_run_range(const RsDriverInput *in, const InputSettings *st, const Inp
     HOK(rs_cluster_group_reset(d_grp.as<double>(), grp->last_row - grp->first_row + 1, grp->spec, stream));
   }
   make_run_policy(st, consts, c, local, pbeg, pend, R);
+  R.kept = kept != nullptr;
   const Call call{in, st, c, consts, device, stream, local, out->status, out->missing_index};
 
   WindowLease arena_lease; /* (declared behind the stream guard: WindowLease::release) */
@@ -2190,7 +2315,7 @@ int driver_run_range(const RsDriverInput *in, const InputSettings *st, const Inp
   const int rows0 = R.cpl_chunked ? std::max(R.TC, std::min(c.L, c.cplLen + 2)) : R.TC;
   Run run{call, params, out, R, pbeg, pend,
           rs_bottom_temperature(params, &consts, in->year[0], in->month[0], in->day[0]), ax, pt, win,
-          R.use_raw ? 0 : (size_t)R.nwin * Ppad * rows0 * sizeof(double), sum, grp, d_grp.as<double>()};
+          R.use_raw ? 0 : (size_t)R.nwin * Ppad * rows0 * sizeof(double), sum, grp, d_grp.as<double>(), kept};
   if (run.win_bytes) HOK(win.acquire(run.win_bytes, device));
   pt.lap(6);
 
@@ -2299,8 +2424,13 @@ int driver_expand(const RsDriverInput *in, const RsGridSource *const *grids, con
 /* rs_driver_run and its kin: one device, or the fan-out */
 int driver_run(const RsDriverInput *in, const RsGridSource *const *grids, const InputSettings *st,
                const InputParameters *params, LocalParameters *local, const RsDriverOutput *out,
-               const RsDriverSummary *sum, const RsDriverGroups *grp, int32_t device) {
+               const RsDriverSummary *sum, const RsDriverGroups *grp, const RsDriverKept *kept, int32_t device) {
   if (!in || in->n_points < 1) return fail_msg("rs_driver_run: bad arguments", -1);
+  if (kept) { /* nothing wanted: as without */
+    bool any = kept->deficit != nullptr;
+    for (int f = 0; f < NFLD; ++f) any = any || kept->merged[f];
+    if (!any) kept = nullptr;
+  }
   if (grp) {
     if (!out) return fail_msg("rs_driver_run: bad arguments", -1);
     if (int rc = check_groups(grp, out->n_out)) return rc;
@@ -2321,7 +2451,7 @@ int driver_run(const RsDriverInput *in, const RsGridSource *const *grids, const 
       gv.dev = G.find(device);
     }
     rsu::g_last_fanout = 1;
-    return driver_run_range(in, st, params, local, out, sum, grp, device, 0, in->n_points, gridded ? &gv : nullptr);
+    return driver_run_range(in, st, params, local, out, sum, grp, kept, device, 0, in->n_points, gridded ? &gv : nullptr);
   }
   /* four blocks per device.  (Six for batches with local horizons were 4 % faster while the horizon table
    * was transposed on the device, tools/experiments/r4_blocks.sh; with the table left in the caller's layout
@@ -2339,7 +2469,7 @@ int driver_run(const RsDriverInput *in, const RsGridSource *const *grids, const 
   }
   return rsu::fan_out(shards, [&](const rsu::Shard &sh, int) {
     const GridView v{grids, G.find(sh.device)};
-    return driver_run_range(in, st, params, local, out, sum, grp, sh.device, sh.off, sh.off + sh.cnt,
+    return driver_run_range(in, st, params, local, out, sum, grp, kept, sh.device, sh.off, sh.off + sh.cnt,
                             gridded ? &v : nullptr);
   });
 }
@@ -2398,7 +2528,7 @@ int rs_driver_run_summary(const RsDriverInput *in, const InputSettings *st, cons
 int rs_driver_run_groups(const RsDriverInput *in, const InputSettings *st, const InputParameters *params,
                          LocalParameters *local, const RsDriverOutput *out, const RsDriverSummary *sum,
                          const RsDriverGroups *grp, int32_t device) {
-  return driver_run(in, nullptr, st, params, local, out, sum, grp, device);
+  return rs_driver_run_grid(in, nullptr, st, params, local, out, sum, grp, device);
 }
 
 /* ... and with sources that arrive as fields: the calling thread checks them and puts their fields on every device of
@@ -2406,7 +2536,16 @@ int rs_driver_run_groups(const RsDriverInput *in, const InputSettings *st, const
 int rs_driver_run_grid(const RsDriverInput *in, const RsGridSource *const *grids, const InputSettings *st,
                        const InputParameters *params, LocalParameters *local, const RsDriverOutput *out,
                        const RsDriverSummary *sum, const RsDriverGroups *grp, int32_t device) {
-  return driver_run(in, grids, st, params, local, out, sum, grp, device);
+  return rs_driver_run_kept(in, grids, st, params, local, out, sum, grp, nullptr, device);
+}
+
+/* ... and with the inputs the model saw at the kept rows and the dew-point deficit: every tile makes them from its raw
+ * columns behind its time loop, every block fills its points' rows of the host arrays */
+int32_t rs_driver_kept_fields(void) { return NFLD; }
+int rs_driver_run_kept(const RsDriverInput *in, const RsGridSource *const *grids, const InputSettings *st,
+                       const InputParameters *params, LocalParameters *local, const RsDriverOutput *out,
+                       const RsDriverSummary *sum, const RsDriverGroups *grp, const RsDriverKept *kept, int32_t device) {
+  return driver_run(in, grids, st, params, local, out, sum, grp, kept, device);
 }
 
 } /* extern "C" */

@@ -74,6 +74,10 @@ class RsGridSource(C.Structure):
         ("stencil", C.c_int32), ("node", abi.c_int32_p), ("weight", abi.c_double_p)]
 
 
+class RsDriverKept(C.Structure):
+    _fields_ = [("merged", abi.c_double_p * len(MERGED_FIELDS)), ("deficit", abi.c_double_p)]
+
+
 @dataclasses.dataclass
 class RawSource:
     """One data source: ``fields`` name -> [n_points][n_times] float64 (absent name = variable
@@ -248,6 +252,11 @@ def _bind(L):
         L.rs_driver_expand_grid.argtypes = [P(RsDriverInput), P(P(RsGridSource)), P(abi.InputSettings),
                                             P(abi.LocalParameters), abi.c_double_p, abi.c_int32_p, abi.c_int32_p,
                                             C.c_int32]
+    if hasattr(L, "rs_driver_kept_fields"):
+        L.rs_driver_kept_fields.restype = C.c_int32
+        L.rs_driver_run_kept.argtypes = [P(RsDriverInput), P(P(RsGridSource)), P(abi.InputSettings),
+                                         P(abi.InputParameters), P(abi.LocalParameters), P(RsDriverOutput),
+                                         P(RsDriverSummary), P(RsDriverGroups), P(RsDriverKept), C.c_int32]
     return L
 
 
@@ -288,11 +297,13 @@ def run(sources, settings: abi.InputSettings, params: abi.InputParameters, start
         forecast_time: int, local=None, cal: dict | None = None,
         horizons: np.ndarray | None = None, device: int = 0, out: dict | None = None,
         summary=None, summary_rows: tuple[int, int] | None = None, series: bool = True,
-        groups=None, group_of=None, group_rows: tuple[int, int] | None = None) -> dict:
+        groups=None, group_of=None, group_rows: tuple[int, int] | None = None,
+        kept=(), deficit: bool = False) -> dict:
     """read_input + runsimulation + save_output's decimation for all points.  Returns the six
     outputs as [n][n_out] arrays plus ``status``, ``missing_index``, ``local`` and ``step``.
     ``device`` < 0 fans the points out over ROADSURF_HIP_DEVICES; ``out`` = a result dict of an
-    earlier call with the same shapes, whose arrays are written again (no fresh allocation).
+    earlier call with the same shapes, whose arrays are written again (no fresh allocation; its ``kept`` and
+    ``deficit`` arrays too).
     ``summary`` = a summary.SummarySpec: the result also has ``summary``, float64 [n][RS_SUM_COLS], the per-point
     summaries (roadsurf_amd/summary.py) of the kept rows ``summary_rows`` = (first_row, last_row) - default all
     of them, ``forecast_rows`` gives the forecast part - reduced on the device (rs_driver_run_summary);
@@ -303,8 +314,20 @@ def run(sources, settings: abi.InputSettings, params: abi.InputParameters, start
     ``series=False``.
     ``sources`` may hold ``grid.GridSource`` entries, mixed with ``RawSource`` ones: their fields go to the device
     as they are and are gathered to the points there (rs_driver_run_grid); the result is that of the same call on
-    ``grid.to_raw_source`` of them."""
+    ``grid.to_raw_source`` of them.
+    ``kept`` = names among ``MERGED_FIELDS``: the result also has ``kept``, name -> float64 [n][n_out], the inputs the
+    model saw at the kept rows - ``read_input``'s ``merged`` at every ``step``-th index (roadsurf_amd/kept.py), for
+    every point, rejected ones included - made on the device from the raw series (rs_driver_run_kept).
+    ``deficit=True``: the result also has ``deficit``, float64 [n][n_out], ``kept.dew_point_deficit`` of the final
+    surface temperature rows and the kept dew point.  Either counts as a summary for ``series=False``."""
     L = _bind(rslib.load())
+    kept = tuple(kept or ())
+    for name in kept:
+        if name not in MERGED_FIELDS:
+            raise KeyError(name)
+    want_kept = bool(kept) or bool(deficit)
+    if want_kept and (not hasattr(L, "rs_driver_kept_fields") or L.rs_driver_kept_fields() != len(MERGED_FIELDS)):
+        raise RuntimeError("this libroadsurf_hip.so has no kept input rows (rs_driver_kept_fields)")
     if cal is None:
         cal = calendar(start_time, settings.SimLen, int(settings.DTSecs))
     inp, grids, keep = make_grid_input(sources, start_time, forecast_time, cal, horizons)
@@ -313,8 +336,13 @@ def run(sources, settings: abi.InputSettings, params: abi.InputParameters, start
     n = inp.n_points
     step, n_out = output_rows(settings)
     larr = _locals(n, local)
-    if not series and summary is None and groups is None:
-        raise ValueError("series=False needs a summary or groups")
+    if not series and summary is None and groups is None and not want_kept:
+        raise ValueError("series=False needs a summary, groups, kept or deficit")
+    earlier = out if out is not None else {}
+
+    def rows(old):  # an [n][n_out] array of the earlier result, or a fresh one
+        ok = old is not None and old.shape == (n, n_out) and old.dtype == np.float64 and old.flags.c_contiguous
+        return old if ok else np.full((n, n_out), np.nan)
     if out is not None and series and out["tsurf"].shape == (n, n_out):
         res = {k: out[k] for k in OUT_FIELDS + ("status", "missing_index")}
     else:
@@ -346,7 +374,18 @@ def run(sources, settings: abi.InputSettings, params: abi.InputParameters, start
         res["groups"] = np.full((max(glast - gfirst + 1, 1), int(groups.ngroups), rslib.group_cols(groups)), np.nan)
         g = RsDriverGroups(rslib.group_spec(groups), gid.ctypes.data_as(abi.c_int32_p), gfirst, glast,
                            res["groups"].ctypes.data_as(abi.c_double_p))
-    if grids is not None:
+    if want_kept:
+        kq = RsDriverKept()
+        res["kept"] = {name: rows(earlier.get("kept", {}).get(name)) for name in kept}
+        for name, a in res["kept"].items():
+            kq.merged[MERGED_FIELDS.index(name)] = a.ctypes.data_as(abi.c_double_p)
+        if deficit:
+            res["deficit"] = rows(earlier.get("deficit"))
+            kq.deficit = res["deficit"].ctypes.data_as(abi.c_double_p)
+        rslib.check(L.rs_driver_run_kept(C.byref(inp), grids, C.byref(settings), C.byref(params), larr, C.byref(out),
+                                         C.byref(q) if q is not None else None,
+                                         C.byref(g) if g is not None else None, C.byref(kq), device), "rs_driver_run_kept")
+    elif grids is not None:
         rslib.check(L.rs_driver_run_grid(C.byref(inp), grids, C.byref(settings), C.byref(params), larr, C.byref(out),
                                          C.byref(q) if q is not None else None,
                                          C.byref(g) if g is not None else None, device), "rs_driver_run_grid")
@@ -420,10 +459,14 @@ def read_json_source(path: str, is_observation: bool = False, utc: bool = True):
     return src, ids, np.asarray(lats), np.asarray(lons)
 
 
-def save_output(path: str, result: dict, ids, lats, lons, start_time: int, dtsecs: int) -> None:
+def save_output(path: str, result: dict, ids, lats, lons, start_time: int, dtsecs: int, extra: dict | None = None) -> None:
     """Write the forecast like save_output/write_output (roadrunner.cpp:285-347): one object per
     simulated point with the kept times and RoadTemperature/Water/Ice/Snow/Deposit.  Numbers are
-    written with Python's shortest round-trip repr (the reference asks jsoncpp for 7 digits)."""
+    written with Python's shortest round-trip repr (the reference asks jsoncpp for 7 digits).
+    ``extra`` = {"tair", "tdew", "deficit"}, [n][n_out] each - ``dict(res["kept"], deficit=res["deficit"])`` of a
+    ``run(..., kept=("tair", "tdew"), deficit=True)``: every station also gets "AirTemperature", "DewPoint" and
+    "DewPointDeficit", what the reference's operational program stores beside the surface temperature
+    (examples/example2/src/QueryDataTools.cpp:323-347).  Without it the file is what it always was."""
     step = result["step"]
     n_out = result["tsurf"].shape[1]
     tstr = [_time.strftime("%Y-%m-%dT%H:%M", _time.gmtime(start_time + r * step * dtsecs))
@@ -438,5 +481,10 @@ def save_output(path: str, result: dict, ids, lats, lons, start_time: int, dtsec
             "Ice": result["ice"][p].tolist(), "Snow": result["snow"][p].tolist(),
             "Deposit": result["deposit"][p].tolist(),
         })
+        if extra is not None:
+            forecast[-1].update({
+                "AirTemperature": np.asarray(extra["tair"])[p].tolist(), "DewPoint": np.asarray(extra["tdew"])[p].tolist(),
+                "DewPointDeficit": np.asarray(extra["deficit"])[p].tolist(),
+            })
     with open(path, "w") as fh:
         json.dump(forecast, fh, indent=3)

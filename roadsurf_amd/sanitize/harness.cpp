@@ -6,9 +6,9 @@
 //            limited to ROADSURF_HIP_COALESCE_MAX callers per batch (set by the test: 5 < threads)
 //   phase 2  threads that come and go (thread-local caches adopted by later threads, rs_host.hip CallerCache)
 //   phase 3  four concurrent runsimulation_batch calls of different sizes (arena / plan bookkeeping)
-//   phase 4  rs_driver_run_groups, which rs_driver_run and rs_driver_run_summary are calls of, with and without the
-//            summaries from two threads (shards, segment table, per-block worker threads, the blocks' merge into the
-//            one array of group series)
+//   phase 4  rs_driver_run_kept, which rs_driver_run and its kin are calls of, with and without the summaries from
+//            three threads (shards, segment table, per-block worker threads, the blocks' merge into the one array of
+//            group series, the blocks' rows of the kept inputs and the deficit)
 // usage: harness [threads=64] [points=640]      exit code 0 and "sanitize harness ok" when every call returned
 #include <atomic>
 #include <cmath>
@@ -201,7 +201,22 @@ void driver_call(int n, int hours, bool coupling, bool gridded = false) {
   g.first_row = n_out / 2;
   g.last_row = n_out - 1;
   g.series = cells.data();
-  const int rc = rs_driver_run_grid(&in, gridded ? grids : nullptr, &s, &p, local.data(), &out, coupling ? &q : nullptr, &g, -1);
+  /* ... and the coupled call for three of the inputs at the kept rows and the dew-point deficit: every block's worker
+   * fills its points' rows of the host arrays */
+  std::vector<double> k_tair((size_t)n * n_out, -1.0), k_tdew(k_tair), k_obs(k_tair), k_def(k_tair);
+  RsDriverKept kept;
+  std::memset(&kept, 0, sizeof(kept));
+  kept.merged[0] = k_tair.data();
+  kept.merged[1] = k_tdew.data();
+  kept.merged[9] = k_obs.data();
+  kept.deficit = k_def.data();
+  if (rs_driver_kept_fields() != 10) {
+    fprintf(stderr, "rs_driver_kept_fields -> %d\n", rs_driver_kept_fields());
+    g_errors++;
+    return;
+  }
+  const int rc = rs_driver_run_kept(&in, gridded ? grids : nullptr, &s, &p, local.data(), &out, coupling ? &q : nullptr, &g,
+                                    coupling ? &kept : nullptr, -1);
   if (rc != 0) {
     fprintf(stderr, "rs_driver_run(%d points) -> %d: %s\n", n, rc, rs_last_error());
     g_errors++;

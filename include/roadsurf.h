@@ -758,6 +758,73 @@ int rs_hip_outputs_groups(RsPlan *plan, const RsOutputs *src, int32_t nrows, con
                           const int32_t *order_device, const RsGroupSpec *spec, double *acc_device, int64_t acc_rows,
                           int64_t acc_row0, void *stream);
 
+/* Per-point threshold episodes, reduced from the output rows on the device (the ABI number stays: every name here is
+ * new, a binding detects them with rs_hip_episode_cols).  The summaries say how cold, when first below a threshold and
+ * for how many rows; a surface that thaws at midday and refreezes at night has several intervals, and only the series
+ * themselves told from when to when.  An EPISODE is a maximal run of consecutive output rows of one point on which a
+ * condition of the caller's holds - a conjunction of strict bounds on any of RS_EPI_VARS variables: Tsurf, Snow,
+ * Water, Ice, Deposit, Ice2 and the dew-point deficit Tsurf - tdew (RsDriverKept::deficit), in this order.
+ *   use               bit k set: variable k is tested, and passes iff above[k] < x and x < below[k] - both strict,
+ *                     -inf / +inf make a bound one-sided, a NaN compares false
+ *   peak              0..6: the variable whose maximum a record keeps
+ *   min_rows          >= 1: a run of fewer rows is dropped and counted nowhere
+ *   max_episodes      K in 1..RS_EPI_MAX: the first K episodes of a point are kept as records, later ones only counted
+ * A spec is refused if use is 0 or has a bit at RS_EPI_VARS or above, if a bound is NaN, and outside these ranges.
+ * A row of a point HOLDS iff its Tsurf is not exactly -9999.0 (the validity rule of the summaries), every used
+ * variable passes and - if the deficit is used - the deficit is not exactly -9999.0 (what a deficit without both
+ * operands reads).  A -9999.0 in a peak variable that is not used in the condition is an ordinary number.
+ * The accumulator of the caller is
+ *     acc_device[col * npoints_padded + point],   point = order[slot],   double,
+ * cols = rs_hip_episode_cols(spec) = RS_EPI_HEAD + K * RS_EPI_REC columns:
+ *   0         episodes committed, those beyond K included
+ *   1         rows in committed episodes
+ *   2         rows of the longest committed episode
+ *   3         the time index the next row must have to continue the open run (0 = nothing expected)
+ *   4..9      the open run, as a record (rows 0 = none)
+ *   10+6j ..  record j = 0..K-1: first time index, last time index, rows, min Tsurf, time index of it (the smallest
+ *             among equals), max of the peak variable
+ * Extremes use strict comparisons and a NaN never wins; the empty record is {0, 0, 0, +inf, 0, -inf}.
+ * Unlike the summaries this reduction is ORDER DEPENDENT: rs_hip_outputs_episodes feeds the first `nrows` rows of a
+ * window `src` ([row][slot], of any launch and any flavour) to every point's automaton in sequence, row r being the
+ * absolute 1-based time index i = index0 + r*index_step.  Per row: if column 3 is non-zero and differs from i, the
+ * open run is closed; column 3 becomes i + index_step; if the row holds it extends the open run (whose first index is
+ * set when its rows go from 0 to 1), otherwise the open run is closed.  Closing: a run of at least min_rows rows is
+ * copied into record number [column 0] if that is below K, then column 0 grows by one, column 1 by the run's rows and
+ * column 2 rises to them; in every case the run is cleared.  So the calls of a pass feed consecutive rows in time
+ * order - cut anywhere, the result is that of one call -, and a call whose index0 is not the expected index starts
+ * afresh behind a gap.  rs_hip_episodes_finish closes every point's open run and sets column 3 to 0: what a consumer
+ * reads; it is idempotent.  rs_hip_episodes_reset writes the accumulator of no rows into all npoints_padded columns
+ * of the cols rows.  The definition, in numpy: roadsurf_amd/episodes.py.
+ * `deficit_device` holds the deficit of the same rows in the layout of the window, [row][slot] with src->t_stride; it
+ * is required iff bit 6 is used or peak is 6, and the call is refused without it then.  On an fp32 plan the members of
+ * `src` and the deficit rows are float arrays, widened exactly.  `order_device` and `stream` as for
+ * rs_hip_outputs_summary: NULL = the plan's current order, on the plan's stream; a stream of the caller's only with a
+ * kept order row; an order entry outside [0, npoints) writes nothing.  All six streams are required; t_stride >=
+ * npoints.  Columns of points >= npoints are never touched by the feed and the finish, rows at or beyond cols by none
+ * of the three.  The accumulator is in POINT order, so re-sorts between the calls do not matter.  One lane owns a
+ * slot and walks its rows in order (they are not split over wavefronts as the summary's are: the automaton is
+ * sequential); it reads 48 B per point and row, 56 B with the deficit (half of that from an fp32 window), and reads and
+ * writes 80 B per point and call plus 48 B per committed episode: measured cost in profiles/episode_outputs.txt
+ * (tools/bench_episode_outputs.py). */
+#define RS_EPI_VARS 7
+#define RS_EPI_MAX 8
+#define RS_EPI_HEAD 10
+#define RS_EPI_REC 6
+typedef struct RsEpisodeSpec {
+  int32_t use;                /* bit k: variable k is tested (Tsurf, Snow, Water, Ice, Deposit, Ice2, deficit) */
+  int32_t peak;               /* 0..6: the variable whose maximum a record keeps */
+  int32_t min_rows;           /* >= 1 */
+  int32_t max_episodes;       /* K: 1..RS_EPI_MAX */
+  double above[RS_EPI_VARS];  /* variable k passes iff above[k] < x ... */
+  double below[RS_EPI_VARS];  /* ... and x < below[k] */
+} RsEpisodeSpec;
+int32_t rs_hip_episode_cols(const RsEpisodeSpec *spec); /* RS_EPI_HEAD + K * RS_EPI_REC; <0: bad spec (host only) */
+int rs_hip_episodes_reset(RsPlan *plan, const RsEpisodeSpec *spec, double *acc_device, void *stream);
+int rs_hip_outputs_episodes(RsPlan *plan, const RsOutputs *src, const void *deficit_device, int32_t nrows,
+                            int32_t index0, int32_t index_step, const int32_t *order_device, const RsEpisodeSpec *spec,
+                            double *acc_device, void *stream);
+int rs_hip_episodes_finish(RsPlan *plan, const RsEpisodeSpec *spec, double *acc_device, void *stream);
+
 /* Gridded fields gathered to points on the device (the ABI number stays: every name here is new, a binding detects
  * them with rs_hip_grid_max_stencil).  A weather model delivers fields [time][node]; every kernel here reads series
  * [time][point].  Each point has a stencil of `stencil` nodes, node_device[point * stencil + k] (int32) with weights
@@ -1002,6 +1069,26 @@ int rs_driver_run_kept(const RsDriverInput *in, const RsGridSource *const *grids
                        const InputSettings *settings, const InputParameters *params, LocalParameters *local,
                        const RsDriverOutput *out, const RsDriverSummary *summary, const RsDriverGroups *groups,
                        const RsDriverKept *kept, int32_t device);
+/* ... and with per-point threshold episodes of the kept rows [first_row, last_row] (rs_hip_outputs_episodes defines
+ * them; the ABI number stays, a binding detects the call with rs_hip_episode_cols): cols = rs_hip_episode_cols(&spec)
+ * doubles per point, FINISHED, the time index of kept row r being r*step + 1.  Every tile resets its accumulator, feeds
+ * the rows in one call from its result block - where the summaries are reduced: behind the blanking of rejected points,
+ * whose episodes are the empty accumulator, and behind every coupling replay -, finishes, and only n_points * cols
+ * doubles come home for them.  A spec that uses the deficit (bit 6, or peak 6) has the tile make it, from the kept dew
+ * point and the final Tsurf rows, whether or not `kept` asks for it: the very values RsDriverKept::deficit returns for
+ * the same call, made once per tile when both want them, in one further [n_out][points] buffer of the tile (0.2 GB for
+ * 524 288 points and 49 rows).  With device < 0 every block writes its own points' rows.  The six series pointers of
+ * `out` may all be NULL.  The six outputs, the summaries, the group series, the kept arrays, status, missing_index and
+ * `local` of a call do not depend on `episodes`.  `episodes` NULL: rs_driver_run_kept. */
+typedef struct RsDriverEpisodes {
+  RsEpisodeSpec spec;
+  int32_t first_row, last_row;
+  double *episodes; /* host [n_points][cols] */
+} RsDriverEpisodes;
+int rs_driver_run_episodes(const RsDriverInput *in, const RsGridSource *const *grids /* [n_sources] or NULL */,
+                           const InputSettings *settings, const InputParameters *params, LocalParameters *local,
+                           const RsDriverOutput *out, const RsDriverSummary *summary, const RsDriverGroups *groups,
+                           const RsDriverKept *kept, const RsDriverEpisodes *episodes, int32_t device);
 /* Tiles: a call steps its points in tiles of ROADSURF_HIP_TILE_POINTS (default 524 288).  With
  * coupling the forcing windows of a tile span [first coupling-window start, last window end + 1]
  * of ITS points; a tile whose windows would exceed ROADSURF_HIP_WINDOW_BUDGET_MB (default 24 576)

@@ -555,6 +555,49 @@ int rs_hip_outputs_groups(RsPlan *pl, const RsOutputs *src, int32_t nrows, const
   return 0;
 }
 
+int32_t rs_hip_episode_cols(const RsEpisodeSpec *spec) { return rs_cluster_episode_cols(spec); }
+
+static const char *const EPISODE_SPEC_MSG =
+    ": bad spec (use: bits 0..6, at least one; no NaN bound; peak 0..6; min_rows >= 1; max_episodes 1..RS_EPI_MAX)";
+
+int rs_hip_episodes_reset(RsPlan *pl, const RsEpisodeSpec *spec, double *acc, void *stream) {
+  if (!pl || !spec || !acc) return set_err("rs_hip_episodes_reset: bad arguments");
+  if (rs_cluster_episode_cols(spec) < 0) return set_err("rs_hip_episodes_reset%s", EPISODE_SPEC_MSG);
+  HIP_OK(hipSetDevice(pl->device));
+  HIP_OK(rs_cluster_episodes_reset(acc, pl->np_pad, *spec, stream ? (hipStream_t)stream : pl->stream));
+  return 0;
+}
+
+int rs_hip_outputs_episodes(RsPlan *pl, const RsOutputs *src, const void *deficit, int32_t nrows, int32_t index0,
+                            int32_t index_step, const int32_t *order, const RsEpisodeSpec *spec, double *acc,
+                            void *stream) {
+  if (!pl || !src || !spec || !acc || nrows < 1 || index0 < 1 || index_step < 1 ||
+      (int64_t)index0 + (int64_t)nrows * index_step > INT32_MAX)
+    return set_err("rs_hip_outputs_episodes: bad arguments (nrows >= 1 rows at the time indices index0 + r*index_step, index0 >= 1, index_step >= 1)");
+  if (rs_cluster_episode_cols(spec) < 0) return set_err("rs_hip_outputs_episodes%s", EPISODE_SPEC_MSG);
+  if (!deficit && (((spec->use >> 6) & 1) || spec->peak == 6))
+    return set_err("rs_hip_outputs_episodes: this spec uses the deficit (bit 6 or peak 6): deficit_device is required");
+  const void *in[6] = {src->tsurf, src->snow, src->water, src->ice, src->deposit, src->ice2};
+  for (int f = 0; f < 6; ++f)
+    if (!in[f]) return set_err("rs_hip_outputs_episodes: all six streams are required");
+  if (src->t_stride < pl->npoints) return set_err("rs_hip_outputs_episodes: t_stride below the plan's points");
+  if (!order && stream) return set_err("rs_hip_outputs_episodes: on a stream of the caller's the order row must be a kept one");
+  if (!order && !rs_hip_plan_order(pl)) return -1;
+  HIP_OK(hipSetDevice(pl->device));
+  HIP_OK(rs_cluster_outputs_episodes(in, deficit, pl->f32, order ? order : pl->order, pl->npoints, src->t_stride, nrows,
+                                     index0, index_step, *spec, acc, pl->np_pad,
+                                     stream ? (hipStream_t)stream : pl->stream));
+  return 0;
+}
+
+int rs_hip_episodes_finish(RsPlan *pl, const RsEpisodeSpec *spec, double *acc, void *stream) {
+  if (!pl || !spec || !acc) return set_err("rs_hip_episodes_finish: bad arguments");
+  if (rs_cluster_episode_cols(spec) < 0) return set_err("rs_hip_episodes_finish%s", EPISODE_SPEC_MSG);
+  HIP_OK(hipSetDevice(pl->device));
+  HIP_OK(rs_cluster_episodes_finish(acc, pl->npoints, pl->np_pad, *spec, stream ? (hipStream_t)stream : pl->stream));
+  return 0;
+}
+
 int32_t rs_hip_grid_max_stencil(void) { return RS_GRID_MAX_STENCIL; }
 
 int rs_hip_gather_nodes(RsPlan *pl, const double *src, int32_t nrows, int64_t n_nodes, int64_t src_stride,

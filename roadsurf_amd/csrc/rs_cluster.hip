@@ -297,6 +297,190 @@ hipError_t rs_cluster_outputs_summary(const void *const src[6], bool f32, const 
   return hipGetLastError();
 }
 
+/* Per-point threshold episodes of the output rows (include/roadsurf.h, rs_hip_outputs_episodes; the definition is
+ * roadsurf_amd/episodes.py, feed): the third sibling.  Unlike the summaries this reduction is order dependent - an
+ * automaton per point that is fed its rows in sequence - so the rows of a slot are NOT split over wavefronts: one lane
+ * owns a slot, loads its head and open run (RS_EPI_HEAD doubles) into registers, walks the rows in order with EPI_ROWS
+ * rows of all seven streams in flight (every row load a coalesced 512 B per wavefront and stream, 256 B of an fp32
+ * window) and stores the head back at the end.  A few hundred points by tens of rows is microseconds either way, and
+ * a million points fill the device with slots alone.  A run that closes with enough rows is committed by storing its
+ * six doubles straight to acc[(RS_EPI_HEAD + RS_EPI_REC * j + c) * np_pad + p], a computed address: the K records are
+ * never held in registers, where an array indexed by the run-time j would put the kernel into scratch.  A point sits
+ * in one slot: plain loads and stores, no atomics; all offsets are 64-bit. */
+int32_t rs_cluster_episode_cols(const RsEpisodeSpec *spec) {
+  if (!spec) return -1;
+  if (spec->use <= 0 || (spec->use >> RS_EPI_VARS) != 0) return -1;
+  for (int k = 0; k < RS_EPI_VARS; ++k)
+    if (spec->above[k] != spec->above[k] || spec->below[k] != spec->below[k]) return -1;
+  if (spec->peak < 0 || spec->peak >= RS_EPI_VARS) return -1;
+  if (spec->min_rows < 1) return -1;
+  if (spec->max_episodes < 1 || spec->max_episodes > RS_EPI_MAX) return -1;
+  return RS_EPI_HEAD + spec->max_episodes * RS_EPI_REC;
+}
+
+namespace {
+constexpr int EPI_ROWS = 4;
+
+struct Epi {
+  double h[RS_EPI_HEAD]; /* the head columns of include/roadsurf.h: everything fp64, indices and counts are exact */
+  __device__ void clear_run() {
+    h[4] = 0.0; h[5] = 0.0; h[6] = 0.0;
+    h[7] = __builtin_huge_val();
+    h[8] = 0.0;
+    h[9] = -__builtin_huge_val();
+  }
+  __device__ void load(const double *p, int64_t stride) {
+#pragma unroll
+    for (int c = 0; c < RS_EPI_HEAD; ++c) h[c] = p[c * stride];
+  }
+  __device__ void store(double *p, int64_t stride) const {
+#pragma unroll
+    for (int c = 0; c < RS_EPI_HEAD; ++c) p[c * stride] = h[c];
+  }
+  /* close the open run: committed if it has min_rows rows - kept as record number h[0] while that is below K -,
+   * cleared in every case.  `col` is the point's column of the accumulator. */
+  __device__ void close(double *col, int64_t stride, const RsEpisodeSpec &sp) {
+    if (h[6] >= (double)sp.min_rows) {
+      if (h[0] >= 0.0 && h[0] < (double)sp.max_episodes) { /* (a record number of the caller's making stays inside) */
+        double *rec = col + ((int64_t)RS_EPI_HEAD + (int64_t)RS_EPI_REC * (int64_t)h[0]) * stride;
+#pragma unroll
+        for (int c = 0; c < RS_EPI_REC; ++c) rec[c * stride] = h[4 + c];
+      }
+      h[0] += 1.0;
+      h[1] += h[6];
+      if (h[6] > h[2]) h[2] = h[6];
+    }
+    clear_run();
+  }
+  /* one row of the point: its time index, the seven variables */
+  __device__ void row(double i, double step, const double x[RS_EPI_VARS], double *col, int64_t stride,
+                      const RsEpisodeSpec &sp) {
+    if (h[3] != 0.0 && h[3] != i) close(col, stride, sp);
+    h[3] = i + step;
+    bool ok = x[0] != -9999.0; /* never saved: behind the last index of a failed point, or a rejected point */
+#pragma unroll
+    for (int k = 0; k < RS_EPI_VARS; ++k)
+      if ((sp.use >> k) & 1) ok = ok && sp.above[k] < x[k] && x[k] < sp.below[k];
+    if ((sp.use >> 6) & 1) ok = ok && x[6] != -9999.0; /* no deficit there (roadsurf_amd/kept.py) */
+    if (!ok) {
+      close(col, stride, sp);
+      return;
+    }
+    double pk = x[0]; /* a select per variable: x[sp.peak] would index registers with a run-time number */
+#pragma unroll
+    for (int k = 1; k < RS_EPI_VARS; ++k) pk = sp.peak == k ? x[k] : pk;
+    if (h[6] == 0.0) h[4] = i;
+    h[5] = i;
+    h[6] += 1.0;
+    if (x[0] < h[7]) { h[7] = x[0]; h[8] = i; } /* strict, in order: the smallest index among equals; a NaN never wins */
+    if (pk > h[9]) h[9] = pk;
+  }
+};
+
+struct EpisodeArgs {
+  const void *src[RS_EPI_VARS]; /* T[nrows][stride] each: Tsurf, Snow, Water, Ice, Deposit, Ice2, deficit (or NULL) */
+  const int32_t *order;         /* column s is point order[s]; NULL: point s (rs_driver_run's result block) */
+  double *acc;                  /* [cols][np_pad], point order */
+  int64_t npoints, stride, np_pad;
+  int32_t nrows, index0, index_step;
+  RsEpisodeSpec spec;
+};
+
+template <typename T>
+__global__ void __launch_bounds__(RS_BLOCK) outputs_episodes_kernel(const EpisodeArgs a) {
+  const int64_t s = (int64_t)blockIdx.x * RS_BLOCK + threadIdx.x;
+  if (s >= a.npoints) return;
+  const int64_t p = a.order ? (int64_t)a.order[s] : s;
+  if (p < 0 || p >= a.npoints) return; /* not an order row of this plan: nothing is written */
+  double *col = a.acc + p;
+  Epi e;
+  e.load(col, a.np_pad);
+  const bool with_deficit = a.src[6] != nullptr;
+  const double step = (double)a.index_step;
+#pragma unroll 1
+  for (int32_t r0 = 0; r0 < a.nrows; r0 += EPI_ROWS) {
+    T x[EPI_ROWS][RS_EPI_VARS];
+#pragma unroll
+    for (int q = 0; q < EPI_ROWS; ++q) {
+      const int32_t r = r0 + q < a.nrows ? r0 + q : a.nrows - 1; /* behind the range: its last row again, not taken */
+#pragma unroll
+      for (int f = 0; f < 6; ++f) x[q][f] = static_cast<const T *>(a.src[f])[(int64_t)r * a.stride + s];
+      x[q][6] = with_deficit ? static_cast<const T *>(a.src[6])[(int64_t)r * a.stride + s] : (T)0;
+    }
+#pragma unroll
+    for (int q = 0; q < EPI_ROWS; ++q) {
+      if (r0 + q >= a.nrows) break;
+      const double v[RS_EPI_VARS] = {(double)x[q][0], (double)x[q][1], (double)x[q][2], (double)x[q][3],
+                                     (double)x[q][4], (double)x[q][5], (double)x[q][6]};
+      e.row((double)a.index0 + (double)(r0 + q) * step, step, v, col, a.np_pad, a.spec);
+    }
+  }
+  e.store(col, a.np_pad);
+}
+
+__global__ void __launch_bounds__(RS_BLOCK) episodes_finish_kernel(double *acc, int64_t npoints, int64_t np_pad,
+                                                                   const RsEpisodeSpec spec) {
+  const int64_t p = (int64_t)blockIdx.x * RS_BLOCK + threadIdx.x;
+  if (p >= npoints) return;
+  Epi e;
+  e.load(acc + p, np_pad);
+  e.close(acc + p, np_pad, spec);
+  e.h[3] = 0.0;
+  e.store(acc + p, np_pad);
+}
+
+/* the accumulator of no rows into all np_pad columns: the head, then the K empty records */
+__global__ void __launch_bounds__(RS_BLOCK) episodes_reset_kernel(double *acc, int64_t np_pad, int32_t nrec) {
+  const int64_t p = (int64_t)blockIdx.x * RS_BLOCK + threadIdx.x;
+  if (p >= np_pad) return;
+  Epi e;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) e.h[c] = 0.0;
+  e.clear_run();
+  e.store(acc + p, np_pad);
+  for (int32_t j = 0; j < nrec; ++j) {
+    double *rec = acc + p + ((int64_t)RS_EPI_HEAD + (int64_t)RS_EPI_REC * j) * np_pad;
+#pragma unroll
+    for (int c = 0; c < RS_EPI_REC; ++c) rec[c * np_pad] = e.h[4 + c];
+  }
+}
+}  // namespace
+
+hipError_t rs_cluster_episodes_reset(double *acc, int64_t np_pad, const RsEpisodeSpec &spec, hipStream_t stream) {
+  hipLaunchKernelGGL(episodes_reset_kernel, grid1(np_pad), dim3(RS_BLOCK), 0, stream, acc, np_pad,
+                     (int32_t)spec.max_episodes);
+  return hipGetLastError();
+}
+
+hipError_t rs_cluster_outputs_episodes(const void *const src[6], const void *deficit, bool f32, const int32_t *order,
+                                       int64_t npoints, int64_t src_stride, int32_t nrows, int32_t index0,
+                                       int32_t index_step, const RsEpisodeSpec &spec, double *acc, int64_t np_pad,
+                                       hipStream_t stream) {
+  EpisodeArgs a;
+  for (int f = 0; f < 6; ++f) a.src[f] = src[f];
+  a.src[6] = deficit;
+  a.order = order;
+  a.acc = acc;
+  a.npoints = npoints;
+  a.stride = src_stride;
+  a.np_pad = np_pad;
+  a.nrows = nrows;
+  a.index0 = index0;
+  a.index_step = index_step;
+  a.spec = spec;
+  if (f32)
+    hipLaunchKernelGGL(outputs_episodes_kernel<float>, grid1(npoints), dim3(RS_BLOCK), 0, stream, a);
+  else
+    hipLaunchKernelGGL(outputs_episodes_kernel<double>, grid1(npoints), dim3(RS_BLOCK), 0, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t rs_cluster_episodes_finish(double *acc, int64_t npoints, int64_t np_pad, const RsEpisodeSpec &spec,
+                                      hipStream_t stream) {
+  hipLaunchKernelGGL(episodes_finish_kernel, grid1(npoints), dim3(RS_BLOCK), 0, stream, acc, npoints, np_pad, spec);
+  return hipGetLastError();
+}
+
 /* Per-group time series of the output rows (include/roadsurf.h, rs_hip_outputs_groups; the definition is
  * roadsurf_amd/groups.py, reduce_groups): the second sibling, reducing over the slots of a row instead of the rows of
  * a slot.  Many slots fold into one cell acc[row][group][col], so the cells are updated with atomics - every column is

@@ -16,6 +16,8 @@
  *   outputs [row][point] --transpose--> [point][row] --D2H--> caller
  *   kept_rows_kernel           on request (rs_driver_run_kept): the merged series at the kept rows, from the raw
  *                              series and plans that are still there, and deficit_kernel over them and the result
+ *   episodes                   on request (rs_driver_run_episodes): the result block's rows, and that deficit, fed to
+ *                              every point's automaton (rs_cluster.hip), finished, [cols][point] -> [point][cols]
  *
  * JsonSource::interpolate walks the raw and the simulation time axes together; which raw
  * interval a simulation index falls into, and whether it copies or interpolates there,
@@ -1390,6 +1392,8 @@ struct RunPolicy {
   bool want_cluster = false; /* plan order, if the tile has more than one launch (TilePolicy::cluster) */
   bool timing = false;       /* ROADSURF_HIP_DRIVER_TIMING */
   bool kept = false;         /* the call wants kept input rows or the deficit (rs_driver_run_kept): one more [n_out][mp] */
+  int epi_cols = 0;          /* the call wants threshold episodes (rs_driver_run_episodes): columns per point, else 0 */
+  bool epi_deficit = false;  /* ... whose spec uses the deficit: one more [n_out][mp] that holds it */
   int P = 0;                 /* points per tile */
   int TC = 0;                /* indices per launch */
   int nwin = 0;              /* forcing windows of a tile (SW_dir / LW_net only with sky view) */
@@ -1537,6 +1541,7 @@ struct Run : Call {
   const RsDriverGroups *grp;  /* NULL: no group series */
   double *grp_acc;            /* device [rows][ngroups][cols]: this block's cells, merged into by every tile */
   const RsDriverKept *kept;   /* NULL: no kept input rows, no deficit */
+  const RsDriverEpisodes *epi; /* NULL: no threshold episodes */
 };
 
 /* tiles the calling thread's last single-device rs_driver_run stepped (tests: the window budget), and how many
@@ -1569,6 +1574,8 @@ struct Tile : TileHead {
   Dev d_sum, d_sumpt;             /* the summaries [RS_SUM_COLS][mp], and as the caller holds them [m][RS_SUM_COLS] */
   Dev d_gid;                      /* the tile's slice of RsDriverGroups::group */
   Dev d_kept;                     /* one variable's kept rows [n_out][mp], then the deficit (rs_driver_run_kept) */
+  Dev d_epidef;                   /* the kept dew point, then the deficit [n_out][mp], where the episodes read it */
+  Dev d_epi, d_epipt;             /* the episodes [cols][mp], and as the caller holds them [m][cols] */
   RsPointParams pp, pps;          /* in point order, in slot order */
   RsOutputs oo, oc;               /* the result [n_out][mp]; one launch's rows in slot order (rows_c) */
   size_t os = 0;                  /* mp * n_out */
@@ -2003,24 +2010,26 @@ struct Tile : TileHead {
                                   r.grp_acc, stream));
     return 0;
   }
-  /* d_kept [n_out][mp] -> [point][row] -> the tile's rows of a host array [n_points][n_out] */
-  int kept_block_home(double *host) {
-    HOK(transpose((const double *)d_kept.as<double>(), d_outpt.as<double>(), R.n_out, m, mp, R.n_out, stream));
+  /* a block [n_out][mp] -> [point][row] -> the tile's rows of a host array [n_points][n_out] */
+  int kept_block_home(const double *block, double *host) {
+    HOK(transpose(block, d_outpt.as<double>(), R.n_out, m, mp, R.n_out, stream));
     HOK(hipMemcpyAsync(host + (size_t)p0 * R.n_out, d_outpt.p, (size_t)m * R.n_out * sizeof(double), hipMemcpyDeviceToHost,
                        stream));
     return 0;
   }
   /* The inputs at the kept rows and the dew-point deficit (rs_driver_run_kept): the wanted variables one at a time from
    * the tile's raw columns and plans through the one buffer - the dew point first, which the deficit then replaces in
-   * place, reading the final, blanked surface temperature rows of the result block. */
+   * place, reading the final, blanked surface temperature rows of the result block.  Where the episodes read the
+   * deficit (rs_driver_run_episodes) the dew point's turn goes through a buffer of its own, which keeps the deficit
+   * for episodes_home: it is made once, whoever wants it. */
   int kept_home() {
-    const RsDriverKept &q = *r.kept;
-    HOK(d_kept.alloc(os * sizeof(double)));
+    const RsDriverKept *q = r.kept;
+    if (q) HOK(d_kept.alloc(os * sizeof(double)));
+    if (R.epi_deficit) HOK(d_epidef.alloc(os * sizeof(double)));
     KeptRowsArgs ka;
     std::memset(&ka, 0, sizeof(ka));
     ka.S = T.S;
     ka.nfld = 1;
-    ka.out[0] = d_kept.as<double>();
     ka.cpl_hi = R.coupled ? D.cpl_hi.as<int32_t>() : nullptr;
     ka.cplLen = c.cplLen;
     ka.step = R.step;
@@ -2029,23 +2038,48 @@ struct Tile : TileHead {
     const int turn[NFLD] = {R_TDEW, R_TAIR, R_VZ, R_RHZ, R_PREC, R_SW, R_LW, R_SWDIR, R_LWNET, R_OBS};
     for (int k = 0; k < NFLD; ++k) {
       const int f = turn[k];
-      if (!q.merged[f] && !(f == R_TDEW && q.deficit)) continue;
+      double *host = q ? q->merged[f] : nullptr;
+      const bool deficit = f == R_TDEW && ((q && q->deficit) || R.epi_deficit);
+      if (!host && !deficit) continue;
+      double *block = f == R_TDEW && R.epi_deficit ? d_epidef.as<double>() : d_kept.as<double>();
       ka.fld[0] = f;
+      ka.out[0] = block;
       const dim3 g((unsigned)(mp / RS_BLOCK), 1), b(RS_BLOCK);
       if (T.any_pp)
         hipLaunchKernelGGL(kept_rows_kernel<true>, g, b, 0, stream, ka);
       else
         hipLaunchKernelGGL(kept_rows_kernel<false>, g, b, 0, stream, ka);
       HOK(hipGetLastError());
-      if (q.merged[f])
-        if (int rc = kept_block_home(q.merged[f])) return rc;
-      if (f == R_TDEW && q.deficit) {
-        hipLaunchKernelGGL(deficit_kernel, grid1(m), dim3(RS_BLOCK), 0, stream, (const double *)d_out.as<double>(),
-                           d_kept.as<double>(), (int64_t)mp, (int32_t)R.n_out, (int64_t)m);
+      if (host)
+        if (int rc = kept_block_home(block, host)) return rc;
+      if (deficit) {
+        hipLaunchKernelGGL(deficit_kernel, grid1(m), dim3(RS_BLOCK), 0, stream, (const double *)d_out.as<double>(), block,
+                           (int64_t)mp, (int32_t)R.n_out, (int64_t)m);
         HOK(hipGetLastError());
-        if (int rc = kept_block_home(q.deficit)) return rc;
+        if (q && q->deficit)
+          if (int rc = kept_block_home(block, q->deficit)) return rc;
       }
     }
+    return 0;
+  }
+  /* The threshold episodes of the kept rows [first_row, last_row] (rs_driver_run_episodes), from the same final, blanked
+   * result block as the summaries and - where the spec uses it - the deficit kept_home left in d_epidef: reset, one feed
+   * of the rows in order, finish; cols doubles per point come home for them. */
+  int episodes_home() {
+    const RsDriverEpisodes &q = *r.epi;
+    const int cols = R.epi_cols;
+    HOK(d_epi.alloc((size_t)cols * mp * sizeof(double)));
+    HOK(d_epipt.alloc((size_t)m * cols * sizeof(double)));
+    HOK(rs_cluster_episodes_reset(d_epi.as<double>(), mp, q.spec, stream));
+    const void *in[6];
+    for (int f = 0; f < 6; ++f) in[f] = d_out.as<double>() + (size_t)f * os + (size_t)q.first_row * mp;
+    const void *def = R.epi_deficit ? d_epidef.as<double>() + (size_t)q.first_row * mp : nullptr;
+    HOK(rs_cluster_outputs_episodes(in, def, false, nullptr, m, mp, q.last_row - q.first_row + 1,
+                                    q.first_row * R.step + 1, R.step, q.spec, d_epi.as<double>(), mp, stream));
+    HOK(rs_cluster_episodes_finish(d_epi.as<double>(), m, mp, q.spec, stream));
+    HOK(transpose((const double *)d_epi.as<double>(), d_epipt.as<double>(), cols, m, mp, cols, stream));
+    HOK(hipMemcpyAsync(q.episodes + (size_t)p0 * cols, d_epipt.p, (size_t)m * cols * sizeof(double),
+                       hipMemcpyDeviceToHost, stream));
     return 0;
   }
   /* blank what read_input rejected, then [row][point] -> [point][row] -> the caller's arrays */
@@ -2058,8 +2092,10 @@ struct Tile : TileHead {
       if (int rc = summaries_home()) return rc;
     if (r.grp)
       if (int rc = groups_home()) return rc;
-    if (r.kept)
+    if (r.kept || R.epi_deficit)
       if (int rc = kept_home()) return rc;
+    if (r.epi)
+      if (int rc = episodes_home()) return rc;
     double *dst[6] = {r.out->tsurf, r.out->snow, r.out->water, r.out->ice, r.out->deposit, r.out->ice2};
     for (int f = 0; f < 6; ++f) {
       if (!dst[f]) continue;
@@ -2069,7 +2105,7 @@ struct Tile : TileHead {
     }
     HOK(hipStreamSynchronize(stream));
     r.pt.lap(5);
-    for (Dev *d : {&d_phase, &d_outc, &d_pp_s, &d_geo_s, &d_out, &d_outpt, &d_prev, &d_sum, &d_sumpt, &d_gid, &d_kept}) d->release();
+    for (Dev *d : {&d_phase, &d_outc, &d_pp_s, &d_geo_s, &d_out, &d_outpt, &d_prev, &d_sum, &d_sumpt, &d_gid, &d_kept, &d_epidef, &d_epi, &d_epipt}) d->release();
     r.pt.lap(7);
     return 0;
   }
@@ -2116,6 +2152,8 @@ size_t arena_estimate(const RsDriverInput *in, const Common &c, const RunPolicy 
                 + 6 * mpx * 8 + L * 40;                /* previews, hour, sun */
   if (R.skyview) need += 2 * (size_t)360 * mpx * 8 + 8 * mpx * 8;
   if (R.kept) need += mpx * (size_t)R.n_out * 8; /* one variable's kept rows */
+  if (R.epi_deficit) need += mpx * (size_t)R.n_out * 8; /* the deficit the episodes read */
+  need += 2 * mpx * (size_t)R.epi_cols * 8;             /* the episodes, twice */
   need += mpx * ((size_t)2 * RS_NSTATE * 8 + 64) + ((size_t)16 << 20); /* the tile's plan: two state blocks, order rows, sort scratch */
   need += need / 16 + ((size_t)64 << 10) * 64; /* alignment of ~60 pieces, slack */
   return need;
@@ -2159,6 +2197,15 @@ int check_groups(const RsDriverGroups *grp, int n_out) {
     return fail_msg("rs_driver_run_groups: bad spec (ngroups >= 1, nedges <= RS_GRP_MAX_EDGES, edges strictly increasing)", -1);
   if (!grp->group || !grp->series || grp->first_row < 0 || grp->last_row < grp->first_row || grp->last_row >= n_out)
     return fail_msg("rs_driver_run_groups: group and series are required, with 0 <= first_row <= last_row < n_out", -1);
+  return 0;
+}
+
+int check_episodes(const RsDriverEpisodes *epi, int n_out) {
+  if (!epi) return 0;
+  if (rs_cluster_episode_cols(&epi->spec) < 0)
+    return fail_msg("rs_driver_run_episodes: bad spec (use: bits 0..6, at least one; no NaN bound; peak 0..6; min_rows >= 1; max_episodes 1..RS_EPI_MAX)", -1);
+  if (!epi->episodes || epi->first_row < 0 || epi->last_row < epi->first_row || epi->last_row >= n_out)
+    return fail_msg("rs_driver_run_episodes: episodes is required, with 0 <= first_row <= last_row < n_out", -1);
   return 0;
 }
 
@@ -2265,8 +2312,8 @@ int upload_grids(const RsDriverInput *in, const RsGridSource *const *grids, cons
 /* points [pbeg, pend) of the input on one device */
 int driver_run_range(const RsDriverInput *in, const InputSettings *st, const InputParameters *params,
                      LocalParameters *local, const RsDriverOutput *out, const RsDriverSummary *sum,
-                     const RsDriverGroups *grp, const RsDriverKept *kept, int32_t device, int64_t pbeg, int64_t pend,
-                     const GridView *gv = nullptr) {
+                     const RsDriverGroups *grp, const RsDriverKept *kept, const RsDriverEpisodes *epi, int32_t device,
+                     int64_t pbeg, int64_t pend, const GridView *gv = nullptr) {
   Common c;
   RunPolicy R;
   RsConstants consts;
@@ -2275,6 +2322,7 @@ int driver_run_range(const RsDriverInput *in, const InputSettings *st, const Inp
   if (sum && (!sum->summary || sum->first_row < 0 || sum->last_row < sum->first_row || sum->last_row >= R.n_out))
     return fail_msg("rs_driver_run_summary: summary is required, with 0 <= first_row <= last_row < n_out", -1);
   if (int rc = check_groups(grp, R.n_out)) return rc;
+  if (int rc = check_episodes(epi, R.n_out)) return rc;
   if (int rc = check_device(device)) return rc;
   HOK(hipSetDevice(device));
   StreamGuard sg; /* the worker's one stream: uploads, kernels and downloads of its tiles (upload_tile) */
@@ -2289,6 +2337,8 @@ int driver_run_range(const RsDriverInput *in, const InputSettings *st, const Inp
   }
   make_run_policy(st, consts, c, local, pbeg, pend, R);
   R.kept = kept != nullptr;
+  R.epi_cols = epi ? rs_cluster_episode_cols(&epi->spec) : 0;
+  R.epi_deficit = epi && (((epi->spec.use >> 6) & 1) || epi->spec.peak == 6);
   const Call call{in, st, c, consts, device, stream, local, out->status, out->missing_index};
 
   WindowLease arena_lease; /* (declared behind the stream guard: WindowLease::release) */
@@ -2315,7 +2365,7 @@ int driver_run_range(const RsDriverInput *in, const InputSettings *st, const Inp
   const int rows0 = R.cpl_chunked ? std::max(R.TC, std::min(c.L, c.cplLen + 2)) : R.TC;
   Run run{call, params, out, R, pbeg, pend,
           rs_bottom_temperature(params, &consts, in->year[0], in->month[0], in->day[0]), ax, pt, win,
-          R.use_raw ? 0 : (size_t)R.nwin * Ppad * rows0 * sizeof(double), sum, grp, d_grp.as<double>(), kept};
+          R.use_raw ? 0 : (size_t)R.nwin * Ppad * rows0 * sizeof(double), sum, grp, d_grp.as<double>(), kept, epi};
   if (run.win_bytes) HOK(win.acquire(run.win_bytes, device));
   pt.lap(6);
 
@@ -2424,8 +2474,13 @@ int driver_expand(const RsDriverInput *in, const RsGridSource *const *grids, con
 /* rs_driver_run and its kin: one device, or the fan-out */
 int driver_run(const RsDriverInput *in, const RsGridSource *const *grids, const InputSettings *st,
                const InputParameters *params, LocalParameters *local, const RsDriverOutput *out,
-               const RsDriverSummary *sum, const RsDriverGroups *grp, const RsDriverKept *kept, int32_t device) {
+               const RsDriverSummary *sum, const RsDriverGroups *grp, const RsDriverKept *kept,
+               const RsDriverEpisodes *epi, int32_t device) {
   if (!in || in->n_points < 1) return fail_msg("rs_driver_run: bad arguments", -1);
+  if (epi) {
+    if (!out) return fail_msg("rs_driver_run: bad arguments", -1);
+    if (int rc = check_episodes(epi, out->n_out)) return rc;
+  }
   if (kept) { /* nothing wanted: as without */
     bool any = kept->deficit != nullptr;
     for (int f = 0; f < NFLD; ++f) any = any || kept->merged[f];
@@ -2451,7 +2506,8 @@ int driver_run(const RsDriverInput *in, const RsGridSource *const *grids, const 
       gv.dev = G.find(device);
     }
     rsu::g_last_fanout = 1;
-    return driver_run_range(in, st, params, local, out, sum, grp, kept, device, 0, in->n_points, gridded ? &gv : nullptr);
+    return driver_run_range(in, st, params, local, out, sum, grp, kept, epi, device, 0, in->n_points,
+                            gridded ? &gv : nullptr);
   }
   /* four blocks per device.  (Six for batches with local horizons were 4 % faster while the horizon table
    * was transposed on the device, tools/experiments/r4_blocks.sh; with the table left in the caller's layout
@@ -2469,7 +2525,7 @@ int driver_run(const RsDriverInput *in, const RsGridSource *const *grids, const 
   }
   return rsu::fan_out(shards, [&](const rsu::Shard &sh, int) {
     const GridView v{grids, G.find(sh.device)};
-    return driver_run_range(in, st, params, local, out, sum, grp, kept, sh.device, sh.off, sh.off + sh.cnt,
+    return driver_run_range(in, st, params, local, out, sum, grp, kept, epi, sh.device, sh.off, sh.off + sh.cnt,
                             gridded ? &v : nullptr);
   });
 }
@@ -2545,7 +2601,16 @@ int32_t rs_driver_kept_fields(void) { return NFLD; }
 int rs_driver_run_kept(const RsDriverInput *in, const RsGridSource *const *grids, const InputSettings *st,
                        const InputParameters *params, LocalParameters *local, const RsDriverOutput *out,
                        const RsDriverSummary *sum, const RsDriverGroups *grp, const RsDriverKept *kept, int32_t device) {
-  return driver_run(in, grids, st, params, local, out, sum, grp, kept, device);
+  return rs_driver_run_episodes(in, grids, st, params, local, out, sum, grp, kept, nullptr, device);
+}
+
+/* ... and with the threshold episodes of the kept rows: every tile feeds its result block's rows - and the deficit,
+ * where the spec uses it - to its points' automata, every block fills its points' rows of the one host array */
+int rs_driver_run_episodes(const RsDriverInput *in, const RsGridSource *const *grids, const InputSettings *st,
+                           const InputParameters *params, LocalParameters *local, const RsDriverOutput *out,
+                           const RsDriverSummary *sum, const RsDriverGroups *grp, const RsDriverKept *kept,
+                           const RsDriverEpisodes *epi, int32_t device) {
+  return driver_run(in, grids, st, params, local, out, sum, grp, kept, epi, device);
 }
 
 } /* extern "C" */

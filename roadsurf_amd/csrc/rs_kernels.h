@@ -187,6 +187,17 @@ hipError_t rs_cluster_group_reset(double *acc, int64_t acc_rows, const RsGroupSp
 hipError_t rs_cluster_outputs_groups(const void *const src[6], bool f32, const int32_t *order, const int32_t *group,
                                      int64_t npoints, int64_t src_stride, int32_t nrows, const RsGroupSpec &spec,
                                      double *acc_row0, hipStream_t stream);
+/* per-point threshold episodes of output rows (rs_hip_outputs_episodes): acc[cols][np_pad] in point order; src and
+ * order as above, deficit: a seventh window of the same layout and type, or NULL.  rs_cluster_episode_cols checks the
+ * spec (<0: bad) */
+int32_t rs_cluster_episode_cols(const RsEpisodeSpec *spec);
+hipError_t rs_cluster_episodes_reset(double *acc, int64_t np_pad, const RsEpisodeSpec &spec, hipStream_t stream);
+hipError_t rs_cluster_outputs_episodes(const void *const src[6], const void *deficit, bool f32, const int32_t *order,
+                                       int64_t npoints, int64_t src_stride, int32_t nrows, int32_t index0,
+                                       int32_t index_step, const RsEpisodeSpec &spec, double *acc, int64_t np_pad,
+                                       hipStream_t stream);
+hipError_t rs_cluster_episodes_finish(double *acc, int64_t npoints, int64_t np_pad, const RsEpisodeSpec &spec,
+                                      hipStream_t stream);
 /* gridded fields gathered to points (rs_grid.hip, rs_hip_gather_nodes): dst[r][slot] for r < nrows, slot < npoints;
  * node / weight [point][stencil]; order NULL = column s is point s */
 hipError_t rs_grid_gather(const double *src, int32_t nrows, int64_t n_nodes, int64_t src_stride, const int32_t *node,

@@ -328,6 +328,61 @@ class Plan:
         """``acc`` as the numpy array [npoints, RS_SUM_COLS] that summary.reduce_series returns (synchronises)."""
         return acc[:, :self.npoints].T.contiguous().cpu().numpy()
 
+    def _episode_acc(self, spec, acc):
+        if not hasattr(self.L, "rs_hip_episode_cols"):
+            raise RuntimeError("this libroadsurf_hip.so has no threshold episodes (rs_hip_episode_cols)")
+        sp = lib.episode_spec(spec)
+        cols = lib.episode_cols(sp)
+        if acc is None:
+            acc = torch.empty((cols, self.np_pad), dtype=torch.float64, device=self.device)
+        assert acc.dtype == torch.float64 and acc.shape == (cols, self.np_pad) and acc.is_contiguous()
+        return sp, acc
+
+    def episodes_reset(self, spec, acc: torch.Tensor | None = None,
+                       stream: torch.cuda.Stream | None = None) -> torch.Tensor:
+        """The accumulator of no rows into every column of ``acc``, float64 [cols, np_pad] on this device (made here
+        if None) - what ``outputs_episodes`` feeds (rs_hip_episodes_reset); ``spec``: episodes.EpisodeSpec."""
+        sp, acc = self._episode_acc(spec, acc)
+        lib.check(self.L.rs_hip_episodes_reset(self._h, C.byref(sp), C.c_void_p(acc.data_ptr()),
+                                               C.c_void_p(stream.cuda_stream) if stream is not None else None),
+                  "rs_hip_episodes_reset")
+        return acc
+
+    def outputs_episodes(self, out: "OutputWindow", nrows: int, index0: int, index_step: int, spec, acc: torch.Tensor,
+                         deficit: torch.Tensor | None = None, order=None, stream: torch.cuda.Stream | None = None,
+                         row: int = 0) -> None:
+        """Rows ``row .. row + nrows - 1`` of the output window, [row][slot], fed IN ORDER into the per-point
+        episodes ``acc`` [cols, np_pad] in POINT order (rs_hip_outputs_episodes; roadsurf_amd/episodes.py defines
+        the automaton).  The first of these rows is the absolute 1-based time index ``index0``, the next ``index0 +
+        index_step``; ``deficit``: the dew-point deficit of the same rows in the window's layout and type
+        ([rows, t_stride]; its row ``row`` is the first one read), required iff the spec tests it or keeps its peak;
+        ``order`` and ``stream`` as for ``outputs_by_point``."""
+        sp, acc = self._episode_acc(spec, acc)
+        o = out.struct(0)
+        for n in OUT_FIELDS:
+            setattr(o, n, C.c_void_p(out.tensors[n][row].data_ptr()))
+        d = None
+        if deficit is not None:
+            assert deficit.dtype == out.tensors["tsurf"].dtype and deficit.dim() == 2 and deficit.stride(1) == 1
+            assert deficit.stride(0) == out.t_stride and deficit.shape[0] >= row + nrows
+            d = C.c_void_p(deficit[row].data_ptr())
+        lib.check(self.L.rs_hip_outputs_episodes(self._h, C.byref(o), d, int(nrows), int(index0), int(index_step),
+                                                 C.c_void_p(order.data_ptr()) if order is not None else None,
+                                                 C.byref(sp), C.c_void_p(acc.data_ptr()),
+                                                 C.c_void_p(stream.cuda_stream) if stream is not None else None),
+                  "rs_hip_outputs_episodes")
+
+    def episodes_finish(self, spec, acc: torch.Tensor, stream: torch.cuda.Stream | None = None) -> None:
+        """Close every point's open run (rs_hip_episodes_finish): what a consumer reads.  Idempotent."""
+        sp, acc = self._episode_acc(spec, acc)
+        lib.check(self.L.rs_hip_episodes_finish(self._h, C.byref(sp), C.c_void_p(acc.data_ptr()),
+                                                C.c_void_p(stream.cuda_stream) if stream is not None else None),
+                  "rs_hip_episodes_finish")
+
+    def episodes(self, acc: torch.Tensor):
+        """``acc`` as the numpy array [npoints, cols] that episodes.reduce_series returns (synchronises)."""
+        return acc[:, :self.npoints].T.contiguous().cpu().numpy()
+
     def groups_reset(self, nrows: int, spec, acc: torch.Tensor | None = None,
                      stream: torch.cuda.Stream | None = None) -> torch.Tensor:
         """The empty cell into every cell of ``acc``, float64 [nrows, ngroups, cols] on this device (made here if
@@ -454,7 +509,7 @@ class Plan:
 def run_points(forcing: dict, settings: abi.InputSettings, params: abi.InputParameters,
                local, chunk: int = 0, variant: int = 0, device: int = 0,
                lean_if_possible: bool = True, year_month_day=None, history_score: bool | None = None,
-               precision: int = 64, horizon_index=None, summary=None, groups=None):
+               precision: int = 64, horizon_index=None, summary=None, groups=None, episodes=None):
     """Run host arrays ``forcing[name][n, SimLen]`` (numpy, reference layout) through the
     device-resident API and return outputs ``[n, SimLen]`` as numpy.  Test/bench helper:
     transposes with torch on the device, windows of ``chunk`` steps (0 = whole series).
@@ -462,7 +517,10 @@ def run_points(forcing: dict, settings: abi.InputSettings, params: abi.InputPara
     (``Plan.outputs_summary``) and the result has ``summary`` [n, RS_SUM_COLS]; not with coupling,
     whose replays rewrite rows that earlier launches wrote.  ``groups``: (groups.GroupSpec, group ids int32 [n]) -
     every launch's rows are also reduced over the points of each group (``Plan.outputs_groups``) and the result
-    has ``groups`` [SimLen, ngroups, cols], row r being time index r + 1; not with coupling either."""
+    has ``groups`` [SimLen, ngroups, cols], row r being time index r + 1; not with coupling either.
+    ``episodes``: an episodes.EpisodeSpec that does not need the deficit - every launch's rows are also fed to the
+    per-point episodes (``Plan.outputs_episodes``) and the result has ``episodes`` [n, cols], finished; not with
+    coupling either."""
     import numpy as np
 
     require_gpu()
@@ -562,6 +620,9 @@ def run_points(forcing: dict, settings: abi.InputSettings, params: abi.InputPara
         gid = torch.from_numpy(np.ascontiguousarray(groups[1], dtype=np.int32)).to(dev)
         assert gid.shape == (n,)
         gacc = plan.groups_reset(L, groups[0])
+    if episodes is not None and coupled:
+        raise ValueError("run_points: no episodes with coupling")
+    eacc = plan.episodes_reset(episodes) if episodes is not None else None
     plan.init_state(win, pp)
     if coupled and chunk:
         # time-chunked coupling: lock-step chunks up to the last coupling-window end, the replay
@@ -596,6 +657,8 @@ def run_points(forcing: dict, settings: abi.InputSettings, params: abi.InputPara
                 plan.outputs_summary(out, ns, t0, 1, summary, acc, row=t0 - 1)
             if gacc is not None:
                 plan.outputs_groups(out, ns, gid, groups[0], gacc, t0 - 1, row=t0 - 1)
+            if eacc is not None:
+                plan.outputs_episodes(out, ns, t0, 1, episodes, eacc, row=t0 - 1)
             t0 += ns
     plan.sync()
     res = {k: out.tensors[k][:, :n].T.contiguous().double().cpu().numpy() for k in OUT_FIELDS}
@@ -603,6 +666,9 @@ def run_points(forcing: dict, settings: abi.InputSettings, params: abi.InputPara
         res["summary"] = plan.summary(acc)
     if gacc is not None:
         res["groups"] = plan.groups(gacc, groups[0])
+    if eacc is not None:
+        plan.episodes_finish(episodes, eacc)
+        res["episodes"] = plan.episodes(eacc)
     nfail = plan.failed_count()
     plan.close()
     return res, nfail

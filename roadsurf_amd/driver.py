@@ -78,6 +78,11 @@ class RsDriverKept(C.Structure):
     _fields_ = [("merged", abi.c_double_p * len(MERGED_FIELDS)), ("deficit", abi.c_double_p)]
 
 
+class RsDriverEpisodes(C.Structure):
+    _fields_ = [("spec", rslib.RsEpisodeSpec), ("first_row", C.c_int32), ("last_row", C.c_int32),
+                ("episodes", abi.c_double_p)]
+
+
 @dataclasses.dataclass
 class RawSource:
     """One data source: ``fields`` name -> [n_points][n_times] float64 (absent name = variable
@@ -257,6 +262,11 @@ def _bind(L):
         L.rs_driver_run_kept.argtypes = [P(RsDriverInput), P(P(RsGridSource)), P(abi.InputSettings),
                                          P(abi.InputParameters), P(abi.LocalParameters), P(RsDriverOutput),
                                          P(RsDriverSummary), P(RsDriverGroups), P(RsDriverKept), C.c_int32]
+    if hasattr(L, "rs_driver_run_episodes"):
+        L.rs_driver_run_episodes.argtypes = [P(RsDriverInput), P(P(RsGridSource)), P(abi.InputSettings),
+                                             P(abi.InputParameters), P(abi.LocalParameters), P(RsDriverOutput),
+                                             P(RsDriverSummary), P(RsDriverGroups), P(RsDriverKept),
+                                             P(RsDriverEpisodes), C.c_int32]
     return L
 
 
@@ -298,7 +308,7 @@ def run(sources, settings: abi.InputSettings, params: abi.InputParameters, start
         horizons: np.ndarray | None = None, device: int = 0, out: dict | None = None,
         summary=None, summary_rows: tuple[int, int] | None = None, series: bool = True,
         groups=None, group_of=None, group_rows: tuple[int, int] | None = None,
-        kept=(), deficit: bool = False) -> dict:
+        kept=(), deficit: bool = False, episodes=None, episode_rows: tuple[int, int] | None = None) -> dict:
     """read_input + runsimulation + save_output's decimation for all points.  Returns the six
     outputs as [n][n_out] arrays plus ``status``, ``missing_index``, ``local`` and ``step``.
     ``device`` < 0 fans the points out over ROADSURF_HIP_DEVICES; ``out`` = a result dict of an
@@ -319,7 +329,12 @@ def run(sources, settings: abi.InputSettings, params: abi.InputParameters, start
     model saw at the kept rows - ``read_input``'s ``merged`` at every ``step``-th index (roadsurf_amd/kept.py), for
     every point, rejected ones included - made on the device from the raw series (rs_driver_run_kept).
     ``deficit=True``: the result also has ``deficit``, float64 [n][n_out], ``kept.dew_point_deficit`` of the final
-    surface temperature rows and the kept dew point.  Either counts as a summary for ``series=False``."""
+    surface temperature rows and the kept dew point.  Either counts as a summary for ``series=False``.
+    ``episodes`` = an episodes.EpisodeSpec: the result also has ``episodes``, float64 [n][cols], the finished per-point
+    threshold episodes (roadsurf_amd/episodes.py; ``episodes.decode`` reads them) of the kept rows ``episode_rows`` =
+    (first_row, last_row) - default the forecast part, ``forecast_rows`` - reduced on the device
+    (rs_driver_run_episodes); a spec that needs the deficit has it made there whether or not ``deficit`` is asked
+    for.  Counts as a summary for ``series=False``."""
     L = _bind(rslib.load())
     kept = tuple(kept or ())
     for name in kept:
@@ -336,8 +351,8 @@ def run(sources, settings: abi.InputSettings, params: abi.InputParameters, start
     n = inp.n_points
     step, n_out = output_rows(settings)
     larr = _locals(n, local)
-    if not series and summary is None and groups is None and not want_kept:
-        raise ValueError("series=False needs a summary, groups, kept or deficit")
+    if not series and summary is None and groups is None and not want_kept and episodes is None:
+        raise ValueError("series=False needs a summary, groups, kept, deficit or episodes")
     earlier = out if out is not None else {}
 
     def rows(old):  # an [n][n_out] array of the earlier result, or a fresh one
@@ -374,6 +389,14 @@ def run(sources, settings: abi.InputSettings, params: abi.InputParameters, start
         res["groups"] = np.full((max(glast - gfirst + 1, 1), int(groups.ngroups), rslib.group_cols(groups)), np.nan)
         g = RsDriverGroups(rslib.group_spec(groups), gid.ctypes.data_as(abi.c_int32_p), gfirst, glast,
                            res["groups"].ctypes.data_as(abi.c_double_p))
+    kq = e = None
+    if episodes is not None:
+        if not hasattr(L, "rs_driver_run_episodes"):
+            raise RuntimeError("this libroadsurf_hip.so has no threshold episodes (rs_driver_run_episodes)")
+        efirst, elast = forecast_rows(settings, start_time, forecast_time) if episode_rows is None else episode_rows
+        res["episodes"] = np.full((n, rslib.episode_cols(episodes)), np.nan)
+        e = RsDriverEpisodes(rslib.episode_spec(episodes), int(efirst), int(elast),
+                             res["episodes"].ctypes.data_as(abi.c_double_p))
     if want_kept:
         kq = RsDriverKept()
         res["kept"] = {name: rows(earlier.get("kept", {}).get(name)) for name in kept}
@@ -382,6 +405,13 @@ def run(sources, settings: abi.InputSettings, params: abi.InputParameters, start
         if deficit:
             res["deficit"] = rows(earlier.get("deficit"))
             kq.deficit = res["deficit"].ctypes.data_as(abi.c_double_p)
+    if e is not None:
+        rslib.check(L.rs_driver_run_episodes(C.byref(inp), grids, C.byref(settings), C.byref(params), larr, C.byref(out),
+                                             C.byref(q) if q is not None else None,
+                                             C.byref(g) if g is not None else None,
+                                             C.byref(kq) if kq is not None else None, C.byref(e), device),
+                    "rs_driver_run_episodes")
+    elif want_kept:
         rslib.check(L.rs_driver_run_kept(C.byref(inp), grids, C.byref(settings), C.byref(params), larr, C.byref(out),
                                          C.byref(q) if q is not None else None,
                                          C.byref(g) if g is not None else None, C.byref(kq), device), "rs_driver_run_kept")

@@ -102,6 +102,17 @@ class RsGroupSpec(C.Structure):
                 ("edges", C.c_double * RS_GRP_MAX_EDGES)]
 
 
+RS_EPI_VARS = 7
+RS_EPI_MAX = 8
+RS_EPI_HEAD = 10
+RS_EPI_REC = 6
+
+
+class RsEpisodeSpec(C.Structure):
+    _fields_ = [("use", C.c_int32), ("peak", C.c_int32), ("min_rows", C.c_int32), ("max_episodes", C.c_int32),
+                ("above", C.c_double * RS_EPI_VARS), ("below", C.c_double * RS_EPI_VARS)]
+
+
 class RsSynthSpec(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("point_offset", C.c_int64),
                 ("steps_per_knot", C.c_int32), ("start_hour", C.c_int32), ("order", C.c_void_p)]
@@ -116,8 +127,8 @@ EXPORTS = (
     "rs_hip_plan_npoints", "rs_hip_plan_npoints_padded", "rs_hip_plan_state_bytes",
     "rs_hip_init_state", "rs_hip_step", "rs_hip_step_cpl", "rs_hip_cpl_replay", "rs_hip_set_output_by_point", "rs_hip_state_download", "rs_hip_state_upload",
     "rs_hip_failed_count", "rs_hip_clock_probe", "rs_hip_first_failed_index", "rs_hip_set_diagnostics", "rs_hip_diagnostics", "rs_hip_sync", "rs_hip_synth_knots", "rs_hip_expand_forcing", "rs_hip_expand_forcing_ordered", "rs_hip_step_knots", "rs_hip_expand_forcing_on",
-    "rs_hip_plan_order", "rs_hip_recluster", "rs_hip_recluster_forecast", "rs_hip_set_history_score", "rs_hip_coupling_windows_closed", "rs_hip_set_writeback", "rs_hip_plan_order_copy", "rs_hip_outputs_by_point", "rs_hip_summary_cols", "rs_hip_summary_reset", "rs_hip_outputs_summary", "rs_hip_group_cols", "rs_hip_group_path", "rs_hip_group_reset", "rs_hip_outputs_groups", "rs_hip_grid_max_stencil", "rs_hip_gather_nodes", "rs_hip_plan_reset_order", "rs_hip_set_variant", "rs_hip_set_precision", "rs_hip_test_math", "rs_hip_division_mode", "rs_hip_div_mismatch_count", "rs_hip_div_special_count", "rs_hip_div_samples", "rs_hip_timing_reset", "rs_hip_timing_step_ms", "rs_hip_timing_intervals",
-    "rs_host_run_batch", "rs_last_fanout", "rs_driver_run", "rs_driver_run_summary", "rs_driver_run_groups", "rs_driver_run_grid", "rs_driver_expand_grid", "rs_driver_run_kept", "rs_driver_kept_fields", "rs_driver_last_tiles", "rs_driver_last_raw_launches", "rs_hip_bl_stats", "rs_compat_begin", "rs_compat_step", "rs_compat_replay", "rs_compat_failed_index", "rs_compat_last_state", "rs_compat_outputs", "rs_compat_end", "rs_driver_expand", "rs_driver_release_cache", "rs_abi_version", "rs_abi_sizeof", "rs_fortran_sizeof",
+    "rs_hip_plan_order", "rs_hip_recluster", "rs_hip_recluster_forecast", "rs_hip_set_history_score", "rs_hip_coupling_windows_closed", "rs_hip_set_writeback", "rs_hip_plan_order_copy", "rs_hip_outputs_by_point", "rs_hip_summary_cols", "rs_hip_summary_reset", "rs_hip_outputs_summary", "rs_hip_group_cols", "rs_hip_group_path", "rs_hip_group_reset", "rs_hip_outputs_groups", "rs_hip_episode_cols", "rs_hip_episodes_reset", "rs_hip_outputs_episodes", "rs_hip_episodes_finish", "rs_hip_grid_max_stencil", "rs_hip_gather_nodes", "rs_hip_plan_reset_order", "rs_hip_set_variant", "rs_hip_set_precision", "rs_hip_test_math", "rs_hip_division_mode", "rs_hip_div_mismatch_count", "rs_hip_div_special_count", "rs_hip_div_samples", "rs_hip_timing_reset", "rs_hip_timing_step_ms", "rs_hip_timing_intervals",
+    "rs_host_run_batch", "rs_last_fanout", "rs_driver_run", "rs_driver_run_summary", "rs_driver_run_groups", "rs_driver_run_grid", "rs_driver_expand_grid", "rs_driver_run_kept", "rs_driver_kept_fields", "rs_driver_run_episodes", "rs_driver_last_tiles", "rs_driver_last_raw_launches", "rs_hip_bl_stats", "rs_compat_begin", "rs_compat_step", "rs_compat_replay", "rs_compat_failed_index", "rs_compat_last_state", "rs_compat_outputs", "rs_compat_end", "rs_driver_expand", "rs_driver_release_cache", "rs_abi_version", "rs_abi_sizeof", "rs_fortran_sizeof",
 )
 
 _lib = None
@@ -226,6 +237,13 @@ def load() -> C.CDLL:
         L.rs_hip_grid_max_stencil.restype = C.c_int32
         L.rs_hip_gather_nodes.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                           C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_int64, C.c_void_p]
+    if hasattr(L, "rs_hip_episode_cols"):  # ... nor for the threshold episodes
+        L.rs_hip_episode_cols.restype = C.c_int32
+        L.rs_hip_episode_cols.argtypes = [P(RsEpisodeSpec)]
+        L.rs_hip_episodes_reset.argtypes = [C.c_void_p, P(RsEpisodeSpec), C.c_void_p, C.c_void_p]
+        L.rs_hip_outputs_episodes.argtypes = [C.c_void_p, P(RsOutputs), C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                              C.c_void_p, P(RsEpisodeSpec), C.c_void_p, C.c_void_p]
+        L.rs_hip_episodes_finish.argtypes = [C.c_void_p, P(RsEpisodeSpec), C.c_void_p, C.c_void_p]
     L.rs_hip_plan_reset_order.argtypes = [C.c_void_p]
     L.rs_hip_set_variant.argtypes = [C.c_void_p, C.c_int32]
     L.rs_hip_set_precision.argtypes = [C.c_void_p, C.c_int32]
@@ -294,6 +312,31 @@ def group_path(spec) -> str:
     """Which kernel the host chooses for this spec (rs_hip_group_path): "lds" or "global"."""
     group_cols(spec)
     return {1: "lds", 2: "global"}[load().rs_hip_group_path(C.byref(group_spec(spec)))]
+
+
+def episode_spec(spec) -> RsEpisodeSpec:
+    """RsEpisodeSpec of anything with ``use``, ``above[7]``, ``below[7]``, ``peak``, ``min_rows`` and
+    ``max_episodes`` (episodes.EpisodeSpec).  Nothing is judged here: the library refuses a bad spec."""
+    if isinstance(spec, RsEpisodeSpec):
+        return spec
+    above, below = [float(x) for x in spec.above], [float(x) for x in spec.below]
+    if len(above) != RS_EPI_VARS or len(below) != RS_EPI_VARS:
+        raise ValueError("above, below: seven bounds (tsurf, snow, water, ice, deposit, ice2, deficit)")
+    return RsEpisodeSpec(int(spec.use), int(spec.peak), int(spec.min_rows), int(spec.max_episodes),
+                         (C.c_double * RS_EPI_VARS)(*above), (C.c_double * RS_EPI_VARS)(*below))
+
+
+def episode_cols(spec) -> int:
+    """Numbers per point of this spec as the library counts them (rs_hip_episode_cols); raises on a spec it
+    refuses."""
+    L = load()
+    if not hasattr(L, "rs_hip_episode_cols"):
+        raise RuntimeError("this libroadsurf_hip.so has no threshold episodes (rs_hip_episode_cols)")
+    n = L.rs_hip_episode_cols(C.byref(episode_spec(spec)))
+    if n < 0:
+        raise RuntimeError("rs_hip_episode_cols: bad spec (use: bits 0..6, at least one; no NaN bound; peak 0..6; "
+                           "min_rows >= 1; max_episodes 1..RS_EPI_MAX)")
+    return n
 
 
 def last_error() -> str:

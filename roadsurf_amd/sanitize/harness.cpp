@@ -6,9 +6,9 @@
 //            limited to ROADSURF_HIP_COALESCE_MAX callers per batch (set by the test: 5 < threads)
 //   phase 2  threads that come and go (thread-local caches adopted by later threads, rs_host.hip CallerCache)
 //   phase 3  four concurrent runsimulation_batch calls of different sizes (arena / plan bookkeeping)
-//   phase 4  rs_driver_run_kept, which rs_driver_run and its kin are calls of, with and without the summaries from
+//   phase 4  rs_driver_run_episodes, which rs_driver_run and its kin are calls of, with and without the summaries from
 //            three threads (shards, segment table, per-block worker threads, the blocks' merge into the one array of
-//            group series, the blocks' rows of the kept inputs and the deficit)
+//            group series, the blocks' rows of the kept inputs, the deficit and the threshold episodes)
 // usage: harness [threads=64] [points=640]      exit code 0 and "sanitize harness ok" when every call returned
 #include <atomic>
 #include <cmath>
@@ -215,11 +215,39 @@ void driver_call(int n, int hours, bool coupling, bool gridded = false) {
     g_errors++;
     return;
   }
-  const int rc = rs_driver_run_kept(&in, gridded ? grids : nullptr, &s, &p, local.data(), &out, coupling ? &q : nullptr, &g,
-                                    coupling ? &kept : nullptr, -1);
+  /* ... and the coupled and the gridded call for the threshold episodes of the same rows, "Tsurf < 0 and deficit < 0":
+   * the coupled call's tiles make the deficit once for both, the gridded call's for the episodes alone; every block's
+   * worker fills its points' rows of the one host array */
+  RsDriverEpisodes epi;
+  std::memset(&epi, 0, sizeof(epi));
+  epi.spec.use = 1 | (1 << 6);
+  epi.spec.peak = 6;
+  epi.spec.min_rows = 1;
+  epi.spec.max_episodes = 3;
+  for (int k = 0; k < RS_EPI_VARS; ++k) { epi.spec.above[k] = -HUGE_VAL; epi.spec.below[k] = k == 0 || k == 6 ? 0.0 : HUGE_VAL; }
+  const int32_t ecols = rs_hip_episode_cols(&epi.spec);
+  if (ecols != RS_EPI_HEAD + 3 * RS_EPI_REC) {
+    fprintf(stderr, "rs_hip_episode_cols -> %d\n", ecols);
+    g_errors++;
+    return;
+  }
+  std::vector<double> erows((size_t)n * ecols, -1.0);
+  epi.first_row = n_out / 2;
+  epi.last_row = n_out - 1;
+  epi.episodes = erows.data();
+  const int rc = rs_driver_run_episodes(&in, gridded ? grids : nullptr, &s, &p, local.data(), &out, coupling ? &q : nullptr,
+                                        &g, coupling ? &kept : nullptr, coupling || gridded ? &epi : nullptr, -1);
   if (rc != 0) {
     fprintf(stderr, "rs_driver_run(%d points) -> %d: %s\n", n, rc, rs_last_error());
     g_errors++;
+  }
+  if (rc == 0 && (coupling || gridded)) { /* every block wrote its points' rows: nothing of the fill is left */
+    size_t left = 0;
+    for (double v : erows) left += v == -1.0 ? 1 : 0;
+    if (left) {
+      fprintf(stderr, "rs_driver_run_episodes(%d points): %zu of %zu episode columns never written\n", n, left, erows.size());
+      g_errors++;
+    }
   }
 }
 

@@ -504,11 +504,32 @@ int rs_hip_expand_forcing_ordered(RsPlan *plan, const RsSynthSpec *spec,
                                   const double *knots, int32_t k0, int32_t nknots,
                                   const RsForcing *f, int32_t t0, int32_t nsteps);
 
-/* rs_hip_expand_forcing_ordered + rs_hip_step in one launch, without the window: the two-wavefront
- * flavour's ground wave interpolates the forcing of the next index from the knots itself (same arithmetic,
- * same values).  knots in POINT order (spec->order NULL), read through the plan's order row.  LEAN feature
- * set, NLayers = 15, fp64 only (anything else: an error - use the two calls).  What a small shard uses:
- * there the window expansion is the longest link of the chain between two step launches of a plan. */
+/* rs_hip_expand_forcing_ordered + rs_hip_step in one launch, without the window: the ground wave of the
+ * two-wavefront flavour (fp64) or every lane of the two-points-per-lane flavour (an fp32 plan) interpolates the
+ * forcing of the next index from the knots itself (same arithmetic, same values as the expansion calls above).
+ * knots in POINT order (spec->order NULL), read through the plan's order row.  NLayers = 15, no output depth, sky
+ * view or coupling (anything else: an error - use the two calls).  The feature set follows pp as in rs_hip_step:
+ * LEAN without pp->initlen, force_tsurf and relaxation targets, else FULL - an initialization phase, relaxation,
+ * the knots' observation at index 1 (field 7 of knot 0) and CheckValues' test of the dew point.  The LEAN set does
+ * not read the dew point of the knots: it has no test of it, where the reference always has one.
+ * What a knot block may hold.  The knots are the caller's.  rs_hip_expand_forcing and
+ * rs_hip_expand_forcing_ordered give k0 + (r * (k1 - k0)) / steps_per_knot in IEEE double arithmetic bit for
+ * bit for EVERY block, r = 0 .. steps_per_knot - 1, and the knot itself at r = 0: a knot of -0.0 stays -0.0, a
+ * subnormal step is divided exactly, an infinite knot or a step whose multiple overflows gives the infinite value,
+ * a NaN knot gives NaN strictly between the knots around it.  (An fp32 plan rounds k0 and k1 - k0 to single
+ * precision and takes one fused multiply-add with the weight float(r) * float(1 / steps_per_knot); where k1 - k0
+ * is not finite in single precision the value at r = 0 is the knot's.)  PrecPhase (field 8) is the later knot's
+ * between knots and the knot's own at r = 0.
+ * rs_hip_step_knots equals that rule on a DOMAIN only - its interpolation is on the headline's critical path and
+ * divides by the reciprocal of the span without a test: steps_per_knot <= 128, every knot finite, and every
+ * difference of two successive knots of a field either zero or 2^-1015 <= |k1 - k0| < 2^1017.  Inside it the
+ * values are the rule's bit for bit, except that a knot of -0.0 reads +0.0 at its own index (the model's
+ * results do not depend on the sign of a zero input).  Outside it: an infinite or NaN knot makes every value of
+ * the intervals around it NaN, the knot's own index included - a NaN passes every test of CheckValues, so the
+ * point is NOT failed where the reference fails it and writes NaN rows; a smaller difference may be off in the
+ * last bit.  A caller that cannot vouch for its knots uses the two calls.
+ * What a small shard uses: there the window expansion is the longest link of the chain between two step launches
+ * of a plan. */
 int rs_hip_step_knots(RsPlan *plan, const RsSynthSpec *spec, const double *knots, int32_t k0,
                       int32_t nknots, const RsOutputs *o, const RsPointParams *pp, int32_t t0,
                       int32_t nsteps);

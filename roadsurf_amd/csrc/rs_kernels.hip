@@ -1705,7 +1705,10 @@ __device__ __forceinline__ void duo_surface(const MathTab &mt, DuoMailT<FULL ? P
  * v0 + (secs * (k1 - k0)) / span with the difference taken once per knot interval and the division by
  * the uniform span as rs_div_u; PrecPhase from the later knot between knots; the hour of rs_sy_hour.
  * (The LEAN feature set reads neither Tdew nor, after the initialization, TsurfObs.)  Knot columns are
- * per point: gathered through the plan's order row, once per interval. */
+ * per point: gathered through the plan's order row, once per interval.
+ * Unlike expand_kernel this has no IEEE path: it equals the rule only inside knot_interval_fast's domain
+ * (include/roadsurf.h states it for rs_hip_step_knots) - a guard here, one uniform branch per index, cost the
+ * headline 1.9 % (profiles/knot_domain_guard.txt). */
 template <bool FULL>
 struct KnotLerp {
   double v0[FULL ? 7 : 6], dv[FULL ? 7 : 6]; /* tair, vz, rhz, prec, sw, lw [, tdew] */
@@ -2505,16 +2508,31 @@ __global__ void __launch_bounds__(kBlock) synth_knots_kernel(const KnotArgs a) {
   }
 }
 
+/* The knot buffers are the caller's (include/roadsurf.h): a knot may be -0.0, infinite or NaN, and two knots
+ * may differ by anything.  rs_div_u is the IEEE quotient of secs * dv by the span only while that quotient is a
+ * normal number and the numerator finite: for 1 <= secs < span <= 2^7 that is 2^-1015 <= |dv| < 2^1017 (derived
+ * in tests/test_knot_reference.py: below, the quotient is subnormal and an exact tie rounds the other way; above,
+ * secs * dv overflows and the remainder is inf - inf); dv = 0 gives +-0, which leaves every v0 but -0.0 as it
+ * is.  An interval with anything else - a non-finite end makes dv non-finite - and every interval of a span
+ * beyond 2^7 divides the IEEE way and takes the knot itself at secs = 0 (0 * inf is NaN), as raw_resolve decides it
+ * for the raw series: once per interval. */
+__device__ __forceinline__ bool knot_interval_fast(double v0, double dv) {
+  const double ad = __builtin_fabs(dv);
+  return (dv == 0.0 || (ad >= 0x1p-1015 && ad < 0x1p1017)) && !(v0 == 0.0 && __builtin_signbit(v0));
+}
+__device__ __forceinline__ double knot_value_ieee(double v0, double dv, int32_t r, double secs, double span) {
+  return r == 0 ? v0 : v0 + (secs * dv) / span;
+}
+
 /* Knots -> step resolution, the device twin of the reference driver's
  * interpolation (examples/example1/src/JsonSource.cpp:115-172): linear between
  * knots, PrecPhase from the later knot.  One thread = one point over one knot
  * interval (blockIdx.y): the two knot rows are read once, then up to
  * steps_per_knot rows are streamed out, each a coalesced 2-KiB store per block
  * and field. */
-/* TDEW/OBS/DEPTH: which optional streams the window has (compile time, so that the loop over the
- * time indices is ONE basic block: the stores then take the scalar row base + 32-bit lane offset
- * form, LaneOff).  At r = 0 the interpolation adds +-0.0 to the knot value, which returns it
- * unchanged (no knot value is -0.0: rs_synth.h), so the first index needs no case of its own. */
+/* TDEW/OBS/DEPTH: which optional streams the window has (the stores take the scalar row base + 32-bit lane
+ * offset form, LaneOff; the tests inside the loop over the time indices are all uniform).  At r = 0 the interpolation adds +-0.0 to the knot value, which returns it
+ * unchanged unless the knot is -0.0 - one of the intervals that divide the IEEE way (knot_interval_fast). */
 /* (the optional streams - dew point, surface observation, output depth - are there or not for the whole launch:
  * uniform tests of the window's pointers; they were three template parameters, eight instances, until round 6) */
 __global__ void __launch_bounds__(kBlock) expand_kernel(const ExpandArgs a) {
@@ -2534,13 +2552,16 @@ __global__ void __launch_bounds__(kBlock) expand_kernel(const ExpandArgs a) {
   double v0[7], dv[7];
   /* rs_sy_lerp, k0 + (secs * (k1 - k0)) / span, with the difference taken once per interval and
    * the division by the uniform span as rs_div_u (rs_math.hpp: exact for a denominator whose
-   * reciprocal is correctly rounded; the numerator is never -0.0 here because k1 - k0 is not) */
+   * reciprocal is correctly rounded) where every lane's interval allows it (knot_interval_fast) */
+  bool fast = true;
 #pragma unroll
   for (int q = 0; q < 7; ++q) {
     v0[q] = ka[(int64_t)q * a.np_pad];
     const double v1 = need_b ? kb[(int64_t)q * a.np_pad] : v0[q];
     dv[q] = v1 - v0[q];
+    fast = fast && knot_interval_fast(v0[q], dv[q]);
   }
+  const bool ieee = a.spk > 128 || __builtin_amdgcn_ballot_w64(!fast) != 0ull; /* uniform per wavefront */
   const double ts0 = ka[7 * a.np_pad];
   const int32_t ph0 = (int32_t)ka[8 * a.np_pad];
   const int32_t ph1 = need_b ? (int32_t)kb[8 * a.np_pad] : ph0;
@@ -2552,8 +2573,13 @@ __global__ void __launch_bounds__(kBlock) expand_kernel(const ExpandArgs a) {
     const int64_t row = (int64_t)(t - (a.t0 - 1)) * a.f.t_stride + col0;
     const LaneOff L(threadIdx.x);
     double v[7];
+    if (!ieee) { /* uniform, and the same for every index of the interval */
 #pragma unroll
-    for (int q = 0; q < 7; ++q) v[q] = v0[q] + rs_div_u(secs * dv[q], span, a.r_spk);
+      for (int q = 0; q < 7; ++q) v[q] = v0[q] + rs_div_u(secs * dv[q], span, a.r_spk);
+    } else {
+#pragma unroll
+      for (int q = 0; q < 7; ++q) v[q] = knot_value_ieee(v0[q], dv[q], r, secs, span);
+    }
     L.st((double *)a.f.tair + row, v[0]);
     if (TDEW) L.st((double *)a.f.tdew + row, v[1]);
     L.st((double *)a.f.vz + row, v[2]);

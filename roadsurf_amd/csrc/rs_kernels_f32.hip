@@ -270,6 +270,12 @@ __global__ void __launch_bounds__(kBlock) init_kernel_f32(const rs::InitArgs a) 
  * (r = 0) the value is the knot's, rounded. */
 __device__ __forceinline__ float rs32_lerp_weight(int32_t r, double r_spk) { return (float)r * (float)r_spk; }
 __device__ __forceinline__ float rs32_lerp(float v0, float dv, float w) { return __builtin_fmaf(w, dv, v0); }
+/* ... of a caller's knots: a difference that is not finite in single precision (an infinite or NaN end, a step
+ * beyond FLT_MAX) makes 0 * inf = NaN at the knot itself, where the value is the knot's */
+__device__ __forceinline__ bool rs32_finite(float x) { return __builtin_fabsf(x) < __builtin_inff(); }
+__device__ __forceinline__ float rs32_lerp_knot(float v0, float dv, float w, int32_t r) {
+  return (r == 0 && !rs32_finite(dv)) ? v0 : rs32_lerp(v0, dv, w);
+}
 
 /* fp32 twin of expand_kernel (rs_kernels.hip: one basic block per time index, stores with a scalar
  * row base): same knots (fp64), interpolated in single precision (rs32_lerp). */
@@ -308,7 +314,7 @@ __global__ void __launch_bounds__(kBlock) expand_kernel_f32(const rs::ExpandArgs
     float v[7];
     const float w = rs32_lerp_weight(r, a.r_spk);
 #pragma unroll
-    for (int q = 0; q < 7; ++q) v[q] = rs32_lerp((float)v0[q], (float)dv[q], w);
+    for (int q = 0; q < 7; ++q) v[q] = rs32_lerp_knot((float)v0[q], (float)dv[q], w, r);
     st(a.f.tair, v[0]);
     if (TDEW) st(a.f.tdew, v[1]);
     st(a.f.vz, v[2]);

@@ -20,6 +20,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
+import golden_helpers as gh
 import oracle_helpers as oh
 from roadsurf_amd import abi, device, lib
 
@@ -243,24 +244,23 @@ def prepare(case: Case, n: int):
 
 
 def knot_series(n: int, seed: int, wave: int):
-    """The host series of a knot-reading case: the edited knots expanded on the device (rs_hip_expand_forcing, fp64 -
-    what rs_hip_step_knots interpolates value for value) and downloaded."""
-    s = abi.default_settings(SIMLEN); p = abi.default_parameters()
-    plan = device.Plan(n, s, p, 0)
-    A = Arena(plan.device, n, plan.np_pad, None)
-    spec, knots = make_knots(plan, A, seed, wave)
-    t = {k: A.rows(k, None, torch.float64, nrows=SIMLEN)
-         for k in ("tair", "tdew", "vz", "rhz", "prec", "sw", "lw", "tsurfobs")}
-    t["depth"] = None
-    t["precphase"] = A.rows("precphase", None, torch.int32, nrows=SIMLEN)
-    t["hour"] = A.carve("hour", (SIMLEN,), torch.int32, 0)
-    plan.expand(spec, knots, device.ForcingWindow(SIMLEN, A.stride, t), 1, SIMLEN)
-    plan.sync()
+    """The host series of a knot-reading case: the hourly knots of the generator's host twin with the dry spell of
+    dry_spell_knots, expanded by the plain numpy rule (golden_helpers.expand_knots: IEEE float64) - nothing of it
+    comes from a kernel, so the oracle's input is independent of the expansion rs_hip_step_knots does itself."""
+    g = oh.synth_forcing(n, (NKNOTS - 1) * SPK + 1, seed=seed)
+    K = {k: np.ascontiguousarray(g[k][:, ::SPK]) for k in gh.KNOT_FIELDS}
+    K["phase"] = np.ascontiguousarray(g["precphase"][:, ::SPK])
+    K["tsurf0"] = g["tsurfobs"][:, 0].copy()
+    a, b = last_wave(n, wave)
+    K["prec"][a:b, :2] = 0.0
+    K["rhz"][a:b, :2] = np.minimum(K["rhz"][a:b, :2], 60.0)
+    K["prec"][a, 2:] = 1.0
+    K["phase"][a, 2:] = 1
+    e = gh.expand_knots(K, SIMLEN, SPK)
     f = oh.synth_forcing(n, SIMLEN, seed=seed)
-    for k, v in t.items():
-        if v is not None and k != "hour":
-            f[k] = np.ascontiguousarray(v[:, :n].T.cpu().numpy())
-    plan.close()
+    for k in ("tair", "tdew", "vz", "rhz", "prec", "sw", "lw", "tsurfobs", "precphase"):
+        assert e[k].dtype == f[k].dtype and e[k].shape == f[k].shape
+        f[k] = e[k]
     return f
 
 

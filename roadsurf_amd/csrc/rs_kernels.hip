@@ -1477,6 +1477,23 @@ __device__ __forceinline__ void duo_surface(const MathTab &mt, DuoMailT<FULL ? P
    * replay launch that ran ahead of this chunk) */
   if (live && s.failed && !REPLAY) blank_rows(CPL && next_i > t0 ? next_i : t0);
   int32_t score = 0; /* scheduling hint of rs_hip_recluster, as in time_loop */
+  /* The output row, launch-uniform and carried from index to index: what output_row<true> returns for every index
+   * of the launch - the row offset of the next index that is written, which grows by the row stride per written
+   * row, and how many indices lie before it (0 at every index without decimation).  One division per launch, for
+   * an index t0 anywhere between two kept rows.  (The loop launders `ka` at every index: left to output_row it
+   * loads decimate, row0 and the stride and multiplies them out at each.)  OUTIDX: the driver path's instances,
+   * whose rows may go to the points' columns, keep asking output_row - the carried row cost the sky-view one a
+   * vector register. */
+  const int32_t odec = ka->o.decimate > 1 ? ka->o.decimate : 1;
+  const int64_t ostride = ka->o.t_stride;
+  int32_t owait = 0;
+  int64_t orow_next = 0;
+  if (!OUTIDX) {
+    const int32_t r = t0 - 1, m = r % odec;
+    owait = __builtin_amdgcn_readfirstlane(m == 0 ? 0 : odec - m);
+    const int32_t row = __builtin_amdgcn_readfirstlane(r / odec + (m == 0 ? 0 : 1));
+    orow_next = ((int64_t)row - ka->o.row0) * ostride;
+  }
   /* (the forcing windows are the ground wave's to read: this wave gets what a step needs of them
    * through the mailbox, worked out one index ahead - ForcingPrep) */
   for (int32_t kv = 0; kv < nsteps; ++kv) {
@@ -1484,8 +1501,9 @@ __device__ __forceinline__ void duo_surface(const MathTab &mt, DuoMailT<FULL ? P
     const ConstsAS &c = consts_of(ka);
     const int32_t k = __builtin_amdgcn_readfirstlane(kv);
     const int32_t i = t0 + k;
-    int64_t orow = 0;
-    const bool owrite = output_row<true>(ka, i, orow);
+    int64_t orow = orow_next;
+    bool owrite = owait == 0;
+    if (OUTIDX) owrite = output_row<true>(ka, i, orow);
     double t3 = mail.v[k & 1][1][ml]; /* Tmp(3) as the last step left it */
     bool go = true; /* CPL: the lane is due for this index (a failed lane keeps counting: its rows are blanked) */
     if (CPL) {
@@ -1677,6 +1695,14 @@ __device__ __forceinline__ void duo_surface(const MathTab &mt, DuoMailT<FULL ? P
     /* CPL: frozen at the NEXT index? (failed, parked, or not due for it) */
     if (CPL) mail.failed[ml] = (s.failed || parked || (i + 1) != next_i) ? 1u : 0u;
     mail.v[(k & 1) ^ 1][0][ml] = T.get(2);
+    if (!OUTIDX) {
+      if (owrite) {
+        orow_next += ostride;
+        owait = odec - 1;
+      } else {
+        --owait;
+      }
+    }
     duo_meet();
   }
   if (CPL && live) a.state[(int64_t)RS_ST_CPL_RESUME * a.np_pad + p] = (double)next_i;
@@ -1713,16 +1739,43 @@ template <bool FULL>
 struct KnotLerp {
   double v0[FULL ? 7 : 6], dv[FULL ? 7 : 6]; /* tair, vz, rhz, prec, sw, lw [, tdew] */
   int32_t ph0, ph1;
+  /* The time bookkeeping, launch-uniform and carried from index to index (knot_begin, knot_forcing): the knot
+   * interval k and the position r in it of the index knot_forcing makes next - one division per launch, for its
+   * first index; the span, its double and its reciprocal, read once per launch; the hour of the interval and
+   * forcing_prep_tail's verdict on it, made where the interval's knots are loaded.  (The time loop launders its
+   * kernel-argument pointer at every index and the build disables machine LICM: the compiler hoists none of it.) */
+  int32_t spk, k, r, hour, night;
+  double span, r_spk;
 };
+/* The launch's first index i0 (1-based; on a knot or between two): where the carried position starts. */
+template <bool FULL>
+__device__ __forceinline__ void knot_begin(KernArgs ka, KnotLerp<FULL> &K, int32_t i0) {
+  K.spk = ka->spk;
+  { /* the conversion is the vector unit's: its result goes back to scalar registers for the launch */
+    const uint64_t u = (uint64_t)__double_as_longlong((double)K.spk);
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)u), hi = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
+    K.span = __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
+  }
+  K.r_spk = ka->r_spk;
+  const int32_t t = i0 - 1;
+  K.k = __builtin_amdgcn_readfirstlane(t / K.spk);
+  K.r = t - K.k * K.spk;
+  K.hour = 0;
+  K.night = 0;
+}
+/* The forcing of index i = k * spk + r + 1, (k, r) as carried; leaves them at index i + 1.  The calls must follow
+ * knot_begin(i0) with i = i0, i0 + 1, ... without a gap: i itself only tells index 1 (the observation) from the rest. */
 template <bool FULL>
 __device__ __forceinline__ Forcing knot_forcing(KernArgs ka, int64_t col, bool live, KnotLerp<FULL> &K,
                                                 int32_t &kcur, int32_t i) {
-  const int32_t spk = ka->spk;
-  const int32_t t = i - 1;
-  const int32_t k = __builtin_amdgcn_readfirstlane(t / spk);
-  const int32_t r = t - k * spk;
+  const int32_t k = K.k, r = K.r;
   if (k != kcur) { /* uniform: a new knot interval */
     kcur = k;
+    /* rs_sy_hour's expression on the interval, forcing_prep_tail's comparison on the hour: both change here only */
+    const ConstsAS &c = consts_of(ka);
+    K.hour = (k + ka->start_hour) % 24;
+    const bool night = ((double)K.hour >= c.NightOn) || ((double)K.hour <= c.NightOff);
+    K.night = __builtin_amdgcn_readfirstlane(night ? 1 : 0);
     const int fld[7] = {0, 2, 3, 4, 5, 6, 1};
     const int64_t np = ka->np_pad;
     const double *ka_ = ka->knots + ((int64_t)(k - ka->knot_k0) * RS_KNOT_FIELDS) * np + col;
@@ -1737,23 +1790,31 @@ __device__ __forceinline__ Forcing knot_forcing(KernArgs ka, int64_t col, bool l
     K.ph0 = live ? (int32_t)ka_[8 * np] : 0;
     K.ph1 = (live && has_b) ? (int32_t)kb_[8 * np] : K.ph0;
   }
-  const double secs = (double)r, span = (double)spk;
+  /* FULL: beside seven knot pairs and thirteen layers the span, its double and its reciprocal cost the instance two
+   * vector registers when they stay resident (120 -> 122): that feature set reads them again at every index */
+  const int32_t spk = FULL ? ka->spk : K.spk;
+  const double secs = (double)r, span = FULL ? (double)spk : K.span, r_spk = FULL ? ka->r_spk : K.r_spk;
   Forcing f;
-  f.tair = K.v0[0] + rs_div_u(secs * K.dv[0], span, ka->r_spk);
-  f.vz = K.v0[1] + rs_div_u(secs * K.dv[1], span, ka->r_spk);
-  f.rhz = K.v0[2] + rs_div_u(secs * K.dv[2], span, ka->r_spk);
-  f.prec = K.v0[3] + rs_div_u(secs * K.dv[3], span, ka->r_spk);
-  f.sw = K.v0[4] + rs_div_u(secs * K.dv[4], span, ka->r_spk);
-  f.lw = K.v0[5] + rs_div_u(secs * K.dv[5], span, ka->r_spk);
+  f.tair = K.v0[0] + rs_div_u(secs * K.dv[0], span, r_spk);
+  f.vz = K.v0[1] + rs_div_u(secs * K.dv[1], span, r_spk);
+  f.rhz = K.v0[2] + rs_div_u(secs * K.dv[2], span, r_spk);
+  f.prec = K.v0[3] + rs_div_u(secs * K.dv[3], span, r_spk);
+  f.sw = K.v0[4] + rs_div_u(secs * K.dv[4], span, r_spk);
+  f.lw = K.v0[5] + rs_div_u(secs * K.dv[5], span, r_spk);
   f.phase = (r == 0) ? K.ph0 : K.ph1;
-  f.hour = rs_sy_hour(i, spk, ka->start_hour);
+  f.hour = K.hour;
   f.tdew = 0.0;
   f.tsurfobs = R4(-9999.9);
   if (FULL) { /* expand_kernel<TDEW, OBS>: the dew point like the others, the observation at index 1 only */
-    f.tdew = K.v0[6] + rs_div_u(secs * K.dv[6], span, ka->r_spk);
-    if (t == 0 && live) f.tsurfobs = (ka->knots + ((int64_t)(k - ka->knot_k0) * RS_KNOT_FIELDS + 7) * ka->np_pad)[col];
+    f.tdew = K.v0[6] + rs_div_u(secs * K.dv[6], span, r_spk);
+    if (i == 1 && live) f.tsurfobs = (ka->knots + ((int64_t)(k - ka->knot_k0) * RS_KNOT_FIELDS + 7) * ka->np_pad)[col];
   }
   f.depth = R4(-9999.9);
+  K.r = r + 1;
+  if (K.r == spk) {
+    K.r = 0;
+    K.k = k + 1;
+  }
   return f;
 }
 
@@ -2014,6 +2075,9 @@ __device__ __forceinline__ void duo_ground(const MathTab &mt, DuoMailT<FULL ? PR
   static_assert(!RAW || FULL, "the driver's series carry the FULL feature set");
   static_assert(!SKYG || RAW, "a sky wave exists only where the forcing is made from the raw series");
   static_assert(!REPLAY || (CPL && RAW && !SKYG), "replay rounds in this flavour: raw series, no sky view");
+  /* knot_forcing walks the launch's indices one by one from knot_begin's: it carries its position and takes no index
+   * to look one up - a flavour that rewinds or skips indices cannot read knots this way */
+  static_assert(!KNOTS || (!CPL && !REPLAY), "the knot-reading source steps every index of the launch in order");
   KernArgs ka = kernargs();
   const uint32_t ml = threadIdx.x & 63u; /* lane of the mailbox; `lane` + row0 = the point (REPLAY: through the list) */
   const int64_t listed = REPLAY ? (int64_t)blockIdx.x * 64 + ml : 0;
@@ -2065,9 +2129,11 @@ __device__ __forceinline__ void duo_ground(const MathTab &mt, DuoMailT<FULL ? PR
   bool anchor_due = false;
   double anchor_t = 0, anchor_v = 0, anchor_r = 0;
   double obs_cur = R4(-9999.9); /* the observation forced on Tmp(1:2) at the current index, or missing */
+  KnotLerp<FULL> klerp; /* KNOTS: the knots of the current interval, where the next index lies in it, its day/night verdict */
+  klerp.night = 0;
   /* the forcing's share of index `in`, from the forcing in `f` */
   auto prep = [&](const ConstsAS &c, const Forcing &f, int32_t in, double &obs) -> ForcingPrep {
-    if (!FULL) return forcing_prep(c, mt, f, in, in < c.SimLen);
+    if (!FULL) return forcing_prep<KNOTS>(c, mt, f, in, in < c.SimLen, klerp.night != 0);
     bool bad;
     const bool has_tdew = RAW ? true : KNOTS ? (ka->knots_tdew & 2) != 0 : ka->f.tdew != nullptr;
     double vz = forcing_prep_head(c, f, in, in < c.SimLen, has_tdew, bad);
@@ -2103,7 +2169,7 @@ __device__ __forceinline__ void duo_ground(const MathTab &mt, DuoMailT<FULL ? PR
         }
       }
     }
-    ForcingPrep q = forcing_prep_tail(c, mt, f, tair, vz, rhz, bad);
+    ForcingPrep q = forcing_prep_tail<KNOTS>(c, mt, f, tair, vz, rhz, bad, klerp.night != 0);
     q.tsurfobs = obs;
     if (REPLAY && live && in == cpl_cs && in < c.SimLen) {
       /* the rewind: CheckValues has just seen the index behind the window end (0-based: cpl_ce) - its forcing
@@ -2124,7 +2190,6 @@ __device__ __forceinline__ void duo_ground(const MathTab &mt, DuoMailT<FULL ? PR
   /* the forcing of the launch's first index, prepared before the first meeting (a lane beyond npoints
    * reads nothing: the windows need only span npoints columns) */
   Forcing nxt = Forcing();
-  KnotLerp<FULL> klerp;
   int32_t kcur = -1;
   const int64_t kcol = (KNOTS && live) ? (ka->knot_gather ? (int64_t)ka->knot_gather[p] : p) : 0;
   /* RAW: the point's column of the raw series, read_input's verdict on it, the segment of the first index */
@@ -2143,8 +2208,10 @@ __device__ __forceinline__ void duo_ground(const MathTab &mt, DuoMailT<FULL ? PR
   }
   {
     const ConstsAS &c0 = consts_of(ka);
-    if (KNOTS) nxt = knot_forcing<FULL>(ka, kcol, live, klerp, kcur, t0);
-    else if (RAW) nxt = raw_forcing<FSET>(ka, rcol, live, rejected, rlerp, t0, obs_wanted(c0, t0));
+    if (KNOTS) {
+      knot_begin<FULL>(ka, klerp, t0);
+      nxt = knot_forcing<FULL>(ka, kcol, live, klerp, kcur, t0);
+    } else if (RAW) nxt = raw_forcing<FSET>(ka, rcol, live, rejected, rlerp, t0, obs_wanted(c0, t0));
     else if (live) nxt = load_forcing<FULL, true>(ka, row0, lane, 0);
     duo_put_prep<FULL, SKYG>(mail, 0, ml, prep(c0, nxt, t0, obs_cur));
   }

@@ -718,6 +718,17 @@ __device__ __forceinline__ void x2d_ground(X2Mail &mail, const rs::StepArgs &a) 
   i2 kph0 = i2{0, 0}, kph1 = i2{0, 0};
   int32_t kcur = -1;
   bool knots_safe = false; /* uniform: no index of the current knot interval can fail CheckValues' forcing tests */
+  /* X2_KNOTS: the time bookkeeping, launch-uniform and carried from index to index as the fp64 flavour carries it
+   * (rs_kernels.hip KnotLerp): the knot interval and the position in it of the index prep() makes next - one division
+   * per launch, for its first index -, the span read once, the hour of the interval and the day/night verdict on it,
+   * made where the interval's knots are loaded */
+  const int32_t kspk = SRC == X2_KNOTS ? ka->spk : 1;
+  const double kr_spk = SRC == X2_KNOTS ? ka->r_spk : 0.0; /* RN(1 / spk), read once like the span */
+  int32_t kk_c = 0, kr_c = 0, khour = 0, knight = 0;
+  if (SRC == X2_KNOTS) {
+    kk_c = __builtin_amdgcn_readfirstlane((t0 - 1) / kspk);
+    kr_c = (t0 - 1) - kk_c * kspk;
+  }
   /* FULL: as the fp64 flavours set a point up (time_loop, duo_ground) */
   i2 initlen = i2{0, 0};
   b2 relax = b2{false, false};
@@ -776,10 +787,7 @@ __device__ __forceinline__ void x2d_ground(X2Mail &mail, const rs::StepArgs &a) 
     bool hour_per_point = false;
     bool has_tdew = false;
     if (SRC == X2_KNOTS) {
-      const int32_t spk = ka->spk;
-      const int32_t t = in - 1;
-      const int32_t kk = __builtin_amdgcn_readfirstlane(t / spk);
-      const int32_t rr = t - kk * spk;
+      const int32_t kk = kk_c, rr = kr_c; /* in = kk * spk + rr + 1 */
       if (kk != kcur) { /* uniform: a new knot interval - expand_kernel_f32's loads and differences */
         kcur = kk;
         const int fld[7] = {0, 2, 3, 4, 5, 6, 1};
@@ -815,19 +823,27 @@ __device__ __forceinline__ void x2d_ground(X2Mail &mail, const rs::StepArgs &a) 
           };
           knots_safe = wave_all2(b2{inside(0), inside(1)});
         }
+        /* rs_sy_hour's expression on the interval, the comparison of SetDayDependendVariables below on the hour */
+        khour = (kk + ka->start_hour) % 24;
+        knight = __builtin_amdgcn_readfirstlane((((float)khour >= c.NightOn) || ((float)khour <= c.NightOff)) ? 1 : 0);
       }
-      const f2 w = S2(rs32_lerp_weight(rr, ka->r_spk));
+      const f2 w = S2(rs32_lerp_weight(rr, kr_spk));
       tair = fma2(w, kdv[0], kv0[0]); vz = fma2(w, kdv[1], kv0[1]); rhz = fma2(w, kdv[2], kv0[2]);
       prec = fma2(w, kdv[3], kv0[3]); sw = fma2(w, kdv[4], kv0[4]); lw = fma2(w, kdv[5], kv0[5]);
       phase = (rr == 0) ? kph0 : kph1;
-      hour_u = rs_sy_hour(in, spk, ka->start_hour);
+      hour_u = khour;
       if (FULL) { /* expand_kernel_f32: the dew point like the others, the observation at index 1 only */
         tdew = fma2(w, kdv[NK - 1], kv0[NK - 1]);
         has_tdew = (ka->knots_tdew & 2) != 0;
-        if (t == 0) {
+        if (in == 1) {
           const double *k7 = ka->knots + ((int64_t)(kk - ka->knot_k0) * RS_KNOT_FIELDS + 7) * np;
           tsobs = f2{(float)k7[kcolx], (float)k7[kcoly]};
         }
+      }
+      kr_c = rr + 1;
+      if (kr_c == kspk) {
+        kr_c = 0;
+        kk_c = kk + 1;
       }
     } else {
       const int64_t row = (int64_t)(in - t0) * ka->f.t_stride + p;
@@ -947,7 +963,7 @@ __device__ __forceinline__ void x2d_ground(X2Mail &mail, const rs::StepArgs &a) 
         flx |= night.x ? 2u : 0u;
         fly |= night.y ? 2u : 0u;
       } else {
-        const bool night = ((float)hour_u >= c.NightOn) || ((float)hour_u <= c.NightOff);
+        const bool night = SRC == X2_KNOTS ? knight != 0 : ((float)hour_u >= c.NightOn) || ((float)hour_u <= c.NightOff);
         calm = S2(night ? calmN : calmD);
         flx |= night ? 2u : 0u;
         fly |= night ? 2u : 0u;
@@ -1062,6 +1078,20 @@ __device__ __forceinline__ void x2d_surface(X2Mail &mail, const rs::StepArgs &a)
   const int32_t nsteps = ka->nsteps, t0 = ka->t0;
   i2 score = i2{0, 0}, regime = i2{0, 0}, last_trips = i2{0, 0};
   const bool ovec = !(ka->o.t_stride & 1) && liveY;
+  /* The output row, launch-uniform and carried from index to index (as rs_kernels.hip duo_surface carries it): the
+   * row offset of the next index that is written, which grows by the row stride per written row, and how many indices
+   * lie before it (0 at every index without decimation) - one division per launch, for a t0 anywhere between two kept
+   * rows */
+  const int32_t odec = ka->o.decimate > 1 ? ka->o.decimate : 1;
+  const int64_t ostride = ka->o.t_stride;
+  int32_t owait;
+  int64_t orow_next;
+  {
+    const int32_t r = t0 - 1, m = r % odec;
+    owait = __builtin_amdgcn_readfirstlane(m == 0 ? 0 : odec - m);
+    const int32_t row = __builtin_amdgcn_readfirstlane(r / odec + (m == 0 ? 0 : 1));
+    orow_next = ((int64_t)row - ka->o.row0) * ostride;
+  }
   lds_st2(mail.v[0][0], lane, T2);
   x2_meet();
   for (int32_t kv = 0; kv < nsteps; ++kv) {
@@ -1069,14 +1099,8 @@ __device__ __forceinline__ void x2d_surface(X2Mail &mail, const rs::StepArgs &a)
     const ConstsAS &c = consts_of(ka);
     const int32_t k = __builtin_amdgcn_readfirstlane(kv);
     const int32_t i = t0 + k;
-    int64_t r = (int64_t)(i - 1);
-    const int32_t dec = ka->o.decimate;
-    bool write = true;
-    if (dec > 1) {
-      write = (r % dec == 0);
-      r /= dec;
-    }
-    const int64_t orow = (r - ka->o.row0) * ka->o.t_stride + p;
+    const bool write = owait == 0;
+    const int64_t orow = orow_next + p;
     auto out2 = [&](void *base, f2 v) {
       float *q = reinterpret_cast<float *>(base) + orow;
       if (ovec) {
@@ -1297,6 +1321,10 @@ __device__ __forceinline__ void x2d_surface(X2Mail &mail, const rs::StepArgs &a)
         out2(ka->o.tsurf, s.tsurf); out2(ka->o.snow, s.snow); out2(ka->o.water, s.wat);
         out2(ka->o.ice, s.ice); out2(ka->o.deposit, s.dep); out2(ka->o.ice2, s.ice2);
       }
+      orow_next += ostride;
+      owait = odec - 1;
+    } else {
+      --owait;
     }
     lds_st2(mail.v[(k & 1) ^ 1][0], lane, T2);
     x2_meet();

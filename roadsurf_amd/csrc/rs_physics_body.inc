@@ -732,9 +732,13 @@ __device__ __forceinline__ RS_REAL forcing_prep_head(const RS_CONSTS &c, const F
 }
 
 /* Second half, from the air temperature, wind speed and humidity the step will use (the FULL feature
- * set relaxes them between the two halves, src/Relaxation.f90) */
+ * set relaxes them between the two halves, src/Relaxation.f90).  NIGHT_U: the caller hands over the day/night
+ * verdict in night_u - the comparison below on the same hour, made once for a run of indices that share the
+ * hour (the knot-reading source: one hour for all points, one per knot interval) - and f.hour is not read. */
+template <bool NIGHT_U = false>
 __device__ __forceinline__ ForcingPrep forcing_prep_tail(const RS_CONSTS &c, const MathTab &mt, const Forcing &f,
-                                                         RS_REAL tair, RS_REAL vz, RS_REAL rhz, bool bad) {
+                                                         RS_REAL tair, RS_REAL vz, RS_REAL rhz, bool bad,
+                                                         bool night_u = false) {
   ForcingPrep q;
   RS_REAL prec_ts = RS_DIVC(f.prec, (RS_REAL)3600.0, r_3600) * c.DTSecs;
   q.bad = bad;
@@ -759,7 +763,7 @@ __device__ __forceinline__ ForcingPrep forcing_prep_tail(const RS_CONSTS &c, con
     q.snow = z.snow;
   }
   const RS_REAL calmN = c.CalmLimNgt, calmD = c.CalmLimDay, fricN = c.TrfFricNgt, fricD = c.TrFfricDay;
-  const bool night = ((RS_REAL)f.hour >= c.NightOn) || ((RS_REAL)f.hour <= c.NightOff);
+  const bool night = NIGHT_U ? night_u : ((RS_REAL)f.hour >= c.NightOn) || ((RS_REAL)f.hour <= c.NightOff);
   const RS_REAL calm = night ? calmN : calmD;
   q.trffric = night ? fricN : fricD;
   q.night = night;
@@ -787,11 +791,12 @@ __device__ __forceinline__ ForcingPrep forcing_prep_tail(const RS_CONSTS &c, con
   return q;
 }
 
+template <bool NIGHT_U = false>
 __device__ __forceinline__ ForcingPrep forcing_prep(const RS_CONSTS &c, const MathTab &mt, const Forcing &f,
-                                                    int32_t i, bool checked) {
+                                                    int32_t i, bool checked, bool night_u = false) {
   bool bad;
   const RS_REAL vz = forcing_prep_head(c, f, i, checked, false, bad);
-  return forcing_prep_tail(c, mt, f, f.tair, vz, f.rhz, bad);
+  return forcing_prep_tail<NIGHT_U>(c, mt, f, f.tair, vz, f.rhz, bad, night_u);
 }
 
 /* model_step_fluxes from a ForcingPrep: the storages take the precipitation, the boundary-layer loop

@@ -76,6 +76,7 @@ def valu_class(op):
 REGIONS = [
     ("boundary_layer_ieee", None, None, "guard (IEEE redo, out of line)"),
     ("knot_forcing", None, None, "knot interpolation"),
+    ("knot_begin", None, None, "knot interpolation"),
     ("rs_sy_hour", None, None, "knot interpolation"),
     ("precipitation_to_storage", None, None, "precipitation (CalcPrecType)"),
     ("forcing_prep_head", None, None, "ForcingPrep"),
@@ -139,7 +140,8 @@ WEIGHTS = {
     "storages": 1.0 - 0.615,            # the bare-road shortcut takes 61.5 % of the wave-steps
     "albedo": 1.0 - 0.615,
 }
-RELOAD = ("ka_[", "kb_[", "K.dv[q]", "K.ph0 =", "K.ph1 =", "has_b", "kcur = k")  # knot_forcing's once-per-interval block
+RELOAD = ("ka_[", "kb_[", "K.dv[q]", "K.ph0 =", "K.ph1 =", "has_b", "kcur = k",
+          "K.hour", "K.night =")  # knot_forcing's once-per-interval block (any line that names K.hour: its per-index use is a scalar copy)
 SNOW, ICE = 0.06, 0.10  # of the wave-steps carry snow / ice (storages' sub-blocks, by their source text)
 
 

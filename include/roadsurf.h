@@ -355,7 +355,10 @@ int rs_hip_device_count(void);
 
 /* Create a plan for `npoints` points on HIP device `device`; uploads constants,
  * allocates the carried-state block.  `stream` is a hipStream_t (0 = default),
- * all rs_hip_* work of this plan is enqueued on it. */
+ * all rs_hip_* work of this plan is enqueued on it.
+ * Domain: a set of constants outside the operand range of the kernels' division sequences is refused with the
+ * name of the offending quantity (NULL, rs_last_error).  Making the plan an fp32 one narrows the domain once
+ * more - MaxSnowmms >= 0 - and is refused there: rs_hip_set_precision below. */
 RsPlan *rs_hip_plan_create(int32_t device, int64_t npoints,
                            const RsConstants *consts, void *stream);
 void rs_hip_plan_destroy(RsPlan *plan);
@@ -561,7 +564,13 @@ int rs_hip_test_math(RsPlan *plan, int32_t fn, int64_t n, const double *x, doubl
  * [t][p] layout, depth, sw_dir and lw_net included (precphase/hour stay int32; tbottom, the sun
  * table and the per-point members of RsPointParams - relaxation targets, coupling observation,
  * sky view, latitude / longitude terms, horizons - stay double: the sun's position is worked out
- * in fp64 in either flavour), and the state block holds floats.  Set before rs_hip_init_state. */
+ * in fp64 in either flavour), and the state block holds floats.  Set before rs_hip_init_state.
+ * Domain of 32: MaxSnowmms >= 0, else the call is refused.  Under a negative limit SnowStorage lifts every
+ * snow-free road to -MaxSnowmms / 2 at every index, and the next index melts exactly that amount: what is left
+ * is a rounding residual whose sign decides whether snow is worn into ice.  Single precision takes the other
+ * sign than the reference, in either fp32 kernel (ice grows by 4e-4 mm an index where the reference keeps none;
+ * tests/test_hip_param_sets.py), so no tolerance against fp64 holds there.  The other upper limits and
+ * MinPrecmm may be negative. */
 int rs_hip_set_precision(RsPlan *plan, int32_t bits);
 
 /* How this build divides: 0 = compiler's IEEE expansion everywhere (-DRS_IEEE_DIV),

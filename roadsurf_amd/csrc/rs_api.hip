@@ -635,6 +635,9 @@ size_t rs_hip_plan_state_bytes(const RsPlan *pl) {
 
 int rs_hip_set_precision(RsPlan *pl, int32_t bits) {
   if (!pl || (bits != 32 && bits != 64)) return set_err("rs_hip_set_precision: bits must be 32 or 64");
+  if (bits == 32 && pl->c.MaxSnowmms < 0.0) /* include/roadsurf.h: the domain of the fp32 flavour */
+    return set_err("rs_hip_set_precision: the fp32 flavour needs MaxSnowmms >= 0 (a negative limit makes every melt a "
+                   "rounding residual that single precision resolves the other way)");
   HIP_OK(hipSetDevice(pl->device));
   if (bits == 32) {
     if (!pl->consts32_dev) HIP_OK(plan_malloc(pl, &pl->consts32_dev, rs32_constants_bytes()));

@@ -474,6 +474,38 @@ int rs_hip_plan_order_copy(RsPlan *pl, int32_t *dst) {
   return 0;
 }
 
+/* What the consumers of output rows resolve before their launch (rs_hip_outputs_*, rs_hip_gather_nodes). */
+struct RowsOn {
+  const void *in[6]; /* the six streams of the source rows (rows_prologue) */
+  const int32_t *order;
+  hipStream_t stream;
+};
+/* the stream half (the _reset / _finish calls take this alone): a stream of the caller's, else the plan's */
+static hipStream_t stream_of(const RsPlan *pl, void *stream) { return stream ? (hipStream_t)stream : pl->stream; }
+
+/* the order and stream half: a kept order row, else the plan's current one - which the next re-sort replaces, so on a
+ * stream of the caller's the row must be a kept one */
+static int rows_order(RsPlan *pl, const int32_t *order, void *stream, const char *who, RowsOn &on) {
+  if (!order && stream) return set_err("%s: on a stream of the caller's the order row must be a kept one", who);
+  if (!order && !rs_hip_plan_order(pl)) return -1;
+  HIP_OK(hipSetDevice(pl->device));
+  on.order = order ? order : pl->order;
+  on.stream = stream_of(pl, stream);
+  return 0;
+}
+
+/* ... and the source rows before it: all six streams, rows of at least the plan's points */
+static int rows_prologue(RsPlan *pl, const RsOutputs *src, const int32_t *order, void *stream, const char *who,
+                         RowsOn &on) {
+  const void *in[6] = {src->tsurf, src->snow, src->water, src->ice, src->deposit, src->ice2};
+  for (int f = 0; f < 6; ++f) {
+    if (!in[f]) return set_err("%s: all six streams are required", who);
+    on.in[f] = in[f];
+  }
+  if (src->t_stride < pl->npoints) return set_err("%s: t_stride below the plan's points", who);
+  return rows_order(pl, order, stream, who, on);
+}
+
 int rs_hip_outputs_by_point(RsPlan *pl, const RsOutputs *src, int32_t nrows, const int32_t *order,
                             double *const *dst, int64_t dst_rows, int64_t dst_row0, void *stream) {
   if (!pl || !src || !dst || nrows < 1 || dst_rows < 1 || dst_row0 < 0 || dst_row0 + nrows > dst_rows)
@@ -485,12 +517,9 @@ int rs_hip_outputs_by_point(RsPlan *pl, const RsOutputs *src, int32_t nrows, con
     if (!in[f] || !dst[f]) return set_err("rs_hip_outputs_by_point: all six streams are required on both sides");
     out[f] = dst[f];
   }
-  if (src->t_stride < pl->npoints) return set_err("rs_hip_outputs_by_point: t_stride below the plan's points");
-  if (!order && stream) return set_err("rs_hip_outputs_by_point: on a stream of the caller's the order row must be a kept one");
-  if (!order && !rs_hip_plan_order(pl)) return -1;
-  HIP_OK(hipSetDevice(pl->device));
-  HIP_OK(rs_cluster_outputs_by_point(in, out, order ? order : pl->order, pl->npoints, src->t_stride, nrows, dst_rows,
-                                     dst_row0, stream ? (hipStream_t)stream : pl->stream));
+  RowsOn on; /* (both sides are tested above: the prologue's own test of the source never fails here) */
+  if (rows_prologue(pl, src, order, stream, "rs_hip_outputs_by_point", on)) return -1;
+  HIP_OK(rs_cluster_outputs_by_point(in, out, on.order, pl->npoints, src->t_stride, nrows, dst_rows, dst_row0, on.stream));
   return 0;
 }
 
@@ -499,7 +528,7 @@ int32_t rs_hip_summary_cols(void) { return RS_SUM_COLS; }
 int rs_hip_summary_reset(RsPlan *pl, double *acc, void *stream) {
   if (!pl || !acc) return set_err("rs_hip_summary_reset: bad arguments");
   HIP_OK(hipSetDevice(pl->device));
-  HIP_OK(rs_cluster_summary_reset(acc, pl->np_pad, stream ? (hipStream_t)stream : pl->stream));
+  HIP_OK(rs_cluster_summary_reset(acc, pl->np_pad, stream_of(pl, stream)));
   return 0;
 }
 
@@ -508,15 +537,10 @@ int rs_hip_outputs_summary(RsPlan *pl, const RsOutputs *src, int32_t nrows, int3
   if (!pl || !src || !spec || !acc || nrows < 1 || index0 < 1 || index_step < 1 ||
       (int64_t)index0 + (int64_t)(nrows - 1) * index_step > INT32_MAX)
     return set_err("rs_hip_outputs_summary: bad arguments (nrows >= 1 rows at the time indices index0 + r*index_step, index0 >= 1, index_step >= 1)");
-  const void *in[6] = {src->tsurf, src->snow, src->water, src->ice, src->deposit, src->ice2};
-  for (int f = 0; f < 6; ++f)
-    if (!in[f]) return set_err("rs_hip_outputs_summary: all six streams are required");
-  if (src->t_stride < pl->npoints) return set_err("rs_hip_outputs_summary: t_stride below the plan's points");
-  if (!order && stream) return set_err("rs_hip_outputs_summary: on a stream of the caller's the order row must be a kept one");
-  if (!order && !rs_hip_plan_order(pl)) return -1;
-  HIP_OK(hipSetDevice(pl->device));
-  HIP_OK(rs_cluster_outputs_summary(in, pl->f32, order ? order : pl->order, pl->npoints, src->t_stride, nrows, index0,
-                                    index_step, *spec, acc, pl->np_pad, stream ? (hipStream_t)stream : pl->stream));
+  RowsOn on;
+  if (rows_prologue(pl, src, order, stream, "rs_hip_outputs_summary", on)) return -1;
+  HIP_OK(rs_cluster_outputs_summary(on.in, pl->f32, on.order, pl->npoints, src->t_stride, nrows, index0, index_step, *spec,
+                                    acc, pl->np_pad, on.stream));
   return 0;
 }
 
@@ -530,7 +554,7 @@ int rs_hip_group_reset(RsPlan *pl, double *acc, int64_t acc_rows, const RsGroupS
   if (!pl || !acc || !spec || acc_rows < 1) return set_err("rs_hip_group_reset: bad arguments");
   if (rs_cluster_group_cols(spec) < 0) return set_err("rs_hip_group_reset%s", GROUP_SPEC_MSG);
   HIP_OK(hipSetDevice(pl->device));
-  HIP_OK(rs_cluster_group_reset(acc, acc_rows, *spec, stream ? (hipStream_t)stream : pl->stream));
+  HIP_OK(rs_cluster_group_reset(acc, acc_rows, *spec, stream_of(pl, stream)));
   return 0;
 }
 
@@ -542,16 +566,10 @@ int rs_hip_outputs_groups(RsPlan *pl, const RsOutputs *src, int32_t nrows, const
   if (cols < 0) return set_err("rs_hip_outputs_groups%s", GROUP_SPEC_MSG);
   if (acc_row0 < 0 || acc_rows < 1 || acc_row0 > acc_rows - nrows)
     return set_err("rs_hip_outputs_groups: rows [acc_row0, acc_row0 + nrows) outside the accumulator's acc_rows");
-  const void *in[6] = {src->tsurf, src->snow, src->water, src->ice, src->deposit, src->ice2};
-  for (int f = 0; f < 6; ++f)
-    if (!in[f]) return set_err("rs_hip_outputs_groups: all six streams are required");
-  if (src->t_stride < pl->npoints) return set_err("rs_hip_outputs_groups: t_stride below the plan's points");
-  if (!order && stream) return set_err("rs_hip_outputs_groups: on a stream of the caller's the order row must be a kept one");
-  if (!order && !rs_hip_plan_order(pl)) return -1;
-  HIP_OK(hipSetDevice(pl->device));
-  HIP_OK(rs_cluster_outputs_groups(in, pl->f32, order ? order : pl->order, group, pl->npoints, src->t_stride, nrows,
-                                   *spec, acc + acc_row0 * spec->ngroups * cols,
-                                   stream ? (hipStream_t)stream : pl->stream));
+  RowsOn on;
+  if (rows_prologue(pl, src, order, stream, "rs_hip_outputs_groups", on)) return -1;
+  HIP_OK(rs_cluster_outputs_groups(on.in, pl->f32, on.order, group, pl->npoints, src->t_stride, nrows, *spec,
+                                   acc + acc_row0 * spec->ngroups * cols, on.stream));
   return 0;
 }
 
@@ -564,7 +582,7 @@ int rs_hip_episodes_reset(RsPlan *pl, const RsEpisodeSpec *spec, double *acc, vo
   if (!pl || !spec || !acc) return set_err("rs_hip_episodes_reset: bad arguments");
   if (rs_cluster_episode_cols(spec) < 0) return set_err("rs_hip_episodes_reset%s", EPISODE_SPEC_MSG);
   HIP_OK(hipSetDevice(pl->device));
-  HIP_OK(rs_cluster_episodes_reset(acc, pl->np_pad, *spec, stream ? (hipStream_t)stream : pl->stream));
+  HIP_OK(rs_cluster_episodes_reset(acc, pl->np_pad, *spec, stream_of(pl, stream)));
   return 0;
 }
 
@@ -577,16 +595,10 @@ int rs_hip_outputs_episodes(RsPlan *pl, const RsOutputs *src, const void *defici
   if (rs_cluster_episode_cols(spec) < 0) return set_err("rs_hip_outputs_episodes%s", EPISODE_SPEC_MSG);
   if (!deficit && (((spec->use >> 6) & 1) || spec->peak == 6))
     return set_err("rs_hip_outputs_episodes: this spec uses the deficit (bit 6 or peak 6): deficit_device is required");
-  const void *in[6] = {src->tsurf, src->snow, src->water, src->ice, src->deposit, src->ice2};
-  for (int f = 0; f < 6; ++f)
-    if (!in[f]) return set_err("rs_hip_outputs_episodes: all six streams are required");
-  if (src->t_stride < pl->npoints) return set_err("rs_hip_outputs_episodes: t_stride below the plan's points");
-  if (!order && stream) return set_err("rs_hip_outputs_episodes: on a stream of the caller's the order row must be a kept one");
-  if (!order && !rs_hip_plan_order(pl)) return -1;
-  HIP_OK(hipSetDevice(pl->device));
-  HIP_OK(rs_cluster_outputs_episodes(in, deficit, pl->f32, order ? order : pl->order, pl->npoints, src->t_stride, nrows,
-                                     index0, index_step, *spec, acc, pl->np_pad,
-                                     stream ? (hipStream_t)stream : pl->stream));
+  RowsOn on;
+  if (rows_prologue(pl, src, order, stream, "rs_hip_outputs_episodes", on)) return -1;
+  HIP_OK(rs_cluster_outputs_episodes(on.in, deficit, pl->f32, on.order, pl->npoints, src->t_stride, nrows, index0,
+                                     index_step, *spec, acc, pl->np_pad, on.stream));
   return 0;
 }
 
@@ -594,7 +606,7 @@ int rs_hip_episodes_finish(RsPlan *pl, const RsEpisodeSpec *spec, double *acc, v
   if (!pl || !spec || !acc) return set_err("rs_hip_episodes_finish: bad arguments");
   if (rs_cluster_episode_cols(spec) < 0) return set_err("rs_hip_episodes_finish%s", EPISODE_SPEC_MSG);
   HIP_OK(hipSetDevice(pl->device));
-  HIP_OK(rs_cluster_episodes_finish(acc, pl->npoints, pl->np_pad, *spec, stream ? (hipStream_t)stream : pl->stream));
+  HIP_OK(rs_cluster_episodes_finish(acc, pl->npoints, pl->np_pad, *spec, stream_of(pl, stream)));
   return 0;
 }
 
@@ -609,11 +621,10 @@ int rs_hip_gather_nodes(RsPlan *pl, const double *src, int32_t nrows, int64_t n_
     return set_err("rs_hip_gather_nodes: stencil outside 1..RS_GRID_MAX_STENCIL");
   if (src_stride < n_nodes) return set_err("rs_hip_gather_nodes: src_stride below n_nodes");
   if (dst_stride < pl->npoints) return set_err("rs_hip_gather_nodes: dst_stride below the plan's points");
-  if (!order && stream) return set_err("rs_hip_gather_nodes: on a stream of the caller's the order row must be a kept one");
-  if (!order && !rs_hip_plan_order(pl)) return -1;
-  HIP_OK(hipSetDevice(pl->device));
-  HIP_OK(rs_grid_gather(src, nrows, n_nodes, src_stride, node, weight, stencil, order ? order : pl->order, present_above,
-                        missing_value, dst, dst_stride, pl->npoints, stream ? (hipStream_t)stream : pl->stream));
+  RowsOn on;
+  if (rows_order(pl, order, stream, "rs_hip_gather_nodes", on)) return -1;
+  HIP_OK(rs_grid_gather(src, nrows, n_nodes, src_stride, node, weight, stencil, on.order, present_above, missing_value, dst,
+                        dst_stride, pl->npoints, on.stream));
   return 0;
 }
 
@@ -727,6 +738,42 @@ static int check_forcing(const RsPlan *pl, const RsForcing *f, const char *who) 
   return 0;
 }
 
+/* The output window of a step launch over [t0, t0 + nsteps): all six streams, rows of at least the plan's points, the
+ * launch inside the series and its first kept row not before the window's row0 (the kernels store row r at r - row0) */
+static int check_out_window(const RsPlan *pl, const RsOutputs *o, int32_t t0, int32_t nsteps, const char *who) {
+  if (!o || !o->tsurf || !o->snow || !o->water || !o->ice || !o->deposit || !o->ice2)
+    return set_err("%s: all six output streams are required", who);
+  if (o->t_stride < pl->npoints) return set_err("%s: output t_stride < npoints", who);
+  if (o->decimate < 1) return set_err("%s: decimate must be >= 1", who);
+  if (t0 < 1 || nsteps < 1 || (int64_t)t0 + nsteps - 1 > pl->c.SimLen)
+    return set_err("%s: window [%d,%d) outside [1,SimLen=%d]", who, t0, t0 + nsteps, pl->c.SimLen);
+  const int64_t first = ((int64_t)t0 - 1 + o->decimate - 1) / o->decimate;
+  if (first < o->row0)
+    return set_err("%s: output row0 %lld beyond first row %lld", who, (long long)o->row0, (long long)first);
+  return 0;
+}
+
+static int check_relaxation(const RsPlan *pl, const RsPointParams *pp, const char *who) {
+  if (pl->c.use_relaxation && pp->tair_relax && (!pp->vz_relax || !pp->rh_relax || !pp->initlen))
+    return set_err("%s: relaxation needs tair_relax, vz_relax, rh_relax and initlen", who);
+  return 0;
+}
+
+/* Sky view needs the points' geometry and, of a forcing window `f`, the two radiation streams, the sun rows and a time
+ * axis shared by all points; f == NULL (the raw series, which have all of that but the sun rows): the sun table */
+static int check_sky_view(const RsPointParams *pp, const RsForcing *f, const double *sun, const char *who) {
+  if (!pp->sky_view) return 0;
+  const bool geometry = pp->sin_lat && pp->cos_lat && pp->lon_rad;
+  if (!f) {
+    if (!geometry || !sun) return set_err("%s: sky view needs sin_lat, cos_lat, lon_rad and the sun table", who);
+    return 0;
+  }
+  if (!geometry || !f->sw_dir || !f->lw_net || !f->sun)
+    return set_err("%s: sky view needs sin_lat, cos_lat, lon_rad, sw_dir, lw_net and sun", who);
+  if (f->hour_pstride) return set_err("%s: sky view needs a time axis shared by all points", who);
+  return 0;
+}
+
 int rs_hip_init_state(RsPlan *pl, const RsForcing *f, const RsPointParams *pp) {
   if (!pl) return set_err("rs_hip_init_state: null plan");
   if (check_forcing(pl, f, "rs_hip_init_state")) return -1;
@@ -798,6 +845,63 @@ static hipError_t launch_step(const RsPlan *pl, const rs::StepArgs &a, rs::StepS
   return s.f32 ? rs32_launch_step(a, l, pl->stream) : rs_launch_step(a, l, pl->stream);
 }
 
+/* The event pair around a timed step launch (rs_hip_timing_reset; rs_hip_step and rs_hip_step_knots).  Every
+ * argument / feature check of the entry point comes before timing_begin: a start event without its stop event would
+ * poison rs_hip_timing_step_ms.  The pair is taken by timing_end alone, which a failed launch never reaches: ev_used
+ * has not advanced and the next launch records the same pair again. */
+static int timing_begin(RsPlan *pl, const char *who) {
+  if (!pl->timing) return 0;
+  if (pl->ev_used + 2 > pl->ev.size()) {
+    hipEvent_t x, y;
+    HIP_OK(hipEventCreate(&x));
+    if (hipEventCreate(&y) != hipSuccess) {
+      (void)hipEventDestroy(x);
+      return set_err("%s: hipEventCreate failed", who);
+    }
+    pl->ev.push_back(x);
+    pl->ev.push_back(y);
+  }
+  HIP_OK(hipEventRecord(pl->ev[pl->ev_used], pl->stream));
+  return 0;
+}
+static int timing_end(RsPlan *pl) {
+  if (!pl->timing) return 0;
+  HIP_OK(hipEventRecord(pl->ev[pl->ev_used + 1], pl->stream));
+  pl->ev_used += 2;
+  return 0;
+}
+
+/* coupling rounds: the scratch of the list of points that replay (allocated on first use) */
+static int ensure_cpl_scratch(RsPlan *pl) {
+  if (pl->cpl_list) return 0;
+  HIP_OK(plan_malloc(pl, &pl->cpl_flags, (size_t)2 * pl->np_pad * sizeof(int32_t)));
+  HIP_OK(plan_malloc(pl, &pl->cpl_list, (size_t)pl->np_pad * sizeof(int32_t)));
+  HIP_OK(plan_malloc(pl, &pl->cpl_count, sizeof(int32_t)));
+  pl->cpl_tmp_bytes = rs_cpl_select_scratch_bytes(pl->npoints);
+  HIP_OK(plan_malloc(pl, &pl->cpl_tmp, pl->cpl_tmp_bytes ? pl->cpl_tmp_bytes : 8));
+  return 0;
+}
+
+/* The window of a replay call must cover [couplingStartI, couplingEndI + 1] of every point that replays: the rewind
+ * reads the forcing of the index behind the window end (CheckValues, Simulation.f90:59-66) - unless that is beyond
+ * SimLen - and a point whose window start lies before t0 would never step.  (A block of rs_cpl_replay_raw ends before
+ * SimLen, so there the clamp never acts: a covered window end + 1 lies inside the block.) */
+static int check_cpl_coverage(RsPlan *pl, const rs::StepArgs &a, const char *who) {
+  if (ensure_cpl_scratch(pl)) return -1;
+  int32_t b[2] = {INT32_MAX, 0};
+  HIP_OK(hipMemcpyAsync(pl->cpl_flags, b, sizeof(b), hipMemcpyHostToDevice, pl->stream));
+  HIP_OK(rs_launch_cpl_window_bounds(a, pl->cpl_flags, pl->stream));
+  HIP_OK(hipMemcpyAsync(b, pl->cpl_flags, sizeof(b), hipMemcpyDeviceToHost, pl->stream));
+  HIP_OK(hipStreamSynchronize(pl->stream));
+  if (b[1] > 0) {
+    const int32_t need_hi = b[1] + 1 < pl->c.SimLen ? b[1] + 1 : pl->c.SimLen;
+    if (b[0] < a.t0 || need_hi > a.t0 + a.nsteps - 1)
+      return set_err("%s: the window [%d,%d] does not cover the coupling windows of the points that replay, [%d,%d] "
+                     "(window start to the index behind the window end)", who, a.t0, a.t0 + a.nsteps - 1, b[0], need_hi);
+  }
+  return 0;
+}
+
 /* The replay rounds of a coupled run: while some points ask for another replay of their coupling
  * window (start_coupling_again), those points - compacted into full wavefronts - rewind, replay
  * the window and park again (step_kernel_coupled with cpl_stop).  `a` describes a window that
@@ -807,13 +911,7 @@ static hipError_t launch_step(const RsPlan *pl, const rs::StepArgs &a, rs::StepS
  * scalar row arithmetic, coalesced outputs of the first pass' quality) instead of the general
  * kernel (s.cpl = GENERAL), which carries a time index per lane.  s.src = RAW: the forcing from the raw series. */
 static int cpl_replay_rounds(RsPlan *pl, rs::StepArgs a, const rs::StepShape &s) {
-  if (!pl->cpl_list) {
-    HIP_OK(plan_malloc(pl, &pl->cpl_flags, (size_t)2 * pl->np_pad * sizeof(int32_t)));
-    HIP_OK(plan_malloc(pl, &pl->cpl_list, (size_t)pl->np_pad * sizeof(int32_t)));
-    HIP_OK(plan_malloc(pl, &pl->cpl_count, sizeof(int32_t)));
-    pl->cpl_tmp_bytes = rs_cpl_select_scratch_bytes(pl->npoints);
-    HIP_OK(plan_malloc(pl, &pl->cpl_tmp, pl->cpl_tmp_bytes ? pl->cpl_tmp_bytes : 8));
-  }
+  if (ensure_cpl_scratch(pl)) return -1;
   a.cpl_stop = 1;
   pl->cpl_rounds_last = 0;
   for (int round = 0; round < 64; ++round) { /* the reference stops at 25 */
@@ -863,18 +961,7 @@ int rs_hip_step(RsPlan *pl, const RsForcing *f, const RsOutputs *o, const RsPoin
   if (!pl) return set_err("rs_hip_step: null plan");
   if (check_forcing(pl, f, "rs_hip_step")) return -1;
   if (!pp || !pp->tbottom) return set_err("rs_hip_step: tbottom is required");
-  if (!o || !o->tsurf || !o->snow || !o->water || !o->ice || !o->deposit || !o->ice2)
-    return set_err("rs_hip_step: all six output streams are required");
-  if (o->t_stride < pl->npoints) return set_err("rs_hip_step: output t_stride < npoints");
-  if (o->decimate < 1) return set_err("rs_hip_step: decimate must be >= 1");
-  if (t0 < 1 || nsteps < 1 || (int64_t)t0 + nsteps - 1 > pl->c.SimLen)
-    return set_err("rs_hip_step: window [%d,%d) outside [1,SimLen=%d]", t0, t0 + nsteps,
-                   pl->c.SimLen);
-  {
-    const int64_t first = ((int64_t)t0 - 1 + o->decimate - 1) / o->decimate;
-    if (first < o->row0) return set_err("rs_hip_step: output row0 %lld beyond first row %lld",
-                                        (long long)o->row0, (long long)first);
-  }
+  if (check_out_window(pl, o, t0, nsteps, "rs_hip_step")) return -1;
   HIP_OK(hipSetDevice(pl->device));
   /* LEAN kernel is exact when nothing optional can act: no observation forcing
    * after index 1 (at index 1 it is a no-op: the profile was initialised from
@@ -883,15 +970,9 @@ int rs_hip_step(RsPlan *pl, const RsForcing *f, const RsOutputs *o, const RsPoin
   const bool full = (pp->initlen != nullptr) || pl->c.force_tsurf || (f->depth != nullptr) ||
                     (pl->c.tsurfOutputDepth >= 0.0) ||
                     (pl->c.use_relaxation && pp->tair_relax != nullptr) || (f->tdew != nullptr);
-  if (pl->c.use_relaxation && pp->tair_relax && (!pp->vz_relax || !pp->rh_relax || !pp->initlen))
-    return set_err("rs_hip_step: relaxation needs tair_relax, vz_relax, rh_relax and initlen");
+  if (check_relaxation(pl, pp, "rs_hip_step")) return -1;
   const bool skyview = pp->sky_view != nullptr;
-  if (skyview) {
-    if (!pp->sin_lat || !pp->cos_lat || !pp->lon_rad || !f->sw_dir || !f->lw_net || !f->sun)
-      return set_err("rs_hip_step: sky view needs sin_lat, cos_lat, lon_rad, sw_dir, lw_net and sun");
-    if (f->hour_pstride)
-      return set_err("rs_hip_step: sky view needs a time axis shared by all points");
-  }
+  if (check_sky_view(pp, f, nullptr, "rs_hip_step")) return -1;
   const bool coupled = pl->c.use_coupling && pp->coupling_index != nullptr;
   if (coupled) {
     if (!pp->coupling_tsurf) return set_err("rs_hip_step: coupling needs coupling_index and coupling_tsurf");
@@ -899,8 +980,6 @@ int rs_hip_step(RsPlan *pl, const RsForcing *f, const RsOutputs *o, const RsPoin
       return set_err("rs_hip_step: with coupling the window must be the whole series "
                      "(t0 = 1, nsteps = SimLen = %d): coupling windows are replayed", pl->c.SimLen);
   }
-  /* every argument / feature check comes before the event pool is touched: a start event
-   * without its stop event would poison rs_hip_timing_step_ms */
   if (pl->c.use_coupling && !pp->coupling_index)
     return set_err("rs_hip_step: use_coupling is set: pass coupling_index/coupling_tsurf");
   if (pl->f32 && pl->diag_on) return set_err("rs_hip_step: diagnostics: the fp64 flavour only");
@@ -918,22 +997,7 @@ int rs_hip_step(RsPlan *pl, const RsForcing *f, const RsOutputs *o, const RsPoin
   s.depth = f->depth || pl->c.tsurfOutputDepth >= 0.0;
   s.cpl = coupled ? rs::StepCoupling::GENERAL : rs::StepCoupling::NONE;
   s.a32 = window_a32(o, t0, nsteps, f->t_stride, a.wb.sw_dir ? a.wb.t_stride : 0);
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (pl->timing) {
-    if (pl->ev_used + 2 > pl->ev.size()) {
-      hipEvent_t x, y;
-      HIP_OK(hipEventCreate(&x));
-      if (hipEventCreate(&y) != hipSuccess) {
-        (void)hipEventDestroy(x);
-        return set_err("rs_hip_step: hipEventCreate failed");
-      }
-      pl->ev.push_back(x);
-      pl->ev.push_back(y);
-    }
-    e0 = pl->ev[pl->ev_used];
-    e1 = pl->ev[pl->ev_used + 1];
-    HIP_OK(hipEventRecord(e0, pl->stream));
-  }
+  if (timing_begin(pl, "rs_hip_step")) return -1; /* (behind the last argument check) */
   hipError_t le;
   if (coupled && !pl->f32) {
     /* Rounds instead of "every wavefront replays until its slowest lane is through"
@@ -955,13 +1019,8 @@ int rs_hip_step(RsPlan *pl, const RsForcing *f, const RsOutputs *o, const RsPoin
     }
   } else
     le = launch_step(pl, a, s);
-  if (le != hipSuccess) /* the pair stays unused: ev_used has not advanced */
-    return set_err("rs_hip_step: kernel launch failed: %s", hipGetErrorString(le));
-  if (pl->timing) {
-    HIP_OK(hipEventRecord(e1, pl->stream));
-    pl->ev_used += 2;
-  }
-  return 0;
+  if (le != hipSuccess) return set_err("rs_hip_step: kernel launch failed: %s", hipGetErrorString(le));
+  return timing_end(pl);
 }
 
 /* The LEAN step of the two-wavefront flavour WITHOUT a forcing window: the ground wave of every
@@ -974,12 +1033,7 @@ int rs_hip_step_knots(RsPlan *pl, const RsSynthSpec *spec, const double *knots, 
                       const RsOutputs *o, const RsPointParams *pp, int32_t t0, int32_t nsteps) {
   if (!pl || !spec || !knots) return set_err("rs_hip_step_knots: bad arguments");
   if (!pp || !pp->tbottom) return set_err("rs_hip_step_knots: tbottom is required");
-  if (!o || !o->tsurf || !o->snow || !o->water || !o->ice || !o->deposit || !o->ice2)
-    return set_err("rs_hip_step_knots: all six output streams are required");
-  if (o->t_stride < pl->npoints) return set_err("rs_hip_step_knots: output t_stride < npoints");
-  if (o->decimate < 1) return set_err("rs_hip_step_knots: decimate must be >= 1");
-  if (t0 < 1 || nsteps < 1 || (int64_t)t0 + nsteps - 1 > pl->c.SimLen)
-    return set_err("rs_hip_step_knots: window [%d,%d) outside [1,SimLen=%d]", t0, t0 + nsteps, pl->c.SimLen);
+  if (check_out_window(pl, o, t0, nsteps, "rs_hip_step_knots")) return -1;
   const int32_t spk = spec->steps_per_knot;
   if (spk < 1) return set_err("rs_hip_step_knots: steps_per_knot < 1");
   {
@@ -987,8 +1041,6 @@ int rs_hip_step_knots(RsPlan *pl, const RsSynthSpec *spec, const double *knots, 
     const int32_t klast = tlast / spk + ((tlast % spk) ? 1 : 0);
     if (kfirst < k0 || klast >= k0 + nknots)
       return set_err("rs_hip_step_knots: need knots %d..%d, buffer has %d..%d", kfirst, klast, k0, k0 + nknots - 1);
-    const int64_t first = ((int64_t)t0 - 1 + o->decimate - 1) / o->decimate;
-    if (first < o->row0) return set_err("rs_hip_step_knots: output row0 beyond first row");
   }
   if (pl->c.NLayers != 15 || pl->c.tsurfOutputDepth >= 0.0 || pp->sky_view ||
       (pl->c.use_coupling && pp->coupling_index) || (!pl->f32 && !window_a32(o, t0, nsteps, 0, 0)))
@@ -998,8 +1050,7 @@ int rs_hip_step_knots(RsPlan *pl, const RsSynthSpec *spec, const double *knots, 
    * of index 1, an initialization phase, relaxation - what rs_hip_step calls `full` for a window with the
    * Tdew and TsurfObs streams and no depth stream */
   const bool full = (pp->initlen != nullptr) || pl->c.force_tsurf || (pl->c.use_relaxation && pp->tair_relax != nullptr);
-  if (pl->c.use_relaxation && pp->tair_relax && (!pp->vz_relax || !pp->rh_relax || !pp->initlen))
-    return set_err("rs_hip_step_knots: relaxation needs tair_relax, vz_relax, rh_relax and initlen");
+  if (check_relaxation(pl, pp, "rs_hip_step_knots")) return -1;
   const int32_t *order = rs_hip_plan_order(pl);
   if (!order) return -1;
   HIP_OK(hipSetDevice(pl->device));
@@ -1018,30 +1069,11 @@ int rs_hip_step_knots(RsPlan *pl, const RsSynthSpec *spec, const double *knots, 
   rs::StepShape s;
   s.src = rs::StepSource::KNOTS;
   s.full = full;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (pl->timing) {
-    if (pl->ev_used + 2 > pl->ev.size()) {
-      hipEvent_t x, y;
-      HIP_OK(hipEventCreate(&x));
-      if (hipEventCreate(&y) != hipSuccess) {
-        (void)hipEventDestroy(x);
-        return set_err("rs_hip_step_knots: hipEventCreate failed");
-      }
-      pl->ev.push_back(x);
-      pl->ev.push_back(y);
-    }
-    e0 = pl->ev[pl->ev_used];
-    e1 = pl->ev[pl->ev_used + 1];
-    HIP_OK(hipEventRecord(e0, pl->stream));
-  }
+  if (timing_begin(pl, "rs_hip_step_knots")) return -1;
   /* fp32: two points per lane, each lane interpolating its own forcing (rs_kernels_f32.hip) */
   const hipError_t le = launch_step(pl, a, s);
   if (le != hipSuccess) return set_err("rs_hip_step_knots: kernel launch failed: %s", hipGetErrorString(le));
-  if (pl->timing) {
-    HIP_OK(hipEventRecord(e1, pl->stream));
-    pl->ev_used += 2;
-  }
-  return 0;
+  return timing_end(pl);
 }
 
 } /* extern "C" */
@@ -1060,23 +1092,15 @@ int rs_step_raw(RsPlan *pl, const rs::RawForcing *raw, const double *sun, const 
   if (!pl || !raw || raw->nsrc < 1 || raw->nsrc > RS_MAX_SOURCES || !raw->segs || !raw->hour)
     return set_err("rs_step_raw: bad arguments");
   if (!pp || !pp->tbottom || !pp->initlen) return set_err("rs_step_raw: tbottom and initlen are required");
-  if (!o || !o->tsurf || !o->snow || !o->water || !o->ice || !o->deposit || !o->ice2)
-    return set_err("rs_step_raw: all six output streams are required");
-  if (o->t_stride < pl->npoints || o->decimate < 1) return set_err("rs_step_raw: bad output window");
-  if (t0 < 1 || nsteps < 1 || (int64_t)t0 + nsteps - 1 > pl->c.SimLen)
-    return set_err("rs_step_raw: window [%d,%d) outside [1,SimLen=%d]", t0, t0 + nsteps, pl->c.SimLen);
-  const int64_t first = ((int64_t)t0 - 1 + o->decimate - 1) / o->decimate;
-  if (first < o->row0) return set_err("rs_step_raw: output row0 beyond first row");
+  if (check_out_window(pl, o, t0, nsteps, "rs_step_raw")) return -1;
   if (!rs_step_raw_ok(pl) || !window_a32(o, t0, nsteps, 0, 0))
     return set_err("rs_step_raw: NLayers = 15, fp64, no output depth and an output window below 4 GiB per stream only");
   const bool coupled = pl->c.use_coupling != 0;
   if (coupled && (!pp->coupling_index || !pp->coupling_tsurf))
     return set_err("rs_step_raw: use_coupling is set: pass coupling_index and coupling_tsurf");
-  if (pl->c.use_relaxation && pp->tair_relax && (!pp->vz_relax || !pp->rh_relax))
-    return set_err("rs_step_raw: relaxation needs tair_relax, vz_relax, rh_relax and initlen");
+  if (check_relaxation(pl, pp, "rs_step_raw")) return -1;
   const bool sky = pp->sky_view != nullptr;
-  if (sky && (!pp->sin_lat || !pp->cos_lat || !pp->lon_rad || !sun))
-    return set_err("rs_step_raw: sky view needs sin_lat, cos_lat, lon_rad and the sun table");
+  if (check_sky_view(pp, nullptr, sun, "rs_step_raw")) return -1;
   if (raw->seg0 < 0 || raw->seg0 >= raw->nseg) return set_err("rs_step_raw: seg0 outside the segment table");
   HIP_OK(hipSetDevice(pl->device));
   rs::StepArgs a;
@@ -1109,9 +1133,8 @@ int rs_cpl_replay_raw(RsPlan *pl, const rs::RawForcing *raw, const RsOutputs *o,
     return set_err("rs_cpl_replay_raw: tbottom, initlen, coupling_index and coupling_tsurf are required");
   if (!pl->c.use_coupling || !rs_step_raw_ok(pl) || pp->sky_view)
     return set_err("rs_cpl_replay_raw: a coupled plan with NLayers = 15, fp64, no output depth, no sky view only");
-  if (!o || !o->tsurf || !o->snow || !o->water || !o->ice || !o->deposit || !o->ice2 || o->decimate < 1)
-    return set_err("rs_cpl_replay_raw: all six output streams are required");
-  if (t0 < 1 || nsteps < 1 || (int64_t)t0 + nsteps - 1 >= pl->c.SimLen)
+  if (check_out_window(pl, o, t0, nsteps, "rs_cpl_replay_raw")) return -1;
+  if ((int64_t)t0 + nsteps - 1 >= pl->c.SimLen)
     return set_err("rs_cpl_replay_raw: the block [%d,%d] must lie inside [1, SimLen - 1]", t0, t0 + nsteps - 1);
   if (!window_a32(o, t0, nsteps, 0, 0))
     return set_err("rs_cpl_replay_raw: output window of 4 GiB per stream or more");
@@ -1123,23 +1146,7 @@ int rs_cpl_replay_raw(RsPlan *pl, const rs::RawForcing *raw, const RsOutputs *o,
   a.knots_tdew = 2;
   a.raw = *raw;
   a.out_index = (out_by_point && pl->order) ? pl->order : nullptr;
-  { /* the block must cover the coupling windows of the points that replay (as rs_hip_cpl_replay checks) */
-    if (!pl->cpl_list) {
-      HIP_OK(plan_malloc(pl, &pl->cpl_flags, (size_t)2 * pl->np_pad * sizeof(int32_t)));
-      HIP_OK(plan_malloc(pl, &pl->cpl_list, (size_t)pl->np_pad * sizeof(int32_t)));
-      HIP_OK(plan_malloc(pl, &pl->cpl_count, sizeof(int32_t)));
-      pl->cpl_tmp_bytes = rs_cpl_select_scratch_bytes(pl->npoints);
-      HIP_OK(plan_malloc(pl, &pl->cpl_tmp, pl->cpl_tmp_bytes ? pl->cpl_tmp_bytes : 8));
-    }
-    int32_t b[2] = {INT32_MAX, 0};
-    HIP_OK(hipMemcpyAsync(pl->cpl_flags, b, sizeof(b), hipMemcpyHostToDevice, pl->stream));
-    HIP_OK(rs_launch_cpl_window_bounds(a, pl->cpl_flags, pl->stream));
-    HIP_OK(hipMemcpyAsync(b, pl->cpl_flags, sizeof(b), hipMemcpyDeviceToHost, pl->stream));
-    HIP_OK(hipStreamSynchronize(pl->stream));
-    if (b[1] > 0 && (b[0] < t0 || b[1] + 1 > t0 + nsteps - 1))
-      return set_err("rs_cpl_replay_raw: the block [%d,%d] does not cover the coupling windows of the points that "
-                     "replay, [%d,%d]", t0, t0 + nsteps - 1, b[0], b[1] + 1);
-  }
+  if (check_cpl_coverage(pl, a, "rs_cpl_replay_raw")) return -1;
   rs::StepShape s;
   s.src = rs::StepSource::RAW;
   s.full = true;
@@ -1164,21 +1171,10 @@ static int cpl_args(RsPlan *pl, const RsForcing *f, const RsOutputs *o, const Rs
     return set_err("%s: tbottom, coupling_index and coupling_tsurf are required", who);
   if (!pl->c.use_coupling) return set_err("%s: the plan's settings have use_coupling = 0", who);
   if (pl->f32) return set_err("%s: time-chunked coupling needs the fp64 flavour (an fp32 plan runs a coupled series whole: rs_hip_step)", who);
-  if (pp->sky_view) {
-    if (!pp->sin_lat || !pp->cos_lat || !pp->lon_rad || !f->sw_dir || !f->lw_net || !f->sun)
-      return set_err("%s: sky view needs sin_lat, cos_lat, lon_rad, sw_dir, lw_net and sun", who);
-    if (f->hour_pstride) return set_err("%s: sky view needs a time axis shared by all points", who);
-    if (pl->wb.sw_dir)
-      return set_err("%s: the write-back of the sky-view edits follows whole-series windows: use "
-                     "rs_hip_step", who);
-  }
-  if (pl->c.use_relaxation && pp->tair_relax && (!pp->vz_relax || !pp->rh_relax || !pp->initlen))
-    return set_err("%s: relaxation needs tair_relax, vz_relax, rh_relax and initlen", who);
-  if (!o || !o->tsurf || !o->snow || !o->water || !o->ice || !o->deposit || !o->ice2)
-    return set_err("%s: all six output streams are required", who);
-  if (o->t_stride < pl->npoints || o->decimate < 1) return set_err("%s: bad output window", who);
-  if (t0 < 1 || nsteps < 1 || (int64_t)t0 + nsteps - 1 > pl->c.SimLen)
-    return set_err("%s: window [%d,%d) outside [1,SimLen=%d]", who, t0, t0 + nsteps, pl->c.SimLen);
+  if (check_sky_view(pp, f, nullptr, who)) return -1;
+  if (pp->sky_view && pl->wb.sw_dir)
+    return set_err("%s: the write-back of the sky-view edits follows whole-series windows: use rs_hip_step", who);
+  if (check_relaxation(pl, pp, who) || check_out_window(pl, o, t0, nsteps, who)) return -1;
   step_args(pl, o, pp, t0, nsteps, a);
   a.f = *f;
   a.out_index = (pl->output_by_point && pl->order) ? pl->order : nullptr;
@@ -1212,30 +1208,7 @@ int rs_hip_cpl_replay(RsPlan *pl, const RsForcing *f, const RsOutputs *o, const 
     if (strcmp(e, "lockstep") == 0) lockstep = true;
   }
   if ((int64_t)t0 + nsteps - 1 >= pl->c.SimLen) lockstep = false;
-  {
-    /* the window must cover [couplingStartI, couplingEndI + 1] of every point that replays: the rewind
-     * reads the forcing of the index behind the window end (CheckValues, Simulation.f90:59-66), and a
-     * point whose window start lies before t0 would never step */
-    if (!pl->cpl_list) { /* scratch of the rounds (allocated here so that cpl_count exists) */
-      HIP_OK(plan_malloc(pl, &pl->cpl_flags, (size_t)2 * pl->np_pad * sizeof(int32_t)));
-      HIP_OK(plan_malloc(pl, &pl->cpl_list, (size_t)pl->np_pad * sizeof(int32_t)));
-      HIP_OK(plan_malloc(pl, &pl->cpl_count, sizeof(int32_t)));
-      pl->cpl_tmp_bytes = rs_cpl_select_scratch_bytes(pl->npoints);
-      HIP_OK(plan_malloc(pl, &pl->cpl_tmp, pl->cpl_tmp_bytes ? pl->cpl_tmp_bytes : 8));
-    }
-    int32_t b[2] = {INT32_MAX, 0};
-    HIP_OK(hipMemcpyAsync(pl->cpl_flags, b, sizeof(b), hipMemcpyHostToDevice, pl->stream));
-    HIP_OK(rs_launch_cpl_window_bounds(a, pl->cpl_flags, pl->stream));
-    HIP_OK(hipMemcpyAsync(b, pl->cpl_flags, sizeof(b), hipMemcpyDeviceToHost, pl->stream));
-    HIP_OK(hipStreamSynchronize(pl->stream));
-    if (b[1] > 0) {
-      const int32_t need_hi = b[1] + 1 < pl->c.SimLen ? b[1] + 1 : pl->c.SimLen;
-      if (b[0] < t0 || need_hi > t0 + nsteps - 1)
-        return set_err("rs_hip_cpl_replay: the window [%d,%d] does not cover the coupling windows of the "
-                       "points that replay, [%d,%d] (window start to the index behind the window end)",
-                       t0, t0 + nsteps - 1, b[0], need_hi);
-    }
-  }
+  if (check_cpl_coverage(pl, a, "rs_hip_cpl_replay")) return -1;
   rs::StepShape s;
   s.full = true;
   s.sky = pp->sky_view != nullptr;

@@ -23,8 +23,12 @@ F64_FORCING = ("tair", "tdew", "vz", "rhz", "prec", "sw", "lw", "tsurfobs", "dep
 OUT_FIELDS = ("tsurf", "snow", "water", "ice", "deposit", "ice2")
 
 
-def _ptr(t):
+def _ptr(t):  # a tensor's device pointer; None (an optional array, the plan's own order row) stays None
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _stream_ptr(stream):  # a stream of the caller's; None: the plan's
+    return None if stream is None else C.c_void_p(stream.cuda_stream)
 
 
 def require_gpu() -> None:
@@ -93,6 +97,18 @@ class OutputWindow:
         o.row0 = row0
         return o
 
+    def struct_at(self, t0: int, out_row0: int | None = None) -> lib.RsOutputs:
+        """For a launch at time index ``t0``: its first output row is the window's row 0, unless ``out_row0`` says
+        which absolute row that is."""
+        return self.struct((t0 - 1 + self.decimate - 1) // self.decimate if out_row0 is None else out_row0)
+
+    def struct_from(self, row: int) -> lib.RsOutputs:
+        """The window from its row ``row`` on (what the consumers of output rows read)."""
+        o = self.struct(0)
+        for n in OUT_FIELDS:
+            setattr(o, n, C.c_void_p(self.tensors[n][row].data_ptr()))
+        return o
+
 
 class Plan:
     """RAII wrapper of ``RsPlan``: one shard of points on one GPU, one stream."""
@@ -159,7 +175,7 @@ class Plan:
     def step(self, window: ForcingWindow, out: OutputWindow, pp, t0: int, nsteps: int,
              window_row: int = 0, out_row0: int | None = None) -> None:
         f = window.struct(window_row)
-        o = out.struct((t0 - 1 + out.decimate - 1) // out.decimate if out_row0 is None else out_row0)
+        o = out.struct_at(t0, out_row0)
         lib.check(self.L.rs_hip_step(self._h, C.byref(f), C.byref(o), C.byref(pp), t0, nsteps),
                   "rs_hip_step")
 
@@ -167,7 +183,7 @@ class Plan:
                    out_row0: int | None = None) -> None:
         """expand_ordered + step in one launch without a forcing window (rs_hip_step_knots: the
         two-wavefront flavour's ground wave interpolates the forcing from the knots)."""
-        o = out.struct((t0 - 1 + out.decimate - 1) // out.decimate if out_row0 is None else out_row0)
+        o = out.struct_at(t0, out_row0)
         lib.check(self.L.rs_hip_step_knots(self._h, C.byref(spec), C.c_void_p(knots.data_ptr()), 0, knots.shape[0],
                                            C.byref(o), C.byref(pp), t0, nsteps), "rs_hip_step_knots")
 
@@ -175,7 +191,7 @@ class Plan:
                  window_row: int = 0, out_row0: int | None = None) -> None:
         """A chunk of a coupled run in lock step (rs_hip_step_cpl): no replays, points park."""
         f = window.struct(window_row)
-        o = out.struct((t0 - 1 + out.decimate - 1) // out.decimate if out_row0 is None else out_row0)
+        o = out.struct_at(t0, out_row0)
         lib.check(self.L.rs_hip_step_cpl(self._h, C.byref(f), C.byref(o), C.byref(pp), t0, nsteps),
                   "rs_hip_step_cpl")
 
@@ -183,7 +199,7 @@ class Plan:
                    window_row: int = 0, out_row0: int | None = None) -> int:
         """The replay rounds of the parked points over [t0, t0+nsteps) (rs_hip_cpl_replay)."""
         f = window.struct(window_row)
-        o = out.struct((t0 - 1 + out.decimate - 1) // out.decimate if out_row0 is None else out_row0)
+        o = out.struct_at(t0, out_row0)
         rounds = C.c_int32(0)
         lib.check(self.L.rs_hip_cpl_replay(self._h, C.byref(f), C.byref(o), C.byref(pp), t0, nsteps,
                                            C.byref(rounds)), "rs_hip_cpl_replay")
@@ -290,11 +306,8 @@ class Plan:
         o = out.struct(0)
         rows = next(iter(dst.values())).shape[1]
         ptrs = (C.c_void_p * 6)(*[dst[n].data_ptr() for n in OUT_FIELDS])
-        lib.check(self.L.rs_hip_outputs_by_point(self._h, C.byref(o), int(nrows),
-                                                 C.c_void_p(order.data_ptr()) if order is not None else None,
-                                                 ptrs, C.c_int64(rows), C.c_int64(dst_row0),
-                                                 C.c_void_p(stream.cuda_stream) if stream is not None else None),
-                  "rs_hip_outputs_by_point")
+        lib.check(self.L.rs_hip_outputs_by_point(self._h, C.byref(o), int(nrows), _ptr(order), ptrs, C.c_int64(rows),
+                                                 C.c_int64(dst_row0), _stream_ptr(stream)), "rs_hip_outputs_by_point")
 
     def summary_reset(self, acc: torch.Tensor | None = None, stream: torch.cuda.Stream | None = None) -> torch.Tensor:
         """The empty summary into every column of ``acc``, float64 [RS_SUM_COLS, np_pad] on this device (made
@@ -302,8 +315,7 @@ class Plan:
         if acc is None:
             acc = torch.empty((lib.RS_SUM_COLS, self.np_pad), dtype=torch.float64, device=self.device)
         assert acc.dtype == torch.float64 and acc.shape == (lib.RS_SUM_COLS, self.np_pad) and acc.is_contiguous()
-        lib.check(self.L.rs_hip_summary_reset(self._h, C.c_void_p(acc.data_ptr()),
-                                              C.c_void_p(stream.cuda_stream) if stream is not None else None),
+        lib.check(self.L.rs_hip_summary_reset(self._h, C.c_void_p(acc.data_ptr()), _stream_ptr(stream)),
                   "rs_hip_summary_reset")
         return acc
 
@@ -314,14 +326,10 @@ class Plan:
         columns).  The first of these rows is the absolute 1-based time index ``index0``, the next ``index0 +
         index_step``; ``spec``: summary.SummarySpec; ``order`` and ``stream`` as for ``outputs_by_point``."""
         assert acc.dtype == torch.float64 and acc.shape == (lib.RS_SUM_COLS, self.np_pad) and acc.is_contiguous()
-        o = out.struct(0)
-        for n in OUT_FIELDS:
-            setattr(o, n, C.c_void_p(out.tensors[n][row].data_ptr()))
+        o = out.struct_from(row)
         sp = lib.summary_spec(spec)
-        lib.check(self.L.rs_hip_outputs_summary(self._h, C.byref(o), int(nrows), int(index0), int(index_step),
-                                                C.c_void_p(order.data_ptr()) if order is not None else None,
-                                                C.byref(sp), C.c_void_p(acc.data_ptr()),
-                                                C.c_void_p(stream.cuda_stream) if stream is not None else None),
+        lib.check(self.L.rs_hip_outputs_summary(self._h, C.byref(o), int(nrows), int(index0), int(index_step), _ptr(order),
+                                                C.byref(sp), C.c_void_p(acc.data_ptr()), _stream_ptr(stream)),
                   "rs_hip_outputs_summary")
 
     def summary(self, acc: torch.Tensor):
@@ -343,8 +351,7 @@ class Plan:
         """The accumulator of no rows into every column of ``acc``, float64 [cols, np_pad] on this device (made here
         if None) - what ``outputs_episodes`` feeds (rs_hip_episodes_reset); ``spec``: episodes.EpisodeSpec."""
         sp, acc = self._episode_acc(spec, acc)
-        lib.check(self.L.rs_hip_episodes_reset(self._h, C.byref(sp), C.c_void_p(acc.data_ptr()),
-                                               C.c_void_p(stream.cuda_stream) if stream is not None else None),
+        lib.check(self.L.rs_hip_episodes_reset(self._h, C.byref(sp), C.c_void_p(acc.data_ptr()), _stream_ptr(stream)),
                   "rs_hip_episodes_reset")
         return acc
 
@@ -358,25 +365,20 @@ class Plan:
         ([rows, t_stride]; its row ``row`` is the first one read), required iff the spec tests it or keeps its peak;
         ``order`` and ``stream`` as for ``outputs_by_point``."""
         sp, acc = self._episode_acc(spec, acc)
-        o = out.struct(0)
-        for n in OUT_FIELDS:
-            setattr(o, n, C.c_void_p(out.tensors[n][row].data_ptr()))
+        o = out.struct_from(row)
         d = None
         if deficit is not None:
             assert deficit.dtype == out.tensors["tsurf"].dtype and deficit.dim() == 2 and deficit.stride(1) == 1
             assert deficit.stride(0) == out.t_stride and deficit.shape[0] >= row + nrows
             d = C.c_void_p(deficit[row].data_ptr())
         lib.check(self.L.rs_hip_outputs_episodes(self._h, C.byref(o), d, int(nrows), int(index0), int(index_step),
-                                                 C.c_void_p(order.data_ptr()) if order is not None else None,
-                                                 C.byref(sp), C.c_void_p(acc.data_ptr()),
-                                                 C.c_void_p(stream.cuda_stream) if stream is not None else None),
-                  "rs_hip_outputs_episodes")
+                                                 _ptr(order), C.byref(sp), C.c_void_p(acc.data_ptr()),
+                                                 _stream_ptr(stream)), "rs_hip_outputs_episodes")
 
     def episodes_finish(self, spec, acc: torch.Tensor, stream: torch.cuda.Stream | None = None) -> None:
         """Close every point's open run (rs_hip_episodes_finish): what a consumer reads.  Idempotent."""
         sp, acc = self._episode_acc(spec, acc)
-        lib.check(self.L.rs_hip_episodes_finish(self._h, C.byref(sp), C.c_void_p(acc.data_ptr()),
-                                                C.c_void_p(stream.cuda_stream) if stream is not None else None),
+        lib.check(self.L.rs_hip_episodes_finish(self._h, C.byref(sp), C.c_void_p(acc.data_ptr()), _stream_ptr(stream)),
                   "rs_hip_episodes_finish")
 
     def episodes(self, acc: torch.Tensor):
@@ -393,8 +395,7 @@ class Plan:
             acc = torch.empty(shape, dtype=torch.float64, device=self.device)
         assert acc.dtype == torch.float64 and acc.shape == shape and acc.is_contiguous()
         lib.check(self.L.rs_hip_group_reset(self._h, C.c_void_p(acc.data_ptr()), int(nrows), C.byref(sp),
-                                            C.c_void_p(stream.cuda_stream) if stream is not None else None),
-                  "rs_hip_group_reset")
+                                            _stream_ptr(stream)), "rs_hip_group_reset")
         return acc
 
     def outputs_groups(self, out: "OutputWindow", nrows: int, group: torch.Tensor, spec, acc: torch.Tensor,
@@ -405,16 +406,11 @@ class Plan:
         groups.GroupSpec; ``order`` and ``stream`` as for ``outputs_by_point``."""
         assert acc.dtype == torch.float64 and acc.dim() == 3 and acc.is_contiguous()
         assert group.dtype == torch.int32 and group.numel() >= self.npoints and group.is_contiguous()
-        o = out.struct(0)
-        for n in OUT_FIELDS:
-            setattr(o, n, C.c_void_p(out.tensors[n][row].data_ptr()))
+        o = out.struct_from(row)
         sp = lib.group_spec(spec)
-        lib.check(self.L.rs_hip_outputs_groups(self._h, C.byref(o), int(nrows), C.c_void_p(group.data_ptr()),
-                                               C.c_void_p(order.data_ptr()) if order is not None else None,
-                                               C.byref(sp), C.c_void_p(acc.data_ptr()), int(acc.shape[0]),
-                                               int(acc_row0),
-                                               C.c_void_p(stream.cuda_stream) if stream is not None else None),
-                  "rs_hip_outputs_groups")
+        lib.check(self.L.rs_hip_outputs_groups(self._h, C.byref(o), int(nrows), C.c_void_p(group.data_ptr()), _ptr(order),
+                                               C.byref(sp), C.c_void_p(acc.data_ptr()), int(acc.shape[0]), int(acc_row0),
+                                               _stream_ptr(stream)), "rs_hip_outputs_groups")
 
     def groups(self, acc: torch.Tensor, spec=None):
         """``acc`` as the numpy array [rows, ngroups, cols] that groups.reduce_groups returns (synchronises)."""
@@ -438,9 +434,8 @@ class Plan:
         lib.check(self.L.rs_hip_gather_nodes(self._h, C.c_void_p(src.data_ptr()), int(src.shape[0]),
                                              int(src.shape[1] if n_nodes is None else n_nodes), int(src.stride(0)),
                                              C.c_void_p(node.data_ptr()), C.c_void_p(weight.data_ptr()),
-                                             int(node.shape[1]), C.c_void_p(order.data_ptr()) if order is not None else None,
-                                             float(present_above), float(missing), C.c_void_p(dst.data_ptr()),
-                                             int(dst.stride(0)), C.c_void_p(stream.cuda_stream) if stream is not None else None),
+                                             int(node.shape[1]), _ptr(order), float(present_above), float(missing),
+                                             C.c_void_p(dst.data_ptr()), int(dst.stride(0)), _stream_ptr(stream)),
                   "rs_hip_gather_nodes")
 
     def reset_order(self) -> None:

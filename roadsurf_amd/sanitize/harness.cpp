@@ -9,12 +9,16 @@
 //   phase 4  rs_driver_run_episodes, which rs_driver_run and its kin are calls of, with and without the summaries from
 //            three threads (shards, segment table, per-block worker threads, the blocks' merge into the one array of
 //            group series, the blocks' rows of the kept inputs, the deficit and the threshold episodes)
+//   phase 5  the device API's answers to its arguments, single-threaded and independent of the two arguments below:
+//            one accepted call per path and one rejected call per rejection of the step entry points and the row
+//            consumers, one line each between two marker lines (tests/golden/api_argument_record.txt)
 // usage: harness [threads=64] [points=640]      exit code 0 and "sanitize harness ok" when every call returned
 #include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <thread>
 #include <vector>
 
@@ -251,6 +255,345 @@ void driver_call(int n, int hours, bool coupling, bool gridded = false) {
   }
 }
 
+/* ---- phase 5: the device API's answers to its arguments -------------------------------------------------------------
+ * On the stub a "device" pointer is a host buffer: one zeroed block of doubles and one of int32 stand for every stream,
+ * row and accumulator (nothing computes, so nothing is written to them). */
+extern "C" long rs_stub_kernel_launches(void);
+
+/* one record line: entry point | case | status | kernel launches of the call | rs_last_error() after it.  A call that
+ * fails on purpose comes first, so that a call that leaves the thread's message alone reads "(untouched)" */
+template <class F>
+void api_call(const char *fn, const char *name, F &&call) {
+  rs_hip_sync(nullptr);
+  const std::string before = rs_last_error();
+  const long l0 = rs_stub_kernel_launches();
+  const int st = call();
+  const long launches = rs_stub_kernel_launches() - l0;
+  const std::string after = rs_last_error();
+  printf("%s | %s | status %d | launches %ld | %s\n", fn, name, st, launches, after == before ? "(untouched)" : after.c_str());
+}
+
+struct ApiArgs {
+  static constexpr int NP = 130, PAD = 256, L = 240; /* npoints < np_pad; SimLen */
+  std::vector<double> z = std::vector<double>((size_t)L * PAD, 0.0);
+  std::vector<int32_t> zi = std::vector<int32_t>((size_t)L * PAD, 0);
+  int fake_stream = 0;
+  void *stream() { return &fake_stream; }
+  RsPlan *plan(bool coupling, int bits) {
+    InputSettings s;
+    InputParameters p;
+    rs_default_settings(&s, L);
+    rs_default_parameters(&p, s.DTSecs);
+    s.use_relaxation = 1; /* (acts only where a call passes tair_relax) */
+    s.use_coupling = coupling ? 1 : 0;
+    RsConstants c;
+    int32_t status = -1;
+    rs_build_constants(&s, &p, &c, &status);
+    RsPlan *pl = status == 0 ? rs_hip_plan_create(0, NP, &c, nullptr) : nullptr;
+    if (pl && bits == 32 && rs_hip_set_precision(pl, 32) != 0) pl = nullptr;
+    if (!pl) {
+      fprintf(stderr, "phase 5: no plan: %s\n", rs_last_error());
+      g_errors++;
+    }
+    return pl;
+  }
+  RsForcing forcing(bool full = false, bool sky = false) {
+    RsForcing f;
+    std::memset(&f, 0, sizeof(f));
+    f.tair = f.vz = f.rhz = f.prec = f.sw = f.lw = z.data();
+    f.precphase = f.hour = zi.data();
+    f.t_stride = PAD;
+    if (full) f.tdew = z.data();
+    if (sky) f.sw_dir = f.lw_net = f.sun = z.data();
+    return f;
+  }
+  RsOutputs outputs() {
+    RsOutputs o;
+    std::memset(&o, 0, sizeof(o));
+    o.tsurf = o.snow = o.water = o.ice = o.deposit = o.ice2 = z.data();
+    o.t_stride = PAD;
+    o.decimate = 1;
+    return o;
+  }
+  RsPointParams params(bool sky = false, bool coupling = false) {
+    RsPointParams pp;
+    std::memset(&pp, 0, sizeof(pp));
+    pp.tbottom = z.data();
+    if (sky) pp.sky_view = pp.sin_lat = pp.cos_lat = pp.lon_rad = z.data();
+    if (coupling) {
+      pp.coupling_index = zi.data();
+      pp.coupling_tsurf = z.data();
+    }
+    return pp;
+  }
+};
+
+void api_step_cases(ApiArgs &A, RsPlan *pa, RsPlan *pb, RsPlan *pc, RsPlan *pd) {
+  const char *fn = "rs_hip_step";
+  auto step = [&](const char *name, RsPlan *pl, RsForcing f, RsOutputs o, RsPointParams pp, int t0 = 1, int ns = ApiArgs::L) {
+    api_call(fn, name, [&] { return rs_hip_step(pl, &f, &o, &pp, t0, ns); });
+  };
+  auto accepted = [&](const char *suffix) {
+    const std::string s = suffix;
+    step(("LEAN" + s).c_str(), pa, A.forcing(), A.outputs(), A.params());
+    step(("FULL" + s).c_str(), pa, A.forcing(true), A.outputs(), A.params());
+    step(("sky view" + s).c_str(), pa, A.forcing(true, true), A.outputs(), A.params(true));
+    step(("coupled whole series" + s).c_str(), pb, A.forcing(true), A.outputs(), A.params(false, true));
+  };
+  accepted("");
+  step("fp32 LEAN", pc, A.forcing(), A.outputs(), A.params());
+  step("fp32 coupled whole series", pd, A.forcing(true), A.outputs(), A.params(false, true));
+  step("a window inside the series, decimated", pa, A.forcing(), [&] { RsOutputs o = A.outputs(); o.decimate = 4; o.row0 = 3; return o; }(),
+       A.params(), 11, 50);
+  /* one thing wrong each */
+  step("null plan", nullptr, A.forcing(), A.outputs(), A.params());
+  { RsForcing f = A.forcing(); f.hour = nullptr; step("forcing without hour", pa, f, A.outputs(), A.params()); }
+  { RsForcing f = A.forcing(); f.t_stride = ApiArgs::NP - 1; step("forcing t_stride below npoints", pa, f, A.outputs(), A.params()); }
+  { RsPointParams pp = A.params(); pp.tbottom = nullptr; step("no tbottom", pa, A.forcing(), A.outputs(), pp); }
+  { RsOutputs o = A.outputs(); o.ice2 = nullptr; step("output without ice2", pa, A.forcing(), o, A.params()); }
+  { RsOutputs o = A.outputs(); o.t_stride = ApiArgs::NP - 1; step("output t_stride below npoints", pa, A.forcing(), o, A.params()); }
+  { RsOutputs o = A.outputs(); o.decimate = 0; step("decimate 0", pa, A.forcing(), o, A.params()); }
+  step("t0 = 0", pa, A.forcing(), A.outputs(), A.params(), 0, 10);
+  { RsOutputs o = A.outputs(); o.row0 = 1; step("row0 beyond the first row", pa, A.forcing(), o, A.params()); }
+  { RsPointParams pp = A.params(); pp.tair_relax = A.z.data(); step("tair_relax alone", pa, A.forcing(), A.outputs(), pp); }
+  { RsForcing f = A.forcing(true, true); f.sun = nullptr; step("sky view without sun", pa, f, A.outputs(), A.params(true)); }
+  { RsForcing f = A.forcing(true, true); f.hour_pstride = 1; step("sky view with per-point hours", pa, f, A.outputs(), A.params(true)); }
+  { RsPointParams pp = A.params(false, true); pp.coupling_tsurf = nullptr; step("coupling without coupling_tsurf", pb, A.forcing(true), A.outputs(), pp); }
+  step("coupling over part of the series", pb, A.forcing(true), A.outputs(), A.params(false, true), 1, 10);
+  step("coupled plan without coupling_index", pb, A.forcing(true), A.outputs(), A.params());
+  if (RsPlan *pe = A.plan(false, 64)) { /* diagnostics switched on while fp64, then the plan made an fp32 one */
+    if (rs_hip_set_diagnostics(pe, 1) != 0 || rs_hip_set_precision(pe, 32) != 0) g_errors++;
+    step("fp32 with diagnostics", pe, A.forcing(), A.outputs(), A.params());
+    rs_hip_plan_destroy(pe);
+  }
+  if (rs_hip_set_writeback(pc, A.z.data(), A.z.data(), A.z.data(), ApiArgs::PAD) != 0) g_errors++;
+  step("fp32 sky view with write-back", pc, A.forcing(true, true), A.outputs(), A.params(true));
+  if (rs_hip_set_writeback(pc, nullptr, nullptr, nullptr, 0) != 0) g_errors++;
+  /* timed: the accepted calls once more and a rejected one, which must leave the event pairs alone */
+  if (rs_hip_timing_reset(pa) != 0 || rs_hip_timing_reset(pb) != 0) g_errors++;
+  accepted(", timed");
+  { RsOutputs o = A.outputs(); o.decimate = 0; step("decimate 0, timed", pa, A.forcing(), o, A.params()); }
+}
+
+void api_knots_cases(ApiArgs &A, RsPlan *pa, RsPlan *pb, RsPlan *pc) {
+  const char *fn = "rs_hip_step_knots";
+  RsSynthSpec spec;
+  std::memset(&spec, 0, sizeof(spec));
+  spec.steps_per_knot = 120;
+  auto step = [&](const char *name, RsPlan *pl, RsSynthSpec sp, const double *knots, int nknots, RsOutputs o, RsPointParams pp,
+                  int t0 = 1, int ns = ApiArgs::L) {
+    api_call(fn, name, [&] { return rs_hip_step_knots(pl, &sp, knots, 0, nknots, &o, &pp, t0, ns); });
+  };
+  const double *k = A.z.data();
+  auto full = [&] { RsPointParams pp = A.params(); pp.initlen = A.zi.data(); return pp; };
+  step("LEAN, timed", pa, spec, k, 3, A.outputs(), A.params());
+  step("FULL, timed", pa, spec, k, 3, A.outputs(), full());
+  step("fp32 LEAN", pc, spec, k, 3, A.outputs(), A.params());
+  step("no knots", pa, spec, nullptr, 3, A.outputs(), A.params());
+  { RsPointParams pp = A.params(); pp.tbottom = nullptr; step("no tbottom", pa, spec, k, 3, A.outputs(), pp); }
+  { RsOutputs o = A.outputs(); o.tsurf = nullptr; step("output without tsurf", pa, spec, k, 3, o, A.params()); }
+  { RsOutputs o = A.outputs(); o.t_stride = ApiArgs::NP - 1; step("output t_stride below npoints", pa, spec, k, 3, o, A.params()); }
+  { RsOutputs o = A.outputs(); o.decimate = 0; step("decimate 0", pa, spec, k, 3, o, A.params()); }
+  step("window beyond SimLen", pa, spec, k, 3, A.outputs(), A.params(), 2, ApiArgs::L);
+  { RsSynthSpec sp = spec; sp.steps_per_knot = 0; step("steps_per_knot 0", pa, sp, k, 3, A.outputs(), A.params()); }
+  step("too few knots", pa, spec, k, 2, A.outputs(), A.params());
+  { RsOutputs o = A.outputs(); o.row0 = 1; step("row0 beyond the first row", pa, spec, k, 3, o, A.params()); }
+  step("sky view", pa, spec, k, 3, A.outputs(), A.params(true));
+  step("coupling", pb, spec, k, 3, A.outputs(), A.params(false, true));
+  { RsPointParams pp = full(); pp.tair_relax = pp.vz_relax = A.z.data(); step("relaxation without rh_relax", pa, spec, k, 3, A.outputs(), pp); }
+}
+
+/* rs_hip_step_cpl and rs_hip_cpl_replay share their checks: the same cases through both */
+void api_cpl_cases(ApiArgs &A, RsPlan *pa, RsPlan *pb, RsPlan *pd, bool replay) {
+  const char *fn = replay ? "rs_hip_cpl_replay" : "rs_hip_step_cpl";
+  auto step = [&](const char *name, RsPlan *pl, RsForcing f, RsOutputs o, RsPointParams pp, int t0 = 1, int ns = 100) {
+    api_call(fn, name, [&] {
+      int32_t rounds = -1;
+      return replay ? rs_hip_cpl_replay(pl, &f, &o, &pp, t0, ns, &rounds) : rs_hip_step_cpl(pl, &f, &o, &pp, t0, ns);
+    });
+  };
+  if (replay) {
+    unsetenv("ROADSURF_HIP_CPL_REPLAY");
+    step("ROADSURF_HIP_CPL_REPLAY unset", pb, A.forcing(true), A.outputs(), A.params(false, true));
+    setenv("ROADSURF_HIP_CPL_REPLAY", "general", 1);
+    step("ROADSURF_HIP_CPL_REPLAY=general", pb, A.forcing(true), A.outputs(), A.params(false, true));
+    setenv("ROADSURF_HIP_CPL_REPLAY", "lockstep", 1);
+    step("ROADSURF_HIP_CPL_REPLAY=lockstep", pb, A.forcing(true), A.outputs(), A.params(false, true));
+    unsetenv("ROADSURF_HIP_CPL_REPLAY");
+    step("a block that ends at SimLen", pb, A.forcing(true), A.outputs(), A.params(false, true), 141, 100);
+  } else {
+    step("a chunk", pb, A.forcing(true), A.outputs(), A.params(false, true));
+    step("the last chunk", pb, A.forcing(true), A.outputs(), A.params(false, true), 141, 100);
+  }
+  step("sky view", pb, A.forcing(true, true), A.outputs(), A.params(true, true));
+  step("null plan", nullptr, A.forcing(true), A.outputs(), A.params(false, true));
+  { RsForcing f = A.forcing(true); f.tair = nullptr; step("forcing without tair", pb, f, A.outputs(), A.params(false, true)); }
+  { RsForcing f = A.forcing(true); f.t_stride = ApiArgs::NP - 1; step("forcing t_stride below npoints", pb, f, A.outputs(), A.params(false, true)); }
+  { RsPointParams pp = A.params(false, true); pp.coupling_tsurf = nullptr; step("no coupling_tsurf", pb, A.forcing(true), A.outputs(), pp); }
+  step("plan without coupling", pa, A.forcing(true), A.outputs(), A.params(false, true));
+  step("fp32 plan", pd, A.forcing(true), A.outputs(), A.params(false, true));
+  { RsForcing f = A.forcing(true, true); f.lw_net = nullptr; step("sky view without lw_net", pb, f, A.outputs(), A.params(true, true)); }
+  { RsForcing f = A.forcing(true, true); f.hour_pstride = 1; step("sky view with per-point hours", pb, f, A.outputs(), A.params(true, true)); }
+  if (rs_hip_set_writeback(pb, A.z.data(), A.z.data(), A.z.data(), ApiArgs::PAD) != 0) g_errors++;
+  step("sky view with write-back", pb, A.forcing(true, true), A.outputs(), A.params(true, true));
+  if (rs_hip_set_writeback(pb, nullptr, nullptr, nullptr, 0) != 0) g_errors++;
+  { RsPointParams pp = A.params(false, true); pp.tair_relax = pp.vz_relax = pp.rh_relax = A.z.data(); step("relaxation without initlen", pb, A.forcing(true), A.outputs(), pp); }
+  { RsOutputs o = A.outputs(); o.water = nullptr; step("output without water", pb, A.forcing(true), o, A.params(false, true)); }
+  { RsOutputs o = A.outputs(); o.t_stride = ApiArgs::NP - 1; step("output t_stride below npoints", pb, A.forcing(true), o, A.params(false, true)); }
+  { RsOutputs o = A.outputs(); o.decimate = 0; step("decimate 0", pb, A.forcing(true), o, A.params(false, true)); }
+  step("nsteps = 0", pb, A.forcing(true), A.outputs(), A.params(false, true), 1, 0);
+}
+
+void api_consumer_cases(ApiArgs &A, RsPlan *pa, RsPlan *pc) {
+  double *z = A.z.data();
+  const int32_t *order = A.zi.data();
+  const int NP = ApiArgs::NP;
+  auto short_rows = [&] { RsOutputs o = A.outputs(); o.t_stride = NP - 1; return o; };
+  auto no_snow = [&] { RsOutputs o = A.outputs(); o.snow = nullptr; return o; };
+  {
+    const char *fn = "rs_hip_outputs_by_point";
+    double *dst[6] = {z, z, z, z, z, z};
+    auto call = [&](const char *name, RsPlan *pl, RsOutputs o, int nrows, const int32_t *ord, double *const *d, void *st) {
+      api_call(fn, name, [&] { return rs_hip_outputs_by_point(pl, &o, nrows, ord, d, 8, 2, st); });
+    };
+    call("the plan's order (made here)", pa, A.outputs(), 4, nullptr, dst, nullptr);
+    call("the plan's order", pa, A.outputs(), 4, nullptr, dst, nullptr);
+    call("a kept order row on a stream of the caller's", pa, A.outputs(), 4, order, dst, A.stream());
+    call("nrows = 0", pa, A.outputs(), 0, order, dst, nullptr);
+    call("rows beyond dst_rows", pa, A.outputs(), 7, order, dst, nullptr);
+    call("fp32 plan", pc, A.outputs(), 4, order, dst, nullptr);
+    call("source without snow", pa, no_snow(), 4, order, dst, nullptr);
+    { double *d2[6] = {z, z, z, nullptr, z, z}; call("destination without ice", pa, A.outputs(), 4, order, d2, nullptr); }
+    call("t_stride below npoints", pa, short_rows(), 4, order, dst, nullptr);
+    call("a stream of the caller's without an order row", pa, A.outputs(), 4, nullptr, dst, A.stream());
+  }
+  {
+    api_call("rs_hip_summary_reset", "the plan's stream", [&] { return rs_hip_summary_reset(pa, z, nullptr); });
+    api_call("rs_hip_summary_reset", "a stream of the caller's", [&] { return rs_hip_summary_reset(pa, z, A.stream()); });
+    api_call("rs_hip_summary_reset", "no accumulator", [&] { return rs_hip_summary_reset(pa, nullptr, nullptr); });
+    const char *fn = "rs_hip_outputs_summary";
+    RsSummarySpec spec;
+    std::memset(&spec, 0, sizeof(spec));
+    auto call = [&](const char *name, RsPlan *pl, RsOutputs o, int index0, const int32_t *ord, void *st) {
+      api_call(fn, name, [&] { return rs_hip_outputs_summary(pl, &o, 4, index0, 1, ord, &spec, z, st); });
+    };
+    call("the plan's order", pa, A.outputs(), 1, nullptr, nullptr);
+    call("a kept order row on a stream of the caller's", pa, A.outputs(), 1, order, A.stream());
+    call("fp32 plan", pc, A.outputs(), 1, order, nullptr);
+    call("index0 = 0", pa, A.outputs(), 0, order, nullptr);
+    call("source without snow", pa, no_snow(), 1, order, nullptr);
+    call("t_stride below npoints", pa, short_rows(), 1, order, nullptr);
+    call("a stream of the caller's without an order row", pa, A.outputs(), 1, nullptr, A.stream());
+  }
+  {
+    RsGroupSpec spec, bad;
+    std::memset(&spec, 0, sizeof(spec));
+    spec.ngroups = 3;
+    spec.nedges = 2;
+    spec.edges[0] = -1.0;
+    spec.edges[1] = 1.0;
+    bad = spec;
+    bad.edges[1] = -2.0;
+    api_call("rs_hip_group_reset", "the plan's stream", [&] { return rs_hip_group_reset(pa, z, 8, &spec, nullptr); });
+    api_call("rs_hip_group_reset", "a stream of the caller's", [&] { return rs_hip_group_reset(pa, z, 8, &spec, A.stream()); });
+    api_call("rs_hip_group_reset", "acc_rows = 0", [&] { return rs_hip_group_reset(pa, z, 0, &spec, nullptr); });
+    api_call("rs_hip_group_reset", "edges not increasing", [&] { return rs_hip_group_reset(pa, z, 8, &bad, nullptr); });
+    const char *fn = "rs_hip_outputs_groups";
+    auto call = [&](const char *name, RsPlan *pl, RsOutputs o, const int32_t *group, const RsGroupSpec &sp, int64_t acc_row0,
+                    const int32_t *ord, void *st) {
+      api_call(fn, name, [&] { return rs_hip_outputs_groups(pl, &o, 4, group, ord, &sp, z, 8, acc_row0, st); });
+    };
+    call("the plan's order", pa, A.outputs(), order, spec, 2, nullptr, nullptr);
+    call("a kept order row on a stream of the caller's", pa, A.outputs(), order, spec, 2, order, A.stream());
+    call("fp32 plan", pc, A.outputs(), order, spec, 2, order, nullptr);
+    call("no group row", pa, A.outputs(), nullptr, spec, 2, order, nullptr);
+    call("edges not increasing", pa, A.outputs(), order, bad, 2, order, nullptr);
+    call("rows beyond acc_rows", pa, A.outputs(), order, spec, 5, order, nullptr);
+    call("source without snow", pa, no_snow(), order, spec, 2, order, nullptr);
+    call("t_stride below npoints", pa, short_rows(), order, spec, 2, order, nullptr);
+    call("a stream of the caller's without an order row", pa, A.outputs(), order, spec, 2, nullptr, A.stream());
+  }
+  {
+    RsEpisodeSpec spec, bad, with_deficit;
+    std::memset(&spec, 0, sizeof(spec));
+    spec.use = 1;
+    spec.min_rows = 1;
+    spec.max_episodes = 3;
+    for (int k = 0; k < RS_EPI_VARS; ++k) { spec.above[k] = -HUGE_VAL; spec.below[k] = k == 0 ? 0.0 : HUGE_VAL; }
+    bad = spec;
+    bad.max_episodes = 0;
+    with_deficit = spec;
+    with_deficit.use = 1 | (1 << 6);
+    for (int fin = 0; fin < 2; ++fin) {
+      const char *fn = fin ? "rs_hip_episodes_finish" : "rs_hip_episodes_reset";
+      auto call = [&](const char *name, const RsEpisodeSpec *sp, double *acc, void *st) {
+        api_call(fn, name, [&] { return fin ? rs_hip_episodes_finish(pa, sp, acc, st) : rs_hip_episodes_reset(pa, sp, acc, st); });
+      };
+      call("the plan's stream", &spec, z, nullptr);
+      call("a stream of the caller's", &spec, z, A.stream());
+      call("no accumulator", &spec, nullptr, nullptr);
+      call("max_episodes = 0", &bad, z, nullptr);
+    }
+    const char *fn = "rs_hip_outputs_episodes";
+    auto call = [&](const char *name, RsPlan *pl, RsOutputs o, const void *deficit, int index_step, const RsEpisodeSpec &sp,
+                    const int32_t *ord, void *st) {
+      api_call(fn, name, [&] { return rs_hip_outputs_episodes(pl, &o, deficit, 4, 1, index_step, ord, &sp, z, st); });
+    };
+    call("the plan's order", pa, A.outputs(), nullptr, 1, spec, nullptr, nullptr);
+    call("a kept order row on a stream of the caller's, with the deficit", pa, A.outputs(), z, 1, with_deficit, order, A.stream());
+    call("fp32 plan", pc, A.outputs(), nullptr, 1, spec, order, nullptr);
+    call("index_step = 0", pa, A.outputs(), nullptr, 0, spec, order, nullptr);
+    call("max_episodes = 0", pa, A.outputs(), nullptr, 1, bad, order, nullptr);
+    call("a spec that tests the deficit, without one", pa, A.outputs(), nullptr, 1, with_deficit, order, nullptr);
+    call("source without snow", pa, no_snow(), nullptr, 1, spec, order, nullptr);
+    call("t_stride below npoints", pa, short_rows(), nullptr, 1, spec, order, nullptr);
+    call("a stream of the caller's without an order row", pa, A.outputs(), nullptr, 1, spec, nullptr, A.stream());
+  }
+  {
+    const char *fn = "rs_hip_gather_nodes";
+    auto call = [&](const char *name, const double *src, int stencil, int64_t src_stride, int64_t dst_stride, const int32_t *ord,
+                    void *st) {
+      api_call(fn, name, [&] {
+        return rs_hip_gather_nodes(pa, src, 4, 100, src_stride, order, z, stencil, ord, -100.0, -9999.9, z, dst_stride, st);
+      });
+    };
+    call("the plan's order", z, 2, 100, ApiArgs::PAD, nullptr, nullptr);
+    call("a kept order row on a stream of the caller's", z, 2, 100, ApiArgs::PAD, order, A.stream());
+    call("no source", nullptr, 2, 100, ApiArgs::PAD, order, nullptr);
+    call("stencil = 0", z, 0, 100, ApiArgs::PAD, order, nullptr);
+    call("src_stride below n_nodes", z, 2, 99, ApiArgs::PAD, order, nullptr);
+    call("dst_stride below npoints", z, 2, 100, NP - 1, order, nullptr);
+    call("a stream of the caller's without an order row", z, 2, 100, ApiArgs::PAD, nullptr, A.stream());
+  }
+}
+
+void api_argument_phase() {
+  ApiArgs A;
+  RsPlan *pa = A.plan(false, 64), *pb = A.plan(true, 64), *pc = A.plan(false, 32), *pd = A.plan(true, 32);
+  if (!pa || !pb || !pc || !pd) return;
+  if (rs_hip_plan_npoints(pa) != ApiArgs::NP || rs_hip_plan_state_bytes(pa) % ((size_t)ApiArgs::PAD * sizeof(double)) != 0) {
+    fprintf(stderr, "phase 5: the plan's padding is not %d\n", ApiArgs::PAD);
+    g_errors++;
+  }
+  printf("phase 5: the device API's answers to its arguments: begin\n");
+  api_consumer_cases(A, pa, pc); /* first: the first of them makes the plan's order row */
+  api_step_cases(A, pa, pb, pc, pd); /* leaves the timing of pa and pb on */
+  api_knots_cases(A, pa, pb, pc);
+  api_cpl_cases(A, pa, pb, pd, false);
+  api_cpl_cases(A, pa, pb, pd, true);
+  RsPlan *timed[2] = {pa, pb};
+  for (int k = 0; k < 2; ++k) {
+    int32_t n = -1;
+    const double ms = rs_hip_timing_step_ms(timed[k], &n);
+    printf("rs_hip_timing_step_ms | %s | nlaunches %d | %s\n", k ? "the coupled plan" : "the default plan", n, ms >= 0.0 ? "ok" : "failed");
+  }
+  printf("phase 5: the device API's answers to its arguments: end\n");
+  rs_hip_plan_destroy(pa);
+  rs_hip_plan_destroy(pb);
+  rs_hip_plan_destroy(pc);
+  rs_hip_plan_destroy(pd);
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -288,6 +631,7 @@ int main(int argc, char **argv) {
     for (auto &x : th) x.join();
   }
   printf("phase 4: concurrent rs_driver_run calls done\n");
+  api_argument_phase();
   if (g_errors.load() != 0) {
     printf("sanitize harness: %d calls failed\n", g_errors.load());
     return 1;

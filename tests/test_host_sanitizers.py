@@ -8,7 +8,12 @@ it the way the reference driver's worker pool drives `runsimulation` (examples/e
 64 caller threads, two groups of settings, the coalescer limited to 5 callers per batch (ROADSURF_HIP_COALESCE_MAX
 < threads), short-lived threads whose caches are adopted, concurrent runsimulation_batch_ex calls of four sizes and
 two concurrent rs_driver_run calls (shards, segment table, one worker thread per block).  Results mean nothing on
-that device; a race, a use-after-free or an out-of-bounds access of the host code fails the test.  No GPU needed."""
+that device; a race, a use-after-free or an out-of-bounds access of the host code fails the test.  No GPU needed.
+
+The harness's last phase is single-threaded: the device API's answers to its arguments - one accepted call per path
+and one rejected call per rejection of the step entry points and the row consumers, a line each with the status, the
+number of kernel launches and the message.  tests/golden/api_argument_record.txt holds those lines; the ASan + UBSan
+run below must print them unchanged."""
 import os
 import subprocess
 
@@ -55,3 +60,12 @@ def test_host_side_is_clean_under_address_and_undefined_behaviour_sanitizers():
     rc, out = _run(exe, {"ASAN_OPTIONS": "detect_leaks=0", "UBSAN_OPTIONS": "print_stacktrace=1"})
     assert "ERROR: AddressSanitizer" not in out and "runtime error" not in out, out[-6000:]
     assert rc == 0 and "sanitize harness ok" in out, out[-3000:]
+    # the device API's answers to its arguments, line for line as recorded
+    lines = out.splitlines()
+    marks = [k for k, l in enumerate(lines) if l.startswith("phase 5: the device API's answers to its arguments: ")]
+    assert len(marks) == 2 and lines[marks[0]].endswith("begin") and lines[marks[1]].endswith("end"), out[-3000:]
+    got = lines[marks[0] + 1:marks[1]]
+    want = open(os.path.join(ROOT, "tests", "golden", "api_argument_record.txt")).read().splitlines()
+    diff = [(k + 1, w, g) for k, (w, g) in enumerate(zip(want, got)) if w != g]
+    assert not diff, "record line %d\n  recorded: %s\n  printed:  %s\n(%d lines differ)" % (diff[0] + (len(diff),))
+    assert len(got) == len(want) and len(want) > 100, (len(got), len(want))

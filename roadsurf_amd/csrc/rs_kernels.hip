@@ -56,22 +56,6 @@ __device__ __forceinline__ const ConstsAS &consts_of(Args a) {
   return *(const ConstsAS *)a->consts;
 }
 
-template <int NL>
-struct RegProfile {
-  double v[NL];
-  static constexpr bool kUnrolled = true; /* the layer count is a compile-time constant */
-  __device__ __forceinline__ constexpr int nlayers() const { return NL; }
-  __device__ __forceinline__ double get(int j) const { return v[j - 1]; }
-  __device__ __forceinline__ void set(int j, double x) { v[j - 1] = x; }
-  /* "the new profile exists here": without it the compiler sinks the update of the layers nothing in
-   * the rest of the step reads (3..N) behind the storages into the loop latch, where the layer
-   * constants no longer fit the scalar registers (124 v_readlane/v_writelane per step) */
-  __device__ __forceinline__ void pin() {
-#pragma unroll
-    for (int j = 0; j < NL; ++j) asm volatile("" : "+v"(v[j]));
-  }
-};
-
 /* The upper NREG layers in registers, the rest in LDS columns: what lets the FULL feature set (more
  * live values than the LEAN one) keep four waves per SIMD without scratch spills.  Layer indices are
  * compile-time constants after unrolling, so the split costs no selects. */
@@ -91,72 +75,6 @@ struct HybridProfile {
     for (int j = 0; j < NREG; ++j) asm volatile("" : "+v"(v[j]));
   }
 };
-
-struct LdsProfile {
-  double *col; /* &lds[threadIdx.x]; layer stride = kBlock doubles */
-  int n;
-  static constexpr bool kUnrolled = false;
-  __device__ __forceinline__ int nlayers() const { return n; }
-  __device__ __forceinline__ double get(int j) const { return col[(j - 1) * kBlock]; }
-  __device__ __forceinline__ void set(int j, double x) { col[(j - 1) * kBlock] = x; }
-  __device__ __forceinline__ void pin() {}
-};
-
-template <bool FULL, class Prof>
-__device__ __forceinline__ void load_state(const double *__restrict__ st, int64_t np, int64_t p,
-                                           Prof &T, Scalars &s) {
-  const int N = T.nlayers();
-#pragma unroll
-  for (int j = 1; j <= N; ++j) T.set(j, st[(int64_t)(RS_ST_TMP0 + j - 1) * np + p]);
-  s.tnw1 = st[(int64_t)RS_ST_TNW1 * np + p];
-  s.tnw2 = st[(int64_t)RS_ST_TNW2 * np + p];
-  s.tsurf = st[(int64_t)RS_ST_TSURF * np + p];
-  s.wat = st[(int64_t)RS_ST_WAT * np + p];
-  s.snow = st[(int64_t)RS_ST_SNOW * np + p];
-  s.ice = st[(int64_t)RS_ST_ICE * np + p];
-  s.ice2 = st[(int64_t)RS_ST_ICE2 * np + p];
-  s.dep = st[(int64_t)RS_ST_DEP * np + p];
-  s.q2melt = st[(int64_t)RS_ST_Q2MELT * np + p];
-  s.t4melt = st[(int64_t)RS_ST_T4MELT * np + p];
-  s.albedo = st[(int64_t)RS_ST_ALBEDO * np + p];
-  s.verycold = st[(int64_t)RS_ST_VERYCOLD * np + p] != 0.0;
-  s.failed = st[(int64_t)RS_ST_FAILED * np + p] != 0.0;
-  if (FULL) { /* relaxation anchors: untouched by the LEAN variant */
-    s.tair_end = st[(int64_t)RS_ST_TAIR_END * np + p];
-    s.vz_end = st[(int64_t)RS_ST_VZ_END * np + p];
-    s.rh_end = st[(int64_t)RS_ST_RH_END * np + p];
-  } else {
-    s.tair_end = s.vz_end = s.rh_end = 0.0;
-  }
-}
-
-/* ANCHORS: the relaxation anchors are part of the Scalars (the general coupled kernel); the
- * lock-step loop writes them to the state block at the index that sets them and carries differences */
-template <bool FULL, class Prof, bool ANCHORS = false>
-__device__ __forceinline__ void store_state(double *__restrict__ st, int64_t np, int64_t p,
-                                            const Prof &T, const Scalars &s) {
-  const int N = T.nlayers();
-#pragma unroll
-  for (int j = 1; j <= N; ++j) st[(int64_t)(RS_ST_TMP0 + j - 1) * np + p] = T.get(j);
-  st[(int64_t)RS_ST_TNW1 * np + p] = s.tnw1;
-  st[(int64_t)RS_ST_TNW2 * np + p] = s.tnw2;
-  st[(int64_t)RS_ST_TSURF * np + p] = s.tsurf;
-  st[(int64_t)RS_ST_WAT * np + p] = s.wat;
-  st[(int64_t)RS_ST_SNOW * np + p] = s.snow;
-  st[(int64_t)RS_ST_ICE * np + p] = s.ice;
-  st[(int64_t)RS_ST_ICE2 * np + p] = s.ice2;
-  st[(int64_t)RS_ST_DEP * np + p] = s.dep;
-  st[(int64_t)RS_ST_Q2MELT * np + p] = s.q2melt;
-  st[(int64_t)RS_ST_T4MELT * np + p] = s.t4melt;
-  st[(int64_t)RS_ST_ALBEDO * np + p] = s.albedo;
-  st[(int64_t)RS_ST_VERYCOLD * np + p] = s.verycold ? 1.0 : 0.0;
-  /* RS_ST_FAILED is written where the failure is detected (the index it happened at) */
-  if (FULL && ANCHORS) {
-    st[(int64_t)RS_ST_TAIR_END * np + p] = s.tair_end;
-    st[(int64_t)RS_ST_VZ_END * np + p] = s.vz_end;
-    st[(int64_t)RS_ST_RH_END * np + p] = s.rh_end;
-  }
-}
 
 /* The kernel arguments are read through the kernarg segment pointer (constant
  * address space: scalar loads) and that pointer is laundered once per time
@@ -267,23 +185,6 @@ __device__ __forceinline__ Forcing load_forcing(KernArgs ka, int64_t row0, uint3
   return o;
 }
 
-/* Output row of time index i: false when the decimation skips it.  UNI: the index is the same in
- * every lane (lock-step kernels) and the row is formed once per step, ahead of the divergent
- * branches, so that it stays in scalar registers (a row computed at each store site is merged by
- * the compiler into a per-lane value). */
-template <bool UNI>
-__device__ __forceinline__ bool output_row(KernArgs ka, int32_t i, int64_t &row) {
-  int32_t r = i - 1;
-  const int32_t dec = ka->o.decimate;
-  if (dec > 1) {
-    if (r % dec != 0) return false;
-    r /= dec;
-  }
-  if (UNI) r = __builtin_amdgcn_readfirstlane(r);
-  row = ((int64_t)r - ka->o.row0) * ka->o.t_stride;
-  return true;
-}
-
 template <bool SCATTER = false, bool A32 = false>
 __device__ __forceinline__ void store_outputs(KernArgs ka, int64_t row, int64_t row0, uint32_t lane,
                                               const Scalars &s, bool valid) {
@@ -318,155 +219,30 @@ __device__ __forceinline__ void store_outputs(KernArgs ka, int64_t row, int64_t 
   L.st(ka->o.ice2 + row, valid ? s.ice2 : miss);
 }
 
-/* ---- coupling: src/Coupling.f90 -------------------------------------------------
- * Per-point state machine that re-runs the point's coupling window with a scaled
- * short- or long-wave input until the simulated surface temperature at the end of
- * the window matches the last observation (secant / halving / doubling, <= 25
- * replays).  On the device every lane carries its OWN time index: a replay sets it
- * back to the window start (src/Coupling.f90:61-78), so forcing reads and output
- * writes are per-lane gathers/scatters into the (whole-series) windows, and a wave
- * runs until its slowest lane is through.  The saved state of
- * saveDataForCoupling (:172-210) is parked in the HBM state block. */
-struct Coupling {
-  double tabove, tbelow, radcoeff, rcabove, rcbelow, rcprev, swcof, lwcof, swcorr, lwcorr,
-      tend1, lastobs;
-  int32_t iter, cs, ce; /* Coupling_iterations, couplingStartI, couplingEndI */
-  int32_t msg;          /* bits 3-4 of RS_ST_CPL_FLAGS: what Coupling_control has printed for the point (rs_state.h) */
-  bool again, failed, on;
-};
-
-/* Coupling_control, src/Coupling.f90:292-481 (called with Coupling_failed == .false.).
- * TsurfAve and LastTsurfObs make a round trip through Kelvin (+273.16, -273.16); the
- * rounding that leaves behind is part of the reference's result. */
-__device__ __forceinline__ void coupling_control(Coupling &q, double &tsurf) {
-  q.again = false;
-  tsurf = tsurf + R4(273.16);
-  q.lastobs = q.lastobs + R4(273.16);
-  if (q.iter == 0) q.tend1 = tsurf;
-  if (q.iter == 25) {
-    if (fabs(q.tend1 - q.lastobs) < fabs(tsurf - q.lastobs)) q.again = true;
-    q.swcof = R4(1.0); q.lwcof = R4(1.0); q.swcorr = R4(0.0); q.lwcorr = R4(0.0);
-    q.radcoeff = R4(1.0);
-    q.failed = true;
-  } else if (q.lastobs < -100) {
-    q.swcof = R4(1.0); q.lwcof = R4(1.0); q.swcorr = R4(0.0); q.lwcorr = R4(0.0);
-    q.radcoeff = R4(1.0);
-    q.failed = true;
-    q.again = true;
-  } else if (tsurf < R4(170.0) || tsurf > R4(400.0)) {
-    q.swcof = R4(1.0); q.lwcof = R4(1.0); q.swcorr = R4(0.0); q.lwcorr = R4(0.0);
-    q.failed = true;
-    q.again = true;
-    q.radcoeff = R4(1.0);
-  } else if (tsurf - q.lastobs > R4(0.1)) {
-    if (q.tabove < -100) {
-      q.tabove = tsurf;
-      q.rcabove = q.radcoeff;
-    } else if (q.tabove - q.lastobs > tsurf - q.lastobs) {
-      q.tabove = tsurf;
-      q.rcabove = q.radcoeff;
-    }
-    q.again = true;
-    if (q.tabove > -100 && q.tbelow > -100) {
-      const double da = q.tabove - q.lastobs, db = q.lastobs - q.tbelow;
-      q.radcoeff = q.rcabove - da / (da + db) * (q.rcabove - q.rcbelow);
-    } else {
-      q.radcoeff = R4(0.5) * q.radcoeff;
-    }
-    if (fabs(q.radcoeff - q.rcprev) < R4(0.00005)) {
-      q.tabove = -9999;
-      q.tbelow = -9999;
-    }
-    if (q.radcoeff < R4(0.01)) { /* "coupling coefficient too small, coupling failed" (:400-401) */
-      q.msg |= RS_CPL_MSG_SMALL;
-      q.radcoeff = R4(1.0);
-      q.failed = true;
-      q.swcof = R4(1.0); q.lwcof = R4(1.0); q.swcorr = R4(0.0); q.lwcorr = R4(0.0);
-    }
-    q.rcprev = q.radcoeff;
-  } else if (q.lastobs - tsurf > R4(0.1)) {
-    if (q.tbelow < -100) {
-      q.tbelow = tsurf;
-      q.rcbelow = q.radcoeff;
-    } else if (q.tbelow - q.lastobs < tsurf - q.lastobs) {
-      q.tbelow = tsurf;
-      q.rcbelow = q.radcoeff;
-    }
-    q.again = true;
-    if (q.tabove > -100 && q.tbelow > -100) {
-      const double da = q.tabove - q.lastobs, db = q.lastobs - q.tbelow;
-      q.radcoeff = q.rcabove - da / (da + db) * (q.rcabove - q.rcbelow);
-    } else {
-      q.radcoeff = R4(2.0) * q.radcoeff;
-    }
-    if (fabs(q.radcoeff - q.rcprev) < R4(0.00005)) {
-      q.tabove = -9999;
-      q.tbelow = -9999;
-    }
-    q.rcprev = q.radcoeff;
-  } else {
-    if (q.radcoeff > R4(3.0)) { /* "coupling coefficient too big, coupling failed" (:451-452) */
-      q.msg |= RS_CPL_MSG_BIG;
-      q.failed = true;
-      q.radcoeff = R4(1.0);
-      q.swcof = R4(1.0); q.lwcof = R4(1.0); q.swcorr = R4(0.0); q.lwcorr = R4(0.0);
-    }
-    q.swcorr = q.swcof - R4(1.0);
-    q.lwcorr = q.lwcof - R4(1.0);
-    q.failed = false;
-    q.iter = -1;
-    q.tabove = R4(-9999.0); q.tbelow = R4(-9999.0);
-    q.radcoeff = R4(1.0);
-    q.rcabove = R4(-9999.0); q.rcbelow = R4(-9999.0);
-    q.rcprev = R4(1.0);
-  }
-  tsurf = tsurf - R4(273.16);
-  q.lastobs = q.lastobs - R4(273.16);
+/* Per-lane gather of the forcing of absolute index i (window row i - t0). */
+__device__ __forceinline__ Forcing gather_forcing(KernArgs ka, int64_t p, int32_t i, int32_t t0) {
+  Forcing o;
+  const int64_t off = (int64_t)(i - t0) * ka->f.t_stride + p;
+  o.tair = ka->f.tair[off]; o.vz = ka->f.vz[off]; o.rhz = ka->f.rhz[off];
+  o.prec = ka->f.prec[off]; o.sw = ka->f.sw[off]; o.lw = ka->f.lw[off];
+  o.phase = ka->f.precphase[off];
+  o.hour = ka->f.hour_pstride ? ka->f.hour[off] : ka->f.hour[i - t0];
+  o.tdew = ka->f.tdew ? ka->f.tdew[off] : 0.0;
+  o.tsurfobs = ka->f.tsurfobs ? ka->f.tsurfobs[off] : R4(-9999.9);
+  o.depth = ka->f.depth ? ka->f.depth[off] : R4(-9999.9);
+  return o;
 }
 
-__device__ __forceinline__ void load_coupling(const double *st, int64_t np, int64_t p, Coupling &q) {
-  q.iter = (int32_t)st[(int64_t)RS_ST_CPL_ITER * np + p];
-  const int32_t fl = (int32_t)st[(int64_t)RS_ST_CPL_FLAGS * np + p];
-  q.again = fl & 1; q.failed = (fl >> 1) & 1; q.msg = fl & (RS_CPL_MSG_SMALL | RS_CPL_MSG_BIG);
-  q.tabove = st[(int64_t)RS_ST_CPL_TABOVE * np + p]; q.tbelow = st[(int64_t)RS_ST_CPL_TBELOW * np + p];
-  q.radcoeff = st[(int64_t)RS_ST_CPL_RADCOEFF * np + p];
-  q.rcabove = st[(int64_t)RS_ST_CPL_RCABOVE * np + p]; q.rcbelow = st[(int64_t)RS_ST_CPL_RCBELOW * np + p];
-  q.rcprev = st[(int64_t)RS_ST_CPL_RCPREV * np + p];
-  q.swcof = st[(int64_t)RS_ST_CPL_SWCOF * np + p]; q.lwcof = st[(int64_t)RS_ST_CPL_LWCOF * np + p];
-  q.swcorr = st[(int64_t)RS_ST_CPL_SWCORR * np + p]; q.lwcorr = st[(int64_t)RS_ST_CPL_LWCORR * np + p];
-  q.tend1 = st[(int64_t)RS_ST_CPL_TEND1 * np + p];
-  q.lastobs = st[(int64_t)RS_ST_CPL_LASTOBS * np + p];
+/* ... and of the two streams sky view adds */
+__device__ __forceinline__ void gather_sky(KernArgs ka, int64_t p, int32_t i, int32_t t0, double &sw_dir, double &lw_net) {
+  const int64_t off = (int64_t)(i - t0) * ka->f.t_stride + p;
+  sw_dir = ka->f.sw_dir[off];
+  lw_net = ka->f.lw_net[off];
 }
 
-__device__ __forceinline__ void store_coupling(double *st, int64_t np, int64_t p, const Coupling &q) {
-  st[(int64_t)RS_ST_CPL_ITER * np + p] = (double)q.iter;
-  const int32_t keep = ((int32_t)st[(int64_t)RS_ST_CPL_FLAGS * np + p]) & 4;
-  st[(int64_t)RS_ST_CPL_FLAGS * np + p] = (double)(keep | (q.again ? 1 : 0) | (q.failed ? 2 : 0) | q.msg);
-  st[(int64_t)RS_ST_CPL_TABOVE * np + p] = q.tabove; st[(int64_t)RS_ST_CPL_TBELOW * np + p] = q.tbelow;
-  st[(int64_t)RS_ST_CPL_RADCOEFF * np + p] = q.radcoeff;
-  st[(int64_t)RS_ST_CPL_RCABOVE * np + p] = q.rcabove; st[(int64_t)RS_ST_CPL_RCBELOW * np + p] = q.rcbelow;
-  st[(int64_t)RS_ST_CPL_RCPREV * np + p] = q.rcprev;
-  st[(int64_t)RS_ST_CPL_SWCOF * np + p] = q.swcof; st[(int64_t)RS_ST_CPL_LWCOF * np + p] = q.lwcof;
-  st[(int64_t)RS_ST_CPL_SWCORR * np + p] = q.swcorr; st[(int64_t)RS_ST_CPL_LWCORR * np + p] = q.lwcorr;
-  st[(int64_t)RS_ST_CPL_TEND1 * np + p] = q.tend1;
-  st[(int64_t)RS_ST_CPL_LASTOBS * np + p] = q.lastobs;
-}
-
-/* the stale TmpNw of a replay's first step, parked in the state block (one column per point) */
-struct GlobalProfile {
-  const double *col;
-  int64_t stride;
-  __device__ __forceinline__ double get(int j) const { return col[(int64_t)(j - 1) * stride]; }
-};
-
-__device__ __forceinline__ Forcing gather_forcing(KernArgs ka, int64_t p, int32_t i, int32_t t0);
-
-/* exp(-(DT*i - DT*couplingEndI)/couplingEffectReduction), src/Coupling.f90:80-88: from the plan's
- * table where the argument is a function of i - couplingEndI alone (rs_consts_dev.h), else here */
-__device__ __forceinline__ double cpl_decay(const ConstsAS &c, const MathTab &mt, int32_t i, int32_t ce) {
-  const uint32_t d = (uint32_t)(i - ce);
-  if (c.cpl_tab && d <= (uint32_t)c.SimLen) return ((const double *)c.cpl_tab)[d];
-  return rs_exp(mt, rs_div(-((c.DTSecs * i) - (c.DTSecs * ce)), c.cplReduction));
+/* SaveOutput for a lane with its own time index: the point's column of the index's row */
+__device__ __forceinline__ void store_point(KernArgs ka, int64_t row, int64_t p, const Scalars &s, bool valid) {
+  store_outputs<true>(ka, row, p, 0u, s, valid);
 }
 
 /* Diagnostics (rs_hip_set_diagnostics; ROADSURF_HIP_DIAGNOSTICS=1 on the host paths): what CalcBLCondAndLE prints
@@ -527,6 +303,9 @@ __device__ __attribute__((noinline)) void bl_diagnose(const ConstsAS *cp, const 
     dg[(int64_t)RS_DG_MAXIT_N * np + p] = n + 1.0;
   }
 }
+
+/* the profiles, state-block access, coupling, the general time loop and init_kernel: one text for both flavours */
+#include "rs_general_body.inc"
 
 /* The time loop of runsimulation (examples/example1/src/Simulation.f90:57-115)
  * for one point over absolute indices [t0, t0+nsteps). */
@@ -923,261 +702,6 @@ __device__ __forceinline__ void time_loop(const MathTab &mt, Prof &T, Scalars &s
     }
   }
   if (CPL) ka->state[(int64_t)RS_ST_CPL_RESUME * ka->np_pad + row0 + lane] = (double)next_i;
-}
-
-/* Per-lane gather of the forcing of absolute index i (window row i - t0). */
-__device__ __forceinline__ Forcing gather_forcing(KernArgs ka, int64_t p, int32_t i, int32_t t0) {
-  Forcing o;
-  const int64_t off = (int64_t)(i - t0) * ka->f.t_stride + p;
-  o.tair = ka->f.tair[off]; o.vz = ka->f.vz[off]; o.rhz = ka->f.rhz[off];
-  o.prec = ka->f.prec[off]; o.sw = ka->f.sw[off]; o.lw = ka->f.lw[off];
-  o.phase = ka->f.precphase[off];
-  o.hour = ka->f.hour_pstride ? ka->f.hour[off] : ka->f.hour[i - t0];
-  o.tdew = ka->f.tdew ? ka->f.tdew[off] : 0.0;
-  o.tsurfobs = ka->f.tsurfobs ? ka->f.tsurfobs[off] : R4(-9999.9);
-  o.depth = ka->f.depth ? ka->f.depth[off] : R4(-9999.9);
-  return o;
-}
-
-/* runsimulation's loop with coupling (examples/example1/src/Simulation.f90:57-115):
- * CheckValues -> CouplingOperations1 (may rewind i) -> SetCurrentValues -> relaxation ->
- * roadModelOneStep -> SaveOutput -> CheckEndCoupling. */
-template <class Prof, bool DIAG = false>
-__device__ __forceinline__ void time_loop_coupled(const MathTab &mt, Prof &T, Scalars &s,
-                                                  Coupling &q, double *st, int64_t np, int64_t p) {
-  KernArgs ka = kernargs();
-  const uint32_t lane = threadIdx.x;
-  const int64_t row0 = (int64_t)blockIdx.x * kBlock;
-  const ConstsAS &c = consts_of(ka);
-  const int N = T.nlayers();
-  const int32_t t0 = ka->t0, tend = ka->t0 + ka->nsteps;
-  const double tbot = ka->pp.tbottom[p];
-  const int32_t initlen = ka->pp.initlen ? ka->pp.initlen[p] : 0;
-  bool relax = false;
-  double tairR = 0, vzR = 0, rhR = 0;
-  if (c.use_relaxation && ka->pp.tair_relax) {
-    tairR = (double)(float)ka->pp.tair_relax[p];
-    vzR = (double)(float)ka->pp.vz_relax[p];
-    rhR = (double)(float)ka->pp.rh_relax[p];
-    relax = !(tairR < R4(-100.0) || tairR > R4(100.0) || vzR < R4(0.0) || vzR > R4(100.0) ||
-              rhR < R4(0.0) || rhR > 110);
-  }
-  /* setInputParam + initCouplingTimes, src/InputOutput.f90:30-36, src/Coupling.f90:486-534 */
-  const int32_t cidx = ka->pp.coupling_index ? ka->pp.coupling_index[p] : 0;
-  q.on = c.use_coupling && ka->pp.coupling_index &&
-         !(ka->pp.coupling_tsurf[p] < -100 || cidx < 1);
-  q.cs = -99; q.ce = -99;
-  if (q.on) {
-    q.ce = cidx;
-    q.cs = ((double)cidx <= c.cplLenR) ? 1 : cidx - c.cplLenI;
-  }
-  (void)lane; (void)row0;
-  /* sky view, examples/example1/src/Simulation.f90:154-156 */
-  double skyv = R4(1.0), sinlat = 0, coslat = 0, lonrad = 0, coslon = 1.0, sinlon = 0;
-  bool sky_on = false;
-  if (ka->pp.sky_view) {
-    skyv = ka->pp.sky_view[p];
-    sky_on = (skyv < R4(1.0) && skyv > R4(-0.01));
-    if (sky_on) {
-      sinlat = ka->pp.sin_lat[p];
-      coslat = ka->pp.cos_lat[p];
-      lonrad = ka->pp.lon_rad[p];
-      coslon = ::cos(lonrad);
-      sinlon = ::sin(lonrad);
-    }
-  }
-
-  auto fail_at = [&](int32_t idx) {
-    s.failed = true;
-    st[(int64_t)RS_ST_FAILED * np + p] = (double)idx;
-  };
-  /* rounds (rs_hip_step): the point resumes where it stopped; a parked point (resume = window
-   * end + 1, start_coupling_again set) rewinds to its window start in the first iteration */
-  const int32_t resume = (int32_t)st[(int64_t)RS_ST_CPL_RESUME * np + p];
-  int32_t i = resume > t0 ? resume : t0;
-  int32_t written_hi = i - 1; /* highest index the point has saved an output for */
-  bool stale_all = false; /* first step after a restore: TmpNw is the pre-restore profile */
-  /* the forcing of index i+1 is fetched in the middle of step i (a replay that rewinds fetches its
-   * row again): with two waves per SIMD a load issued at its point of use would stall every step */
-  Forcing nxt;
-  int32_t nxt_i = -1;
-  if (i < tend && !s.failed) {
-    nxt = gather_forcing(ka, p, i, t0);
-    nxt_i = i;
-  }
-  while (i < tend) {
-    if (s.failed) {
-      /* the reference's loop has exited: outputs it never saved stay -9999.0 - but a point
-       * that fails in the middle of a coupling replay keeps, beyond the failure, what the
-       * EARLIER passes saved there (src/InputOutput.f90:151-165 only ever overwrites) */
-      int64_t orow;
-      if (i > written_hi && output_row<false>(ka, i, orow)) store_outputs<true>(ka, orow, p, 0u, s, false);
-      ++i;
-      continue;
-    }
-    Forcing f = (nxt_i == i) ? nxt : gather_forcing(ka, p, i, t0);
-    if (i == 1 && f.vz < R4(0.4)) f.vz = R4(0.4);
-    CouplingInputs cp;
-    double sw_dir = 0.0, lw_net = 0.0;
-    if (ka->f.sw_dir) {
-      const int64_t off = (int64_t)(i - t0) * ka->f.t_stride + p;
-      sw_dir = ka->f.sw_dir[off];
-      lw_net = ka->f.lw_net[off];
-    }
-    if (i < c.SimLen) {
-      if (check_values(c, f, s.tsurf, ka->f.tdew != nullptr)) fail_at(i);
-      if (sky_on && (sw_dir < R4(-0.1) || sw_dir > R4(4000.0) || lw_net < R4(-1000.0) ||
-                     lw_net > R4(1000.0)))
-        fail_at(i); /* src/InputOutput.f90:68-74 */
-      if (sw_dir > f.sw) sw_dir = f.sw; /* :75-77 */
-      if (q.on) {
-        /* CouplingOperations1, src/Coupling.f90:10-96 */
-        bool in_phase = (i >= q.cs && i <= q.ce);
-        if (i == q.cs && q.iter == 0) {
-          /* saveDataForCoupling :172-210 */
-          st[(int64_t)RS_ST_CPL_SAVE_TSURF * np + p] = s.tsurf;
-          st[(int64_t)RS_ST_CPL_SAVE_WAT * np + p] = s.wat;
-          st[(int64_t)RS_ST_CPL_SAVE_ICE2 * np + p] = s.ice2;
-          st[(int64_t)RS_ST_CPL_SAVE_DEP * np + p] = s.dep;
-          st[(int64_t)RS_ST_CPL_SAVE_SNOW * np + p] = s.snow;
-          st[(int64_t)RS_ST_CPL_SAVE_ALBEDO * np + p] = s.albedo;
-          const int32_t fl = ((int32_t)st[(int64_t)RS_ST_CPL_FLAGS * np + p]) & (3 | RS_CPL_MSG_SMALL | RS_CPL_MSG_BIG);
-          st[(int64_t)RS_ST_CPL_FLAGS * np + p] = (double)(fl | (s.verycold ? 4 : 0));
-          for (int j = 1; j <= N; ++j) st[(int64_t)(RS_ST_CPL_SAVE_TMP0 + j - 1) * np + p] = T.get(j);
-          q.swcof = R4(1.0); q.lwcof = R4(1.0); q.swcorr = R4(0.0); q.lwcorr = R4(0.0);
-        }
-        if (q.again) {
-          /* uploadDataForCoupling :213-255: back to the window start; SrfIcemms, Q2Melt,
-           * T4Melt and TmpNw are NOT restored */
-          i = q.cs;
-          s.tsurf = st[(int64_t)RS_ST_CPL_SAVE_TSURF * np + p];
-          s.wat = st[(int64_t)RS_ST_CPL_SAVE_WAT * np + p];
-          s.ice2 = st[(int64_t)RS_ST_CPL_SAVE_ICE2 * np + p];
-          s.dep = st[(int64_t)RS_ST_CPL_SAVE_DEP * np + p];
-          s.snow = st[(int64_t)RS_ST_CPL_SAVE_SNOW * np + p];
-          s.albedo = st[(int64_t)RS_ST_CPL_SAVE_ALBEDO * np + p];
-          s.verycold = (((int32_t)st[(int64_t)RS_ST_CPL_FLAGS * np + p]) & 4) != 0;
-          for (int j = 1; j <= N; ++j) {
-            /* TmpNw keeps the end-of-window profile */
-            st[(int64_t)(RS_ST_CPL_STALE_TMP0 + j - 1) * np + p] = T.get(j);
-            T.set(j, st[(int64_t)(RS_ST_CPL_SAVE_TMP0 + j - 1) * np + p]);
-          }
-          stale_all = true;
-          q.again = false;
-          f = gather_forcing(ka, p, i, t0);
-          if (i == 1 && f.vz < R4(0.4)) f.vz = R4(0.4);
-          if (ka->f.sw_dir) {
-            /* the restored window holds the arrays as CheckValues left them in the first
-             * pass: SW_dir already clamped to SW (src/Coupling.f90:204-208,249-253) */
-            const int64_t off = (int64_t)(i - t0) * ka->f.t_stride + p;
-            sw_dir = ka->f.sw_dir[off];
-            lw_net = ka->f.lw_net[off];
-            if (sw_dir > f.sw) sw_dir = f.sw;
-          }
-          /* short-wave scaling only without sky view (:68-76) */
-          if (f.sw > f.lw && !sky_on) {
-            q.swcof = q.radcoeff;
-            q.lwcof = R4(1.0);
-          } else {
-            q.swcof = R4(1.0);
-            q.lwcof = q.radcoeff;
-          }
-        }
-        if (i > q.ce) {
-          const double e = cpl_decay(c, mt, i, q.ce);
-          q.swcof = R4(1.0) + q.swcorr * e;
-          q.lwcof = R4(1.0) + q.lwcorr * e;
-        }
-        if (in_phase) {
-          /* snowIceCheck :259-289 */
-          if (q.lastobs > c.TLimMeltSnow && s.snow > R4(0.00)) { s.wat = s.wat + s.snow; s.snow = R4(0.00); }
-          if (q.lastobs > c.TLimMeltIce && s.ice > R4(0.00)) { s.wat = s.wat + s.ice; s.ice = R4(0.00); }
-          if (q.lastobs > c.TLimMeltIce && s.ice2 > R4(0.00)) s.ice2 = R4(0.00);
-          if (q.lastobs > c.TLimMeltDep && s.dep > R4(0.00)) { s.wat = s.wat + s.dep; s.dep = R4(0.00); }
-        }
-        cp.in_phase = in_phase;
-      }
-      /* SetCurrentValues obs forcing, src/InputOutput.f90:116-148 */
-      if ((i <= initlen || c.force_tsurf) && f.tsurfobs > R4(-100.0) && (!q.on || i < q.cs)) {
-        T.set(1, f.tsurfobs);
-        T.set(2, f.tsurfobs);
-        const double depth = (c.tsurfOutputDepth >= R4(0.0)) ? c.tsurfOutputDepth : f.depth;
-        s.tsurf = surface_temperature(c, T, tbot, depth);
-      }
-    } else {
-      /* lastValues, src/InputOutput.f90:169-198 */
-      s.tsurf = surface_temperature(c, T, tbot, f.depth);
-      cp.in_phase = false; /* coupling%inCouplingPhase keeps its last value: index SimLen-1 */
-      if (q.on) cp.in_phase = (c.SimLen - 1 >= q.cs && c.SimLen - 1 <= q.ce);
-    }
-    double tair = f.tair, vz = f.vz, rhz = f.rhz;
-    const double prec_ts = RS_DIVC(f.prec, 3600.0, r_3600) * c.DTSecs;
-    if (i < c.SimLen && relax) {
-      if (i == initlen) { s.tair_end = tair; s.vz_end = vz; s.rh_end = rhz; }
-      if (i > initlen) {
-        const double den = (double)(4.f * 3600.f);
-        const double e = rs_exp(mt, rs_div(-((c.DTSecs * i) - (c.DTSecs * initlen)), den));
-        tair = tair - (tairR - s.tair_end) * e;
-        vz = vz - (vzR - s.vz_end) * e;
-        rhz = rhz - (rhR - s.rh_end) * e;
-        if (rhz > R4(100.)) rhz = R4(100.0);
-      }
-    }
-    cp.sw_cof = q.swcof; cp.lw_cof = q.lwcof; cp.last_tsurf_obs = q.lastobs;
-    double sw_in = f.sw, lw_in = f.lw;
-    if (sky_on) {
-      /* the reference runs this between PrecipitationToStorage and BalanceModelOneStep
-       * (Simulation.f90:151-162); the two do not share data, so the order is free */
-      if (!sky_view_radiation(ka->f.sun + (int64_t)(i - t0) * RS_SUN_COLS, sinlat, coslat, lonrad, coslon, sinlon, skyv,
-                              ka->pp.albedo_surroundings,
-                              ka->pp.horizons
-                                  ? ka->pp.horizons + (ka->pp.horizon_index ? (int64_t)ka->pp.horizon_index[p] : p) *
-                                                          (ka->pp.horizons_by_point ? 360 : 1)
-                                  : nullptr,
-                              ka->pp.horizons_by_point ? (int64_t)1 : np, sw_in, sw_dir, lw_in, lw_net))
-        fail_at(i); /* the reference would `stop` the process here */
-    }
-    if (ka->wb.sw_dir) { /* in-place input edits of the reference; a replay overwrites them */
-      const int64_t woff = (int64_t)(i - t0) * ka->wb.t_stride + p;
-      ka->wb.sw_dir[woff] = sw_dir;
-      if (sky_on) {
-        ka->wb.sw[woff] = sw_in;
-        ka->wb.lw[woff] = lw_in;
-      }
-    }
-    if (DIAG) bl_diagnose(&c, mt.expT, mt.logT, mt.K, s.tsurf, tair, vz, rhz, f.hour, i, ka->diag, np, p);
-    const Fluxes fx = model_step_fluxes(c, mt, s, tair, vz, rhz, prec_ts, sw_in, lw_in, f.phase,
-                                        f.hour, cp);
-    if (i + 1 < tend) { /* next index's forcing, half a step ahead of its use */
-      nxt = gather_forcing(ka, p, i + 1, t0);
-      nxt_i = i + 1;
-    }
-    if (stale_all) {
-      /* observation forcing cannot follow a restore (i >= couplingStartI), so TmpNw(1:2)
-       * are the stale values too */
-      const GlobalProfile Tstale{st + (int64_t)RS_ST_CPL_STALE_TMP0 * np + p, np};
-      model_step_ground(c, s, T, tbot, tair, fx, f.depth, cp, &Tstale);
-      stale_all = false;
-    } else {
-      model_step_ground(c, s, T, tbot, tair, fx, f.depth, cp);
-    }
-    int64_t orow;
-    if (output_row<false>(ka, i, orow)) store_outputs<true>(ka, orow, p, 0u, s, true);
-    if (i > written_hi) written_hi = i;
-    /* CheckEndCoupling + CouplingOperations2, src/Coupling.f90:98-141 */
-    if (i < c.SimLen && q.on && i == q.ce && !q.failed) {
-      if (q.iter == 0) q.tend1 = s.tsurf;
-      coupling_control(q, s.tsurf);
-      q.iter = q.iter + 1;
-      if (s.failed) q.again = false; /* failed at this index: the loop exits, no rewind, not listed */
-      if (ka->cpl_stop) { /* park: the next round decides between a replay and going on */
-        ++i;
-        break;
-      }
-    }
-    ++i;
-  }
-  st[(int64_t)RS_ST_CPL_RESUME * np + p] = (double)i;
 }
 
 /* RS_ST_BLSCORE from the loop's counter: bits 0-18 extra passes (saturating), bit 19 cover,
@@ -2472,84 +1996,6 @@ __global__ void __launch_bounds__(kBlock, RS_CPL_WAVES) step_kernel_coupled(cons
   time_loop_coupled<LdsProfile, DIAG>(mt, T, s, q, a.state, a.np_pad, p);
   store_state<true, LdsProfile, true>(a.state, a.np_pad, p, T, s);
   store_coupling(a.state, a.np_pad, p, q);
-}
-
-/* Device part of Initialization (src/Initialization.f90:65-147): initial
- * profile (initTemp :238-287), surface state (initSurf :290-308), T4Melt
- * (condInit :518), albedo (InitParam :339).  The first CalcBLCondAndLE call
- * (:138-139) and the first CalcHCapHCond (:109) only produce values that are
- * overwritten before they are read, so they are not executed. */
-__global__ void __launch_bounds__(kBlock) init_kernel(const InitArgs a) {
-  const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (p >= a.npoints) return;
-  const ConstsAS &c = consts_of(&a);
-  const int N = c.NLayers;
-  const double tair = a.f.tair[p];
-  const double tobs = a.f.tsurfobs ? a.f.tsurfobs[p] : R4(-9999.9);
-  const double depth = a.f.depth ? a.f.depth[p] : R4(-9999.9);
-  const double tbot = a.pp.tbottom[p];
-  const double t4 = (tobs > -100) ? tobs : tair;
-  const int64_t np = a.np_pad;
-  double *st = a.state;
-  for (int i = 1; i <= 4; ++i) st[(int64_t)(RS_ST_TMP0 + i - 1) * np + p] = t4;
-  for (int i = 5; i <= N; ++i)
-    st[(int64_t)(RS_ST_TMP0 + i - 1) * np + p] =
-        t4 + (tbot - t4) / (c.ZDpth[N + 1] - c.ZDpth[4]) * (c.ZDpth[i] - c.ZDpth[4]);
-  for (int i = N + 1; i <= RS_MAX_LAYERS; ++i) st[(int64_t)(RS_ST_TMP0 + i - 1) * np + p] = 0.0;
-  double tsurf;
-  if (depth >= 0) {
-    /* getTempAtDepth on the fresh profile, src/Initialization.f90:129-136 */
-    if (fabs(depth - R4(0.0)) < R4(0.00001)) {
-      tsurf = t4;
-    } else if (depth > c.ZDpth[N + 1]) {
-      tsurf = tbot;
-    } else {
-      tsurf = 0.0;
-      for (int k = 1; k <= N; ++k) {
-        if (depth > c.ZDpth[k] && depth <= c.ZDpth[k + 1]) {
-          const double tk = st[(int64_t)(RS_ST_TMP0 + k - 1) * np + p];
-          const double tk1 = (k == N) ? tbot : st[(int64_t)(RS_ST_TMP0 + k) * np + p];
-          tsurf = tk + (depth - c.ZDpth[k]) * (tk1 - tk) / (c.ZDpth[k + 1] - c.ZDpth[k]);
-          break;
-        }
-      }
-    }
-  } else {
-    tsurf = (t4 + t4) / R4(2.0);
-  }
-  st[(int64_t)RS_ST_TNW1 * np + p] = t4;
-  st[(int64_t)RS_ST_TNW2 * np + p] = t4;
-  st[(int64_t)RS_ST_TSURF * np + p] = tsurf;
-  st[(int64_t)RS_ST_WAT * np + p] = R4(0.0);
-  st[(int64_t)RS_ST_SNOW * np + p] = R4(0.0);
-  st[(int64_t)RS_ST_ICE * np + p] = R4(0.0);
-  st[(int64_t)RS_ST_ICE2 * np + p] = R4(0.0);
-  st[(int64_t)RS_ST_DEP * np + p] = R4(0.0);
-  st[(int64_t)RS_ST_Q2MELT * np + p] = R4(0.0);
-  st[(int64_t)RS_ST_T4MELT * np + p] = c.T4Melt0;
-  st[(int64_t)RS_ST_ALBEDO * np + p] = c.Albedo0;
-  st[(int64_t)RS_ST_VERYCOLD * np + p] = 0.0;
-  st[(int64_t)RS_ST_FAILED * np + p] = 0.0;
-  st[(int64_t)RS_ST_TAIR_END * np + p] = R4(-99.9); /* src/Initialization.f90:377-379 */
-  st[(int64_t)RS_ST_VZ_END * np + p] = R4(-99.9);
-  st[(int64_t)RS_ST_RH_END * np + p] = R4(-99.9);
-  st[(int64_t)RS_ST_BLSCORE * np + p] = 0.0;
-  /* initCoupling, src/Coupling.f90:144-169 */
-  st[(int64_t)RS_ST_CPL_ITER * np + p] = 0.0;
-  st[(int64_t)RS_ST_CPL_FLAGS * np + p] = 0.0;
-  st[(int64_t)RS_ST_CPL_TABOVE * np + p] = R4(-9999.0);
-  st[(int64_t)RS_ST_CPL_TBELOW * np + p] = R4(-9999.0);
-  st[(int64_t)RS_ST_CPL_RADCOEFF * np + p] = R4(1.0);
-  st[(int64_t)RS_ST_CPL_RCABOVE * np + p] = R4(-9999.0);
-  st[(int64_t)RS_ST_CPL_RCBELOW * np + p] = R4(-9999.0);
-  st[(int64_t)RS_ST_CPL_RCPREV * np + p] = R4(1.0);
-  st[(int64_t)RS_ST_CPL_SWCOF * np + p] = R4(1.0);
-  st[(int64_t)RS_ST_CPL_LWCOF * np + p] = R4(1.0);
-  st[(int64_t)RS_ST_CPL_SWCORR * np + p] = R4(0.0);
-  st[(int64_t)RS_ST_CPL_LWCORR * np + p] = R4(0.0);
-  st[(int64_t)RS_ST_CPL_TEND1 * np + p] = 0.0;
-  st[(int64_t)RS_ST_CPL_LASTOBS * np + p] = a.pp.coupling_tsurf ? a.pp.coupling_tsurf[p] : R4(-9999.0);
-  st[(int64_t)RS_ST_CPL_RESUME * np + p] = 1.0;
 }
 
 /* Hourly knots of the synthetic workload, [knot][RS_KNOT_FIELDS][np_pad]. */

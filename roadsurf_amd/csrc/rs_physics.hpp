@@ -37,6 +37,16 @@
 #define RS_CONSTS RsConstantsDev __attribute__((address_space(4)))
 /* a / b with b uniform and its reciprocal in the constant block */
 #define RS_DIVC(a, b, rb) rs_div_u(a, b, c.rb)
+/* ---- the fp64 flavour's side of rs_general_body.inc (the fp32 one: the head of rs_kernels_f32.hip) ---- */
+#define RS_SECANT_DIV(a, b) ((a) / (b)) /* Coupling_control's secant: the IEEE quotient, as the reference forms it */
+#define RS_PROFILE_PIN 1                /* RegProfile::pin holds the new profile in place (see there) */
+#define RS_CPL_SLOTS(c) true            /* the coupling slots of the state block are written and read by every plan */
+#define RS_CPL_DECAY_TABLE 1            /* the coupling decay from the plan's table (RsConstantsDev::cpl_tab) */
+#define RS_GEN_PREFETCH 1               /* the general loop fetches the next index's forcing half a step early */
+#define RS_GEN_FP64_FEATURES 1          /* diagnostics, write-back of the in-place input edits, the cpl_stop park */
+#define RS_INIT_KERNEL init_kernel      /* the name of the kernel that makes the initial state */
+#define RS_INIT_ANCHOR R4(-99.9)        /* the relaxation anchors' seed, src/Initialization.f90:377-379 */
+#define RS_INIT_ZERO_TAIL 1             /* init zeroes the profile slots behind NLayers */
 #define RS_BL_GUARD 1
 #define RS_MELTDEN c.meltDen /* WatMHeat*WatDens, the same IEEE product formed once on the host */
 #define RS_BARE_FAST(c) ((c).bareFastOk != 0) /* rs_consts_dev.h */
@@ -62,7 +72,7 @@
 #undef RS_FROZEN_TABLE
 #undef RS_HCW_TABLE
 #undef RS_LK
-#undef RS_REAL
+/* (RS_REAL, R4, RS_DIVC and the rs_general_body.inc macros above stay defined: rs_kernels.hip includes that text) */
 #undef RS_NS
 #undef RS_CONSTS
 #undef RS_BL_GUARD

@@ -336,16 +336,12 @@ def test_fp32_sky_view_against_the_fp64_reference(summer, world, chunk, history)
     assert np.abs(plain["tsurf"][ok] - ora["tsurf"][ok]).max() > 0.5
 
 
-@pytest.mark.parametrize("nl,chunk", [(15, 0), (12, 97)])
-def test_fp32_output_depth_and_the_full_feature_set_at_any_layer_count(nl, chunk):
-    """The general fp32 kernel (step_kernel_f32_coupled, here without coupling) takes what the two-wavefront kernels do not
-    have: an output depth - tsurfOutputDepth, or a depth stream with values inside the grid, below it and exactly 0
-    (getTempAtDepth, src/BalanceModel.f90:390-417; src/Initialization.f90:129-136 for the first index) - and the FULL
-    feature set (initialization phase with observations, relaxation) at NLayers != 15, whole series and launches of 97
-    indices.  Against the fp64 reference, the FULL flavour's gate."""
-    from roadsurf_amd import device
-    n, L, seed = 512, 2881, 23
-    f = oh.synth_forcing(n, L, seed=seed)
+def _depth_cases(n, L, nl, fail_index):
+    """The inputs of test_fp32_output_depth_and_the_full_feature_set_at_any_layer_count (tools/compare_library_results.py
+    runs them too): initialization phases of 1, 240 and 600 indices with observations, relaxation, and an output depth
+    once as the setting and once as a depth stream; point 5 fails the dew-point test at index fail_index.
+    -> forcing without a depth, parameters, local parameters, [(what, forcing, settings)]"""
+    f = oh.synth_forcing(n, L, seed=23)
     p = abi.default_parameters()
     s0 = abi.default_settings(L); s0.NLayers = nl
     l0 = abi.default_local(); l0.InitLenI = 1
@@ -358,6 +354,7 @@ def test_fp32_output_depth_and_the_full_feature_set_at_any_layer_count(nl, chunk
         li.VZ_relax = float(rs.uniform(0.5, 6.0)); li.RH_relax = float(rs.uniform(60, 99))
         ls.append(li)
     f["tsurfobs"][:, :] = base["tsurf"] + rs.uniform(-1.0, 1.0, (n, 1))
+    cases = []
     for what in ("depth-setting", "depth-array"):
         g = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in f.items()}
         s = abi.default_settings(L); s.NLayers = nl; s.use_relaxation = 1
@@ -365,7 +362,22 @@ def test_fp32_output_depth_and_the_full_feature_set_at_any_layer_count(nl, chunk
             s.tsurfOutputDepth = 0.05
         else:
             g["depth"][:] = 0.0; g["depth"][::2] = 0.12; g["depth"][1::4] = 7.0
-        g["tdew"][5, 1500] = 120.0  # CheckValues fails the point at index 1501, in the middle of a launch
+        g["tdew"][5, fail_index - 1] = 120.0
+        cases.append((what, g, s))
+    return f, p, ls, cases
+
+
+@pytest.mark.parametrize("nl,chunk", [(15, 0), (12, 97)])
+def test_fp32_output_depth_and_the_full_feature_set_at_any_layer_count(nl, chunk):
+    """The general fp32 kernel (step_kernel_f32_coupled, here without coupling) takes what the two-wavefront kernels do not
+    have: an output depth - tsurfOutputDepth, or a depth stream with values inside the grid, below it and exactly 0
+    (getTempAtDepth, src/BalanceModel.f90:390-417; src/Initialization.f90:129-136 for the first index) - and the FULL
+    feature set (initialization phase with observations, relaxation) at NLayers != 15, whole series and launches of 97
+    indices.  Against the fp64 reference, the FULL flavour's gate."""
+    from roadsurf_amd import device
+    n, L = 512, 2881
+    f, p, ls, cases = _depth_cases(n, L, nl, 1501)  # CheckValues fails point 5 at index 1501, in the middle of a launch
+    for what, g, s in cases:
         ora, _, _ = oh.run_oracle("ref" if oh.have_ref() else "port", g, s, p, ls)
         res, nfail = device.run_points(g, s, p, ls, chunk=chunk, precision=32)
         assert nfail == 1
@@ -451,6 +463,26 @@ def test_fp32_coupling_against_the_fp64_reference():
         assert (np.abs(ora["tsurf"] - base["tsurf"]).max(1) > 1e-3).sum() > n // 2  # coupling really acts
 
 
+def _coupling_sky_case(f, ls, SL, nl):
+    """The inputs of test_fp32_coupling_with_sky_view_and_other_layer_counts (tools/compare_library_results.py runs them
+    too): a sky-view case of tests/test_hip_skyview.py with a coupling window that ends at index 900, observations 0 to
+    5 K off the uncoupled run.  -> forcing, settings, parameters, local parameters"""
+    p = abi.default_parameters()
+    s0 = abi.default_settings(SL); s0.NLayers = nl
+    basel = [abi.LocalParameters.from_buffer_copy(li) for li in ls]
+    base, _, _ = oh.run_oracle("port", f, s0, p, basel)
+    rs = np.random.RandomState(1)
+    ls2 = []
+    for i, li in enumerate(basel):
+        li.couplingIndexI = 900; li.InitLenI = 900
+        li.couplingTsurf = float(base["tsurf"][i, 899] + rs.choice([0.0, 1.0, -2.0, 5.0]))
+        ls2.append(li)
+    g = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in f.items()}
+    g["tsurfobs"][:, :] = base["tsurf"] + 0.2
+    s = abi.default_settings(SL); s.use_coupling = 1; s.NLayers = nl
+    return g, s, p, ls2
+
+
 def test_fp32_coupling_with_sky_view_and_other_layer_counts():
     """... together with sky view (long-wave scaling only: src/Coupling.f90:68-76), and for a profile of 12 layers (the
     kernel keeps the profile in LDS: any NLayers)."""
@@ -460,19 +492,7 @@ def test_fp32_coupling_with_sky_view_and_other_layer_counts():
     n, SL = 200, 1441
     f, ls = _sky_case(n, SL, 7, summer=True)
     for nl in (15, 12):
-        p = abi.default_parameters()
-        s0 = abi.default_settings(SL); s0.NLayers = nl
-        basel = [abi.LocalParameters.from_buffer_copy(li) for li in ls]
-        base, _, _ = oh.run_oracle("port", f, s0, p, basel)
-        rs = np.random.RandomState(1)
-        ls2 = []
-        for i, li in enumerate(basel):
-            li.couplingIndexI = 900; li.InitLenI = 900
-            li.couplingTsurf = float(base["tsurf"][i, 899] + rs.choice([0.0, 1.0, -2.0, 5.0]))
-            ls2.append(li)
-        g = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in f.items()}
-        g["tsurfobs"][:, :] = base["tsurf"] + 0.2
-        s = abi.default_settings(SL); s.use_coupling = 1; s.NLayers = nl
+        g, s, p, ls2 = _coupling_sky_case(f, ls, SL, nl)
         ora, _, _ = oh.run_oracle(_kind(), g, s, p, ls2)
         res, nfail = device.run_points(g, s, p, ls2, precision=32)
         assert nfail == 0

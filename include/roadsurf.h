@@ -430,6 +430,20 @@ int rs_hip_set_writeback(RsPlan *plan, double *sw, double *sw_dir, double *lw, i
  * tests).  Layout: [RS_NSTATE][npoints_padded] doubles. */
 int rs_hip_state_download(RsPlan *plan, double *host, size_t bytes);
 int rs_hip_state_upload(RsPlan *plan, const double *host, size_t bytes);
+/* Branching a run on the device (the ABI number stays; a binding detects the call by its symbol): point p of `dst`
+ * takes the carried state of point parent[p] of `src` (parent: HOST int32[dst npoints], every entry in
+ * [0, src npoints) - checked here, rs_last_error names the first that is not, and uploaded to scratch of dst).  The
+ * state block is all a launch inherits - the step calls keep no time bookkeeping in the plan - so dst goes on with
+ * rs_hip_step* at the index src was about to step, under the same SimLen, as parent[p] would have: an ensemble
+ * forecast steps the analysis its members share once (roadsurf_amd/ensemble.py is the definition and a runner).
+ * Copied are the rows a re-sort moves: Tmp(1..NLayers), the named rows TmpNw(1) .. the sort key, with use_coupling
+ * the coupling scalars and, unless src's coupling windows are closed, the saved and stale profiles.  Either plan
+ * may have been re-sorted: the copy goes from src's slot of parent[p] to dst's slot of p; dst keeps its order row and
+ * its padding columns, src is not written.  The two plans are on one device, of one precision, with equal
+ * RsConstants, without diagnostics, and not the same plan; anything else is refused.  Asynchronous: enqueued on
+ * dst's stream behind what src's stream held at the call, and src's stream goes on behind the copy.  Afterwards dst
+ * has src's rs_hip_coupling_windows_closed, and a wave table a forecast re-sort left it is dropped. */
+int rs_hip_state_fanout(RsPlan *dst, RsPlan *src, const int32_t *parent);
 /* Number of points with the sticky failure flag set (src/InputOutput.f90:66). */
 int64_t rs_hip_failed_count(RsPlan *plan);
 /* Measurement aid: one wavefront that reads the shader-clock counter and the constant 100 MHz

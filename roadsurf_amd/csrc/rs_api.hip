@@ -84,6 +84,11 @@ struct RsPlan {
   int32_t *wave_tab = nullptr;
   int32_t wave_n = 0;
   bool wave_tab_valid = false;
+  /* rs_hip_state_fanout: the checked parent row of a dst plan (host copy and device [np_pad]), the inverse of a src
+   * plan's order row [np_pad], and a dst plan's events: src ready, copy done, parent row uploaded */
+  std::vector<int32_t> fan_host;
+  int32_t *fan_parent = nullptr, *fan_inv = nullptr;
+  hipEvent_t fan_ev[3] = {nullptr, nullptr, nullptr};
   std::vector<void *> owned; /* hipMalloc-ed pieces (plan_malloc): what rs_hip_plan_destroy frees */
   /* the arena the plan's first pieces came out of (nullptr: hipMalloc) and where it stood: a later piece is
    * taken from an arena only if it is still THAT arena and it has not been rewound since (a plan
@@ -336,6 +341,8 @@ void rs_hip_plan_destroy(RsPlan *pl) {
   (void)hipSetDevice(pl->device);
   (void)hipStreamSynchronize(pl->stream);
   for (hipEvent_t e : pl->ev) (void)hipEventDestroy(e);
+  for (hipEvent_t e : pl->fan_ev)
+    if (e) (void)hipEventDestroy(e);
   for (void *q : pl->owned) (void)hipFree(q); /* pieces of a worker's arena are the worker's to reclaim */
   delete pl;
 }
@@ -1272,6 +1279,59 @@ int rs_hip_state_upload(RsPlan *pl, const double *host, size_t bytes) {
   HIP_OK(hipSetDevice(pl->device));
   HIP_OK(hipMemcpyAsync(pl->state, host, bytes, hipMemcpyHostToDevice, pl->stream));
   HIP_OK(hipStreamSynchronize(pl->stream));
+  return 0;
+}
+
+/* Point p of dst takes the carried state of point parent[p] of src, on the device, whatever order the slots of either
+ * plan are in.  Every index a kernel reads is the library's own or was checked here: parent is validated on the host
+ * and then uploaded to scratch of dst. */
+int rs_hip_state_fanout(RsPlan *dst, RsPlan *src, const int32_t *parent) {
+  if (!dst || !src || !parent) return set_err("rs_hip_state_fanout: null argument (dst, src and parent are required)");
+  if (dst == src) return set_err("rs_hip_state_fanout: dst and src are the same plan");
+  if (dst->device != src->device)
+    return set_err("rs_hip_state_fanout: the plans live on different devices (dst %d, src %d)", dst->device, src->device);
+  if (dst->f32 != src->f32)
+    return set_err("rs_hip_state_fanout: the plans differ in precision (dst fp%d, src fp%d)", dst->f32 ? 32 : 64,
+                   src->f32 ? 32 : 64);
+  if (std::memcmp(&dst->c, &src->c, sizeof(RsConstants)) != 0)
+    return set_err("rs_hip_state_fanout: the plans' RsConstants differ (same settings and parameters, SimLen included)");
+  if (dst->diag_on || src->diag_on)
+    return set_err("rs_hip_state_fanout: not for a plan with diagnostics on (its record is kept by slot: "
+                   "rs_hip_set_diagnostics)");
+  for (int64_t p = 0; p < dst->npoints; ++p)
+    if (parent[p] < 0 || (int64_t)parent[p] >= src->npoints)
+      return set_err("rs_hip_state_fanout: parent[%lld] = %d is outside src's points [0, %lld)", (long long)p,
+                     parent[p], (long long)src->npoints);
+  HIP_OK(hipSetDevice(dst->device));
+  for (hipEvent_t &e : dst->fan_ev)
+    if (!e) HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  if (!dst->fan_parent) HIP_OK(plan_malloc(dst, &dst->fan_parent, (size_t)dst->np_pad * sizeof(int32_t)));
+  if (!dst->fan_host.empty()) HIP_OK(hipEventSynchronize(dst->fan_ev[2])); /* the upload of the call before */
+  dst->fan_host.assign(parent, parent + dst->npoints);
+  HIP_OK(hipMemcpyAsync(dst->fan_parent, dst->fan_host.data(), (size_t)dst->npoints * sizeof(int32_t),
+                        hipMemcpyHostToDevice, dst->stream));
+  HIP_OK(hipEventRecord(dst->fan_ev[2], dst->stream));
+  const int32_t *inv = nullptr;
+  if (src->resorted) { /* else point q sits in slot q */
+    if (!src->fan_inv) HIP_OK(plan_malloc(src, &src->fan_inv, (size_t)src->np_pad * sizeof(int32_t)));
+    HIP_OK(rs_cluster_inverse(src->order, src->npoints, src->fan_inv, src->stream));
+    inv = src->fan_inv;
+  }
+  /* behind everything src's stream holds so far; and src's stream goes on behind the copy */
+  const bool two_streams = dst->stream != src->stream;
+  if (two_streams) {
+    HIP_OK(hipEventRecord(dst->fan_ev[0], src->stream));
+    HIP_OK(hipStreamWaitEvent(dst->stream, dst->fan_ev[0], 0));
+  }
+  HIP_OK(rs_cluster_fanout(src->state, dst->state, dst->f32, dst->order, dst->fan_parent, inv,
+                           src->np_pad, src->npoints, dst->np_pad, dst->npoints, dst->c.NLayers,
+                           dst->c.use_coupling == 0 ? 0 : src->cpl_windows_closed ? 1 : 2, dst->stream));
+  if (two_streams) {
+    HIP_OK(hipEventRecord(dst->fan_ev[1], dst->stream));
+    HIP_OK(hipStreamWaitEvent(src->stream, dst->fan_ev[1], 0));
+  }
+  dst->cpl_windows_closed = src->cpl_windows_closed;
+  dst->wave_tab_valid = false; /* the table was made for what the slots held before */
   return 0;
 }
 

@@ -72,6 +72,40 @@ __global__ void __launch_bounds__(RS_BLOCK) apply_kernel(const T *__restrict__ s
   dst[row * np_pad + s] = src[row * np_pad + from];
 }
 
+/* inv[order[s]] = s: where every point of a re-sorted plan sits (rs_hip_state_fanout) */
+__global__ void __launch_bounds__(RS_BLOCK) inverse_kernel(const int32_t *__restrict__ order, int64_t npoints,
+                                                           int32_t *__restrict__ inv) {
+  const int64_t s = (int64_t)blockIdx.x * RS_BLOCK + threadIdx.x;
+  if (s >= npoints) return;
+  const int64_t p = order[s];
+  if (p >= 0 && p < npoints) inv[p] = (int32_t)s;
+}
+
+/* The carried state of another plan's points (rs_hip_state_fanout): dst[row][s] = src[row][slot of parent[point of s]]
+ * for the slots s < npoints of dst and the rows of `rows`.  One lane per dst slot, one grid row per state row: the
+ * stores are coalesced, the loads gathers - a broadcast within the wavefront where the members of a station sit side
+ * by side.  order_dst NULL: slot s holds point s; inv_src NULL: point q sits in slot q.  parent was checked on the
+ * host; an index that is no point of its plan (an order row of the caller's making) writes nothing.  Columns beyond
+ * dst's npoints and everything of src stay as they are. */
+template <typename T>
+__global__ void __launch_bounds__(RS_BLOCK) fanout_kernel(const T *__restrict__ src, T *__restrict__ dst,
+                                                          const int32_t *__restrict__ order_dst,
+                                                          const int32_t *__restrict__ parent,
+                                                          const int32_t *__restrict__ inv_src, int64_t np_pad_src,
+                                                          int64_t npoints_src, int64_t np_pad_dst, int64_t npoints_dst,
+                                                          const RowMap rows) {
+  const int64_t s = (int64_t)blockIdx.x * RS_BLOCK + threadIdx.x;
+  if (s >= npoints_dst) return;
+  const int64_t p = order_dst ? (int64_t)order_dst[s] : s;
+  if (p < 0 || p >= npoints_dst) return;
+  const int64_t q = parent[p];
+  if (q < 0 || q >= npoints_src) return;
+  const int64_t from = inv_src ? (int64_t)inv_src[q] : q;
+  if (from < 0 || from >= npoints_src) return;
+  const int64_t row = rows.row((int32_t)blockIdx.y);
+  dst[row * np_pad_dst + s] = src[row * np_pad_src + from];
+}
+
 __global__ void __launch_bounds__(RS_BLOCK) iota_kernel(int32_t *x, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * RS_BLOCK + threadIdx.x;
   if (i < n) x[i] = (int32_t)i;
@@ -999,16 +1033,43 @@ hipError_t rs_cpl_select_again(const double *state, int64_t np_pad, int64_t npoi
 
 /* nlayers: NLayers of the plan; cpl_rows: 0 no coupling block, 1 the coupling scalars only (every
  * coupling window is behind the plan: nothing reads the saved state any more), 2 everything */
-hipError_t rs_cluster_apply(const double *state_src, double *state_dst, bool f32,
-                            const int32_t *order_src, int32_t *order_dst, const uint32_t *perm,
-                            int64_t np_pad, int64_t npoints, int nlayers, int cpl_rows,
-                            hipStream_t stream) {
-  dim3 g = grid1(np_pad);
+static RowMap row_map(int nlayers, int cpl_rows) {
   RowMap rows;
   rows.nlayers = nlayers;
   rows.nscal = RS_ST_BLSCORE - RS_ST_TNW1 + 1;
   rows.ncpl = cpl_rows >= 1 ? RS_ST_CPL_RESUME - RS_ST_CPL_ITER + 1 : 0;
   rows.nsave = cpl_rows >= 2 ? RS_ST_CPL_SAVE_ALBEDO - RS_ST_CPL_SAVE_TSURF + 1 : 0;
+  return rows;
+}
+
+hipError_t rs_cluster_inverse(const int32_t *order, int64_t npoints, int32_t *inv, hipStream_t stream) {
+  hipLaunchKernelGGL(inverse_kernel, grid1(npoints), dim3(RS_BLOCK), 0, stream, order, npoints, inv);
+  return hipGetLastError();
+}
+
+/* the rows a re-sort of src would move (nlayers, cpl_rows as below), from src's slots into dst's */
+hipError_t rs_cluster_fanout(const double *state_src, double *state_dst, bool f32, const int32_t *order_dst,
+                             const int32_t *parent, const int32_t *inv_src, int64_t np_pad_src, int64_t npoints_src,
+                             int64_t np_pad_dst, int64_t npoints_dst, int nlayers, int cpl_rows, hipStream_t stream) {
+  dim3 g = grid1(npoints_dst);
+  const RowMap rows = row_map(nlayers, cpl_rows);
+  g.y = (unsigned)rows.total();
+  if (f32)
+    hipLaunchKernelGGL(fanout_kernel<float>, g, dim3(RS_BLOCK), 0, stream, reinterpret_cast<const float *>(state_src),
+                       reinterpret_cast<float *>(state_dst), order_dst, parent, inv_src, np_pad_src, npoints_src,
+                       np_pad_dst, npoints_dst, rows);
+  else
+    hipLaunchKernelGGL(fanout_kernel<double>, g, dim3(RS_BLOCK), 0, stream, state_src, state_dst, order_dst, parent,
+                       inv_src, np_pad_src, npoints_src, np_pad_dst, npoints_dst, rows);
+  return hipGetLastError();
+}
+
+hipError_t rs_cluster_apply(const double *state_src, double *state_dst, bool f32,
+                            const int32_t *order_src, int32_t *order_dst, const uint32_t *perm,
+                            int64_t np_pad, int64_t npoints, int nlayers, int cpl_rows,
+                            hipStream_t stream) {
+  dim3 g = grid1(np_pad);
+  const RowMap rows = row_map(nlayers, cpl_rows);
   g.y = (unsigned)rows.total();
   if (f32)
     hipLaunchKernelGGL(apply_kernel<float>, g, dim3(RS_BLOCK), 0, stream,

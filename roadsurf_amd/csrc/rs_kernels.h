@@ -224,6 +224,13 @@ hipError_t rs_cluster_apply(const double *state_src, double *state_dst, bool f32
                             const int32_t *order_src, int32_t *order_dst, const uint32_t *perm,
                             int64_t np_pad, int64_t npoints, int nlayers, int cpl_rows,
                             hipStream_t stream);
+/* the carried state of src's points into dst's slots (rs_hip_state_fanout): dst slot s takes the rows of src's point
+ * parent[order_dst[s]], which sits in slot inv_src[...] (rs_cluster_inverse of src's order row; NULL: its own number);
+ * order_dst NULL: slot s holds point s; nlayers, cpl_rows as for rs_cluster_apply */
+hipError_t rs_cluster_inverse(const int32_t *order, int64_t npoints, int32_t *inv, hipStream_t stream);
+hipError_t rs_cluster_fanout(const double *state_src, double *state_dst, bool f32, const int32_t *order_dst,
+                             const int32_t *parent, const int32_t *inv_src, int64_t np_pad_src, int64_t npoints_src,
+                             int64_t np_pad_dst, int64_t npoints_dst, int nlayers, int cpl_rows, hipStream_t stream);
 
 /* fp32 flavour (rs_kernels_f32.hip) */
 /* single-precision mirror of the constants: fills *dst (device, rs32_constants_bytes() bytes) */

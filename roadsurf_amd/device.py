@@ -268,6 +268,30 @@ class Plan:
         lib.check(self.L.rs_hip_state_upload(self._h, C.c_void_p(t.data_ptr()), t.numel() * 8),
                   "rs_hip_state_upload")
 
+    def fanout_from(self, src: "Plan", parent) -> None:
+        """Point p of this plan takes the carried state of point ``parent[p]`` of ``src``, on the device, whatever
+        order the slots of either plan are in (rs_hip_state_fanout; roadsurf_amd/ensemble.py is the definition).
+        ``parent``: int32 numpy array or CPU tensor of ``npoints`` entries, every one a point of ``src`` - the
+        library checks them before anything is launched.  Asynchronous: on this plan's stream, behind ``src``'s."""
+        import numpy as np
+        if not hasattr(self.L, "rs_hip_state_fanout"):
+            raise RuntimeError("this libroadsurf_hip.so has no state fan-out (rs_hip_state_fanout)")
+        if not isinstance(src, Plan) or not src._h or not self._h:
+            raise RuntimeError("rs_hip_state_fanout: null argument (dst, src and parent are required)")
+        if parent is None:
+            raise RuntimeError("rs_hip_state_fanout: null argument (dst, src and parent are required)")
+        if torch.is_tensor(parent):
+            if parent.is_cuda:
+                raise ValueError("fanout_from: parent is a HOST array (numpy or a CPU tensor)")
+            parent = parent.numpy()
+        par = np.asarray(parent)
+        if par.dtype.kind not in "iu" or par.shape != (self.npoints,):
+            raise ValueError(f"fanout_from: parent must be {self.npoints} integers, one per point of this plan")
+        if par.size and (par.min() < -2**31 or par.max() >= 2**31):
+            raise ValueError("fanout_from: parent does not fit int32")
+        par = np.ascontiguousarray(par, dtype=np.int32)
+        lib.check(self.L.rs_hip_state_fanout(self._h, src._h, C.c_void_p(par.ctypes.data)), "rs_hip_state_fanout")
+
     # -- synthetic workload -----------------------------------------------------
     def synth_knots(self, seed: int, nknots: int, point_offset: int = 0, steps_per_knot: int = 120,
                     start_hour: int = 0):

@@ -90,6 +90,7 @@ using rs::rs_exp;
 using rs::rs_fabs;
 using rs::rs_fmax;
 using rs::rs_fmin;
+using rs::rs_min_num_one;
 using rs::rs_is_pos_zero;
 using rs::rs_wave_all;
 using rs::rs_log;

@@ -131,7 +131,7 @@ static __device__ unsigned long long g_div_mismatch[3] = {0ull, 0ull, 0ull};
  * forcing_prep_tail: [17] wave-steps, [18] the precipitation branch taken; boundary-layer passes as wavefronts issue
  * them: [19] all, [20] with a lane on the unstable arm, [21] with lanes on both paths of its log, [22] with lanes on
  * both arms, [23] with a lane on log's table path; [48] lane-passes, [46] of them on the unstable arm, [47] on log's
- * table path */
+ * table path; [49..52] CalcLE's dry tail (rs_physics_body.inc, dry_tail_count) */
 #define RS_BL_NSTATS 56 /* [24..31] wave-steps by the wavefront's trip count 5, 6, 7, 8, 9-12, 13-20, 21-39, 40; [32..39] lane-steps likewise; [40..45] wave-steps with 1, 2-3, 4-7, 8-15, 16-31, 32-64 lanes of more than 20 passes */
 static __device__ unsigned long long g_bl_stats[RS_BL_NSTATS];
 /* the first RS_DIV_SAMPLES finite mismatches: {numerator (or sqrt argument), denominator (0 for
@@ -262,6 +262,10 @@ __device__ __forceinline__ double rs_sq(double x) {
 __device__ __forceinline__ bool rs_is_pos_zero(double x) { return __double_as_longlong(x) == 0; }
 __device__ __forceinline__ bool rs_is_pos_zero(float x) { return __float_as_int(x) == 0; }
 __device__ __forceinline__ bool rs_is_neg_zero(double x) { return __double_as_longlong(x) == (long long)0x8000000000000000ull; }
+/* x is positive and finite / positive and normal: false for a NaN, an infinity, either zero and every negative
+ * number (one v_cmp_class_f64: 0x080 +subnormal, 0x100 +normal) */
+__device__ __forceinline__ bool rs_is_pos_finite(double x) { return __builtin_amdgcn_class(x, 0x180); }
+__device__ __forceinline__ bool rs_is_pos_normal(double x) { return __builtin_amdgcn_class(x, 0x100); }
 /* true in every ACTIVE lane of the wavefront (lanes that have left the time step do not vote) */
 __device__ __forceinline__ bool rs_wave_all(bool p) { return __builtin_amdgcn_ballot_w64(!p) == 0ull; }
 
@@ -285,6 +289,10 @@ __device__ __forceinline__ double rs_min_one(double x) {
   asm("v_min_f64 %0, %1, 1.0" : "=v"(r) : "v"(x));
   return r;
 }
+/* IEEE minNum(x, 1.0) - 1.0 for a NaN - of an x that an arithmetic instruction has just made (nothing to
+ * canonicalise: one v_min_f64 that the compiler may place); the float flavour keeps its compare and select */
+__device__ __forceinline__ double rs_min_num_one(double x) { return __builtin_fmin(x, 1.0); }
+__device__ __forceinline__ float rs_min_num_one(float x) { return (x > 1.0f) ? 1.0f : x; }
 __device__ __forceinline__ float rs_fmax(float a, float b) { return __builtin_fmaxf(a, b); }
 __device__ __forceinline__ float rs_fmin(float a, float b) { return __builtin_fminf(a, b); }
 __device__ __forceinline__ double rs_fabs(double x) { return __builtin_fabs(x); }

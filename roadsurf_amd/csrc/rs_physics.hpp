@@ -67,7 +67,18 @@
 #define RS_HCW_TABLE 1 /* layer_vsh: the water polynomials' coefficients from RsConstantsDev::hcw */
 #endif
 #define RS_STAB_UPPER(x) rs_min_one(x) /* bl_iteration: the stability parameter's upper clamp, one v_min_f64 in the stable arm */
+/* CalcLE's tail skipped for a wavefront in which the reference zeroes it in every point (rs_physics_body.inc, DRY
+ * TAIL; the argument there rests on this flavour's correctly rounded arithmetic).  A/B builds: -DRS_NO_DRY_TAIL_SKIP
+ * is the text without either stage, -DRS_NO_DRY_ESURF_SKIP the first stage alone. */
+#ifndef RS_NO_DRY_TAIL_SKIP
+#define RS_DRY_TAIL 1
+#if !defined(RS_NO_DRY_ESURF_SKIP) && !defined(RS_EXP_SURFACE_LIGHT) && !defined(RS_EXP_PIPE1)
+#define RS_DRY_ESURF 1
+#endif
+#endif
 #include "rs_physics_body.inc"
+#undef RS_DRY_TAIL
+#undef RS_DRY_ESURF
 #undef RS_STAB_UPPER
 #undef RS_FROZEN_TABLE
 #undef RS_HCW_TABLE

@@ -197,10 +197,96 @@ __device__ __forceinline__ bool bl_iteration(const RS_CONSTS &c, const MathTab &
   return (j >= 5) && (rs_fabs(x.BLCond - BLCond_Old) < ConvLim);
 }
 
+#ifdef RS_DRY_TAIL
+/* DRY TAIL.  CalcLE ends with `if (le > 0 .and. wat <= 0) then le = 0; evap = 0` (src/BoundaryLayer.f90:186-189): a
+ * dry surface that would evaporate does not.  A wavefront in which that rule fires in every point - most of the
+ * bench workload's: the bare-road shortcut of road_condition needs evap == 0 in all 64 - skips what the rule throws
+ * away: calcRaero's division and clamp, le's and evap's divisions, the latent-heat select and the water density.
+ *
+ * dry_tail_le says, from signs and classes alone (every test is false on a NaN), that the reference's le comes out
+ * of its division positive, so that the rule fires and leaves le = +0.0, evap = +0.0.  With
+ *   N = AirVCap*(ESurf - EAir)   positive and NORMAL  (>= 2^-1022, finite)
+ *   raNum = (logMom + PSIM)*(logHeat + PSIH) > 0      (+inf allowed)
+ *   raDen = VK^2*VZ              positive and finite
+ *   0 < PsychC < 1
+ * the IEEE quotient raNum/raDen is in [+0, +inf] and not a NaN (neither 0/0 nor inf/inf can occur), the clamp leaves
+ * RAero in [+0, 30], D = PsychC*RAero is in [+0, 30) and le = N/D is +inf for D = 0 and at least 2^-1022/30 > 2^-1074
+ * otherwise: positive, never an underflowed +0 (which the rule would leave alone, with evap = +0/(lat*WatDen) at the
+ * mercy of lat and WatDen).  `le > 0` holds, `wat <= 0` is tested as the reference tests it, both results are +0.0
+ * whatever lat, WatDen and DTSecs are.  The bare sequence's NaN where IEEE gives +inf or 0 (the GUARD below) needs no
+ * thought here: the guard's redo is the IEEE evaluation this argument is about, and ends in the same two zeros.
+ *
+ * dry_tail_warm says the same without ESurf, for a surface warmer than the air:
+ *   -100 < tair,  tair + 0.01 <= tsurf < 100,  EAir not a NaN  (and the tests on wat, raNum, raDen above).
+ * Both Magnus curves rise with T above -237.3 and -265.5 degrees, the one over ice lies below the one over water for
+ * T < 0 and meets it at 0, and d ln E / dT = a*b/(T + b)^2 is at least 0.036 / K below 100 degrees: the exact
+ * ESurf(tsurf) exceeds the exact saturation pressure at tair by 3.6e-4 of itself.  The computed values carry a few
+ * ulp each (as*T and T + bs rounded, a correctly rounded quotient of magnitude < 20, rs_exp within an ulp of exp, one
+ * product): below 1e-14 relative, ten orders under the gap.  hum <= 1 after its clamp and rounding is monotone, so
+ * the computed EAir = hum*ESat <= ESat < ESurf (a negative hum makes EAir <= 0 < ESurf, -inf included).  On that
+ * range of tair, AirDens is in (0.9, 2.1), AirHCap in [1005, 1010], PsychC in (0.058, 0.071) and ESurf - EAir >=
+ * 3.6e-4 * 1e-6, so N is normal or +inf (EAir = -inf) and le = N/D positive or +inf as above: zeroed.  (With the
+ * humidity's limit taken as the reference's MIN takes it - a NaN reads 1.0, forcing_prep_tail - EAir cannot be a
+ * NaN on that range of tair; the test stands so that the argument does not lean on it.) */
+__device__ __forceinline__ bool dry_tail_signs(RS_REAL wat, RS_REAL raNum, RS_REAL raDen) {
+  return (wat <= R4(0.0)) && (raNum > R4(0.0)) && rs_is_pos_finite(raDen);
+}
+__device__ __forceinline__ bool dry_tail_le(bool signs, RS_REAL N, RS_REAL PsychC) {
+  return signs && rs_is_pos_normal(N) && (PsychC > R4(0.0)) && (PsychC < R4(1.0));
+}
+__device__ __forceinline__ bool dry_tail_warm(bool signs, RS_REAL tsurf, RS_REAL tair, RS_REAL EAir) {
+  return signs && (tair > R4(-100.0)) && (tsurf < R4(100.0)) && (tsurf >= tair + R4(0.01)) && (EAir == EAir);
+}
+#ifdef RS_BL_STATS
+/* [49] wave-steps in which dry_tail_le holds in every active lane, [50] lane-steps in which it holds; [51], [52] the
+ * same for dry_tail_warm ([0], [1] are the totals) */
+__device__ __forceinline__ void dry_tail_count(bool le_dry, bool warm) {
+  const unsigned long long act = __builtin_amdgcn_ballot_w64(true), m1 = __builtin_amdgcn_ballot_w64(le_dry),
+                           m2 = __builtin_amdgcn_ballot_w64(warm);
+  if ((unsigned long long)__builtin_ctzll(act) == (unsigned long long)(threadIdx.x & 63u)) {
+    if (m1 == act) atomicAdd(&rs::g_bl_stats[49], 1ull);
+    atomicAdd(&rs::g_bl_stats[50], (unsigned long long)__builtin_popcountll(m1));
+    if (m2 == act) atomicAdd(&rs::g_bl_stats[51], 1ull);
+    atomicAdd(&rs::g_bl_stats[52], (unsigned long long)__builtin_popcountll(m2));
+  }
+}
+#endif
+#endif
+
 template <bool IEEE = false>
 __device__ __forceinline__ void bl_finish(const RS_CONSTS &c, const MathTab &mt, const BlAux &a,
                                           const BlVar &x, RS_REAL tsurf, RS_REAL tair, RS_REAL vz,
                                           RS_REAL rhz, RS_REAL wat, RS_REAL &le, RS_REAL &evap) {
+#ifdef RS_DRY_TAIL
+  /* the text below in the order the skips need: what the tests read first, what they skip last */
+  const RS_REAL raNum = (c.logMom + x.PSIM) * (c.logHeat + x.PSIH), raDen = c.VK_Const * c.VK_Const * vz;
+  const RS_REAL aa = (tair < 0) ? R4(21.875) : R4(17.269);
+  const RS_REAL ba = (tair < 0) ? R4(265.5) : R4(237.3);
+  const RS_REAL ESat = R4(0.61078) * rs_exp(mt, rs_dv<IEEE>(aa * tair, tair + ba));
+  const RS_REAL EAir = rs_min_num_one(R4(0.01) * rhz) * ESat; /* (Min's NaN rule: forcing_prep_tail) */
+  const bool signs = dry_tail_signs(wat, raNum, raDen); /* (IEEE: the guard's redo runs the whole text) */
+#ifdef RS_DRY_ESURF
+  if (!IEEE && rs_wave_all(dry_tail_warm(signs, tsurf, tair, EAir))) {
+    le = R4(0.0);
+    evap = R4(0.0);
+    return;
+  }
+#endif
+  const RS_REAL as = (tsurf < 0) ? R4(21.875) : R4(17.269);
+  const RS_REAL bs = (tsurf < 0) ? R4(265.5) : R4(237.3);
+  const RS_REAL ESurf = R4(0.61078) * rs_exp(mt, rs_dv<IEEE>(as * tsurf, tsurf + bs));
+  const RS_REAL N = a.AirDens * a.AirHCap * (ESurf - EAir);
+  if (!IEEE && rs_wave_all(dry_tail_le(signs, N, a.PsychC))) {
+    le = R4(0.0);
+    evap = R4(0.0);
+    return;
+  }
+  if (!IEEE) asm volatile(""); /* keeps the skip a branch, as in layer_vsh */
+  RS_REAL RAero = rs_dvb<IEEE>(raNum, raDen);
+  if (RAero > R4(30.0)) RAero = R4(30.);
+  le = rs_dvb<IEEE>(N, a.PsychC * RAero);
+#else /* the flavours without the skip (fp32, -DRS_NO_DRY_TAIL_SKIP): the statements in the order they had, which the
+         compiler's schedule follows - the fp32 kernels stay the machine code they were */
   RS_REAL RAero = rs_dvb<IEEE>((c.logMom + x.PSIM) * (c.logHeat + x.PSIH), c.VK_Const * c.VK_Const * vz);
   if (RAero > R4(30.0)) RAero = R4(30.);
 
@@ -216,6 +302,7 @@ __device__ __forceinline__ void bl_finish(const RS_CONSTS &c, const MathTab &mt,
   if (hum > R4(1.0)) hum = R4(1.0);
   const RS_REAL EAir = hum * ESat;
   le = rs_dvb<IEEE>(a.AirDens * a.AirHCap * (ESurf - EAir), a.PsychC * RAero);
+#endif
   /* (both latent heats read as scalars, the lane picks a value: see SetDayDependendVariables) */
   const RS_REAL lvap = c.LVap, lfus = c.LFus;
   const RS_REAL lat = (tsurf >= R4(0.0)) ? lvap : lfus;
@@ -783,9 +870,9 @@ __device__ __forceinline__ ForcingPrep forcing_prep_tail(const RS_CONSTS &c, con
   const RS_REAL aa = (tair < 0) ? R4(21.875) : R4(17.269);
   const RS_REAL ba = (tair < 0) ? R4(265.5) : R4(237.3);
   const RS_REAL ESat = R4(0.61078) * rs_exp(mt, rs_dv<false>(aa * tair, tair + ba));
-  RS_REAL hum = R4(0.01) * rhz;
-  if (hum > R4(1.0)) hum = R4(1.0);
-  q.EAir = hum * ESat;
+  /* Min((0.01*Rhz), 1.0), src/BoundaryLayer.f90:172: the compiled reference's MIN returns the other operand where
+   * one is a NaN - a NaN humidity (CheckValues lets it through) reads as saturated air - and so does v_min_f64 */
+  q.EAir = rs_min_num_one(R4(0.01) * rhz) * ESat;
   q.sw = f.sw;
   q.lw = f.lw;
   return q;
@@ -815,7 +902,9 @@ __device__ __forceinline__ Fluxes model_step_fluxes_prepped(const RS_CONSTS &c, 
   BlVar x;
   BlAux a;
   a.PsychC = q.PsychC;
-  a.WatDen = R4(-0.0050) * s.tsurf * s.tsurf + R4(0.0079) * s.tsurf + R4(1000.0028);
+#ifndef RS_DRY_TAIL /* (with the skip: in the tail, where the skip covers it) */
+  const RS_REAL WatDen = R4(-0.0050) * s.tsurf * s.tsurf + R4(0.0079) * s.tsurf + R4(1000.0028);
+#endif
   v.dT = s.tsurf - q.tair;
   v.den0 = q.den0;
   v.vkvz = q.vkvz;
@@ -902,9 +991,21 @@ __device__ __forceinline__ Fluxes model_step_fluxes_prepped(const RS_CONSTS &c, 
 #endif
   fx.trips = TRIPS == 1 ? j + (unstable ? 64 : 0) : TRIPS == 2 ? (j > RS_BL_MAXIT ? RS_BL_MAXIT : j) : 5;
   fx.blcond = x.BLCond;
-  { /* bl_finish with EAir handed over */
-    RS_REAL RAero = rs_dvb<false>((c.logMom + x.PSIM) * (c.logHeat + x.PSIH), c.VK_Const * c.VK_Const * q.vz);
-    if (RAero > R4(30.0)) RAero = R4(30.);
+  do { /* bl_finish with EAir handed over */
+    const RS_REAL raNum = (c.logMom + x.PSIM) * (c.logHeat + x.PSIH), raDen = c.VK_Const * c.VK_Const * q.vz;
+#ifdef RS_DRY_TAIL
+    const bool signs = dry_tail_signs(s.wat, raNum, raDen);
+#endif
+#ifdef RS_DRY_ESURF
+    const bool warm = dry_tail_warm(signs, s.tsurf, q.tair, q.EAir);
+#ifndef RS_BL_STATS
+    if (rs_wave_all(warm)) {
+      fx.le = R4(0.0);
+      fx.evap = R4(0.0);
+      break;
+    }
+#endif
+#endif
     const RS_REAL as = (s.tsurf < 0) ? R4(21.875) : R4(17.269);
     const RS_REAL bs = (s.tsurf < 0) ? R4(265.5) : R4(237.3);
 #ifdef RS_EXP_SURFACE_LIGHT
@@ -916,15 +1017,31 @@ __device__ __forceinline__ Fluxes model_step_fluxes_prepped(const RS_CONSTS &c, 
     const RS_REAL ESurf = R4(0.61078) * rs_exp(mt, rs_dv<false>(as * s.tsurf, s.tsurf + bs));
 #endif
     /* (AirDens x AirHCap x (...) is (AirDens x AirHCap) x (...): the product arrives as AirVCap) */
-    fx.le = rs_dvb<false>(q.AirVCap * (ESurf - q.EAir), a.PsychC * RAero);
+    const RS_REAL N = q.AirVCap * (ESurf - q.EAir);
+#ifdef RS_DRY_TAIL
+    const bool le_dry = dry_tail_le(signs, N, a.PsychC);
+#if defined(RS_BL_STATS) && defined(RS_DRY_ESURF)
+    dry_tail_count(le_dry, warm);
+#endif
+    if (rs_wave_all(le_dry)) {
+      fx.le = R4(0.0);
+      fx.evap = R4(0.0);
+      break;
+    }
+    asm volatile(""); /* keeps the skip a branch, as in layer_vsh */
+    const RS_REAL WatDen = R4(-0.0050) * s.tsurf * s.tsurf + R4(0.0079) * s.tsurf + R4(1000.0028);
+#endif
+    RS_REAL RAero = rs_dvb<false>(raNum, raDen);
+    if (RAero > R4(30.0)) RAero = R4(30.);
+    fx.le = rs_dvb<false>(N, a.PsychC * RAero);
     const RS_REAL lvap = c.LVap, lfus = c.LFus;
     const RS_REAL lat = (s.tsurf >= R4(0.0)) ? lvap : lfus;
-    fx.evap = rs_dvb<false>(fx.le, lat * a.WatDen) * R4(1000.0) * c.DTSecs;
+    fx.evap = rs_dvb<false>(fx.le, lat * WatDen) * R4(1000.0) * c.DTSecs;
     if ((fx.le > R4(0.0)) && (s.wat <= R4(0.0))) {
       fx.le = R4(0.0);
       fx.evap = R4(0.0);
     }
-  }
+  } while (false);
 #if RS_BL_GUARD && !defined(RS_IEEE_DIV) && !defined(RS_DIV_CHECK) && !defined(RS_NO_BL_GUARD) && !defined(RS_BL_FIXUP)
   if (!(rs_fabs(fx.blcond) < __builtin_inf()) || !(rs_fabs(fx.le) < __builtin_inf())) {
     const BlOut o = boundary_layer_ieee(&c, mt.expT, mt.logT, mt.K, s.tsurf, q.tair, q.vz, q.rhz, s.wat);

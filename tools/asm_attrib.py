@@ -89,6 +89,16 @@ REGIONS = [
     ("rs_log", None, None, "boundary-layer pass: unstable arm, log (two paths, one taken)"),
     ("model_step_fluxes_prepped", "boundary_layer_ieee", None, "guard (IEEE redo, out of line)"),
     ("model_step_fluxes_prepped", "__builtin_inf", None, "ESurf / fluxes"),
+    ("dry_tail_signs", None, None, "CalcLE: dry-tail tests"),
+    ("dry_tail_le", None, None, "CalcLE: dry-tail tests"),
+    ("dry_tail_warm", None, None, "CalcLE: dry-tail tests"),
+    ("model_step_fluxes_prepped", "rs_wave_all", None, "CalcLE: dry-tail tests"),
+    ("model_step_fluxes_prepped", "RAero", None, "CalcLE: tail (skipped where every lane is dry and evaporating)"),
+    ("model_step_fluxes_prepped", "WatDen", None, "CalcLE: tail (skipped where every lane is dry and evaporating)"),
+    ("model_step_fluxes_prepped", "lfus", None, "CalcLE: tail (skipped where every lane is dry and evaporating)"),
+    ("model_step_fluxes_prepped", "fx.le > ", None, "CalcLE: tail (skipped where every lane is dry and evaporating)"),
+    ("model_step_fluxes_prepped", "ESurf", None, "CalcLE: ESurf (skipped where every lane is dry and warmer than the air)"),
+    ("model_step_fluxes_prepped", "s.tsurf < 0", None, "CalcLE: ESurf (skipped where every lane is dry and warmer than the air)"),
     ("bl_iteration", "rs_log", None, "boundary-layer pass: unstable arm"),
     ("bl_iteration", "PSIM = R4(0.6)", None, "boundary-layer pass: unstable arm"),
     ("bl_iteration", None, None, "boundary-layer pass"),
@@ -136,6 +146,10 @@ WEIGHTS = {
     "boundary-layer pass: unstable arm, log (two paths, one taken)": 0.367,
     "layers 1-2: thawed arm": THAWED, "layers 3-15: thawed arm": THAWED,
     "layers 1-2: frozen arm": 1.0 - THAWED, "layers 3-15: frozen arm": 1.0 - THAWED,
+    # profiles/r09_dry_tail_counts.txt: every lane dry and evaporating in 0.6458 of the wave-steps, dry and warmer than
+    # the air by the margin in 0.4406
+    "CalcLE: tail (skipped where every lane is dry and evaporating)": 1.0 - 0.6458,
+    "CalcLE: ESurf (skipped where every lane is dry and warmer than the air)": 1.0 - 0.4406,
     "melting": 0.10,
     "storages": 1.0 - 0.615,            # the bare-road shortcut takes 61.5 % of the wave-steps
     "albedo": 1.0 - 0.615,

@@ -1,6 +1,6 @@
 """What a wavefront of the step kernel pays for on a workload: boundary-layer passes (the wavefront's trip count is
-its slowest lane's), which of road_condition's storage blocks any lane needs, how often the precipitation branch
-runs.  Experiment build `make -C roadsurf_amd blstats` (counters in rs_math.hpp g_bl_stats, read by
+its slowest lane's), which of road_condition's storage blocks any lane needs, how often CalcLE's tail is discarded
+by the reference in every lane (the dry-tail tests of rs_physics_body.inc), how often the precipitation branch runs.  Experiment build `make -C roadsurf_amd blstats` (counters in rs_math.hpp g_bl_stats, read by
 rs_hip_bl_stats); the product build carries none of this.
 usage: wave_stats.py bench|bench-full|driver-relax|driver-coupling [points] [hours]"""
 import ctypes as C, os, sys
@@ -49,5 +49,7 @@ rc = max(out[10], 1)
 print(f"  road_condition: {out[10]} wave-steps; bare-road shortcut {out[11] / rc:.4f}; every lane without snow {out[12] / rc:.4f}, "
       f"without ice {out[13] / rc:.4f}, without deposit or condensation {out[14] / rc:.4f}, without water {out[15] / rc:.4f}, "
       f"without snow, ice and deposit {out[16] / rc:.4f}")
+print(f"  CalcLE's tail: the reference zeroes le and evap by sign (dry_tail_le) in every lane of {out[49] / ws:.4f} of the wave-steps, "
+      f"{out[50] / ls:.4f} of the lane-steps; warm dry surface (dry_tail_warm) in every lane of {out[51] / ws:.4f}, {out[52] / ls:.4f} of the lane-steps")
 fp = max(out[17], 1)
 print(f"  forcing's share: {out[17]} wave-steps, precipitation branch in {out[18] / fp:.4f}")

@@ -802,6 +802,61 @@ int rs_hip_outputs_groups(RsPlan *plan, const RsOutputs *src, int32_t nrows, con
                           const int32_t *order_device, const RsGroupSpec *spec, double *acc_device, int64_t acc_rows,
                           int64_t acc_row0, void *stream);
 
+/* Per-station ensemble statistics, reduced from the member rows on the device (the ABI number stays: every name here
+ * is new, a binding detects them with rs_hip_ens_cols).  The group series above hold counts and extremes only, so that
+ * atomics stay exact; a mean, a spread and percentiles equal a definition bit for bit only if the members of a station
+ * are visited in ONE fixed order and every operation is rounded on its own.  That order is a table of the caller's:
+ * rs_ens_member_table (host only, no device) turns group_host[npoints] (int32, POINT order; an id outside [0, ngroups)
+ * belongs to no station) into table_host[rs_ens_table_ints = ngroups + 1 + npoints]:
+ *     table[0 .. ngroups]            start[g]: station g's members are the entries start[g] .. start[g + 1] - 1 of
+ *     table[ngroups + 1 + e]         the member list, e in [0, npoints): the points of station 0, of station 1, ...,
+ *                                    each station's in ascending point index; the unused tail is -1
+ * and returns -1, rs_last_error naming the first such station, where a station has more than spec.max_members members.
+ * The caller uploads the table.  rs_hip_outputs_ens reads the first `nrows` rows of a window `src` ([row][slot], of
+ * any launch and any flavour; float arrays on an fp32 plan, widened exactly; all arithmetic is fp64) and WRITES
+ *     acc_device[((acc_row0 + r) * ngroups + g) * cols + col],   double,   cols = rs_hip_ens_cols = RS_ENS_COLS + nquant
+ * A member is VALID at a row iff its Tsurf is not exactly -9999.0 and USED iff it is valid and its Tsurf is not NaN;
+ * with the k used members of g in table order, x_0 .. x_{k-1} their Tsurf:
+ *   0       number of valid members
+ *   1       k
+ *   2       mean Tsurf (((x_0 + x_1) + x_2) + ...) / k: every addition rounded on its own, one division
+ *   3       spread sqrt(((d_0*d_0 + d_1*d_1) + ...) / k), d_j = x_j - mean: the population form, every product, sum,
+ *           the division and the root rounded on their own
+ *   4..8    mean of Snow, Water, Ice, Deposit, Ice2 over the USED members, summed the same way; a NaN storage of a used
+ *           member makes that one mean NaN and nothing else
+ *   9 + j   quantile spec.quant[j] (each in [0, 1], strictly increasing, nquant <= RS_ENS_MAX_QUANT) of the used Tsurf
+ *           sorted ascending to y: h = q * (k - 1), lo = floor(h), hi = min(lo + 1, k - 1), t = h - lo, the value
+ *           y[lo] + t * (y[hi] - y[lo]), every operation rounded on its own
+ * k = 0: columns 2 and above are -9999.0.  roadsurf_amd/ensstats.py (reduce_members) is the definition in numpy, and
+ * the tests hold the device to it exactly.  A cell is complete in one call - every member of a station lives in THIS
+ * plan - so the call writes and never merges: every station's cell of every fed row is written, the empty one
+ * included, rows outside [acc_row0, acc_row0 + nrows) are not touched, and there is no reset.  A station whose members
+ * are spread over several plans or devices is not supported (documented, not detected).
+ * `order_device` and `stream` as for rs_hip_outputs_groups.  `work_device`: int32[npoints_padded] of the caller's; the
+ * call fills it, on the same stream, with the inverse of the order row it resolved (point -> slot) and leaves its
+ * contents unspecified.  No state is hidden in the plan, so calls on different streams (with a work row each) cannot
+ * race.  Refused, with nothing launched: null arguments or nrows < 1; a bad spec; rows outside acc_rows; a missing
+ * stream of the six; t_stride below the plan's points; a stream of the caller's without a kept order row; no
+ * work_device.  A table that rs_ens_member_table did not make may give unspecified cells, never an access out of
+ * bounds: the kernel reads the table's ngroups + 1 + npoints ints and the window's columns [0, npoints) only, clamps a
+ * segment to max_members and to the table, and an entry or an inverse outside [0, npoints) contributes nothing.
+ * The kernel uses no atomics: a workgroup takes 64 consecutive stations, brings their members' values of one row and
+ * variable together in LDS (65 * max_members doubles per wavefront, each wavefront rows of its own), and lane g owns
+ * station g.  tools/bench_ensemble_stats.py measures the cost (its output is kept as profiles/ensemble_stats.txt). */
+#define RS_ENS_MAX_MEMBERS 64
+#define RS_ENS_MAX_QUANT 8
+#define RS_ENS_COLS 9
+typedef struct RsEnsSpec {
+  int32_t ngroups, max_members, nquant;
+  double quant[RS_ENS_MAX_QUANT];
+} RsEnsSpec;
+int32_t rs_hip_ens_cols(const RsEnsSpec *spec); /* RS_ENS_COLS + nquant; <0: bad spec (host only) */
+int64_t rs_ens_table_ints(int32_t npoints, const RsEnsSpec *spec); /* ngroups + 1 + npoints; <0: bad spec */
+int rs_ens_member_table(int32_t npoints, const int32_t *group_host, const RsEnsSpec *spec, int32_t *table_host);
+int rs_hip_outputs_ens(RsPlan *plan, const RsOutputs *src, int32_t nrows, const int32_t *table_device,
+                       const int32_t *order_device, const RsEnsSpec *spec, double *acc_device, int64_t acc_rows,
+                       int64_t acc_row0, int32_t *work_device, void *stream);
+
 /* Per-point threshold episodes, reduced from the output rows on the device (the ABI number stays: every name here is
  * new, a binding detects them with rs_hip_episode_cols).  The summaries say how cold, when first below a threshold and
  * for how many rows; a surface that thaws at midday and refreezes at night has several intervals, and only the series

@@ -19,6 +19,7 @@
 
 #include "../../include/roadsurf.h"
 #include "rs_kernels.h"
+#include "rs_ens_table.hpp"
 #include "rs_devutil.hpp"
 #include <cstdint>
 #include <algorithm>
@@ -577,6 +578,35 @@ int rs_hip_outputs_groups(RsPlan *pl, const RsOutputs *src, int32_t nrows, const
   if (rows_prologue(pl, src, order, stream, "rs_hip_outputs_groups", on)) return -1;
   HIP_OK(rs_cluster_outputs_groups(on.in, pl->f32, on.order, group, pl->npoints, src->t_stride, nrows, *spec,
                                    acc + acc_row0 * spec->ngroups * cols, on.stream));
+  return 0;
+}
+
+int32_t rs_hip_ens_cols(const RsEnsSpec *spec) { return rs_ens::cols(spec); }
+int64_t rs_ens_table_ints(int32_t npoints, const RsEnsSpec *spec) { return rs_ens::table_ints(npoints, spec); }
+
+int rs_ens_member_table(int32_t npoints, const int32_t *group, const RsEnsSpec *spec, int32_t *table) {
+  return rs_ens::member_table(npoints, group, spec, table, g_err, sizeof(g_err));
+}
+
+int rs_hip_outputs_ens(RsPlan *pl, const RsOutputs *src, int32_t nrows, const int32_t *table, const int32_t *order,
+                       const RsEnsSpec *spec, double *acc, int64_t acc_rows, int64_t acc_row0, int32_t *work,
+                       void *stream) {
+  if (!pl || !src || !table || !spec || !acc || nrows < 1)
+    return set_err("rs_hip_outputs_ens: bad arguments (nrows >= 1 rows, a member table, a spec and an accumulator)");
+  const int32_t cols = rs_ens::cols(spec);
+  if (cols < 0)
+    return set_err("rs_hip_outputs_ens: bad spec (ngroups >= 1, 1 <= max_members <= RS_ENS_MAX_MEMBERS, at most "
+                   "RS_ENS_MAX_QUANT quantiles in [0, 1], strictly increasing)");
+  if (acc_row0 < 0 || acc_rows < 1 || acc_row0 > acc_rows - nrows)
+    return set_err("rs_hip_outputs_ens: rows [acc_row0, acc_row0 + nrows) outside the accumulator's acc_rows");
+  if (!work) return set_err("rs_hip_outputs_ens: work_device is required (int32[npoints_padded] of the caller's)");
+  RowsOn on;
+  if (rows_prologue(pl, src, order, stream, "rs_hip_outputs_ens", on)) return -1;
+  /* where every point sits in the order row the window was stepped in; a point the row does not name has no slot */
+  HIP_OK(hipMemsetAsync(work, 0xff, (size_t)pl->npoints * sizeof(int32_t), on.stream));
+  HIP_OK(rs_cluster_inverse(on.order, pl->npoints, work, on.stream));
+  HIP_OK(rs_cluster_outputs_ens(on.in, pl->f32, table, work, pl->npoints, src->t_stride, nrows, *spec,
+                                acc + acc_row0 * spec->ngroups * cols, on.stream));
   return 0;
 }
 

@@ -8,6 +8,7 @@
 
 #include <algorithm>
 
+#include "rs_ens_table.hpp"
 #include "rs_kernels.h"
 #include "rs_state.h"
 
@@ -712,6 +713,255 @@ hipError_t rs_cluster_outputs_groups(const void *const src[6], bool f32, const i
     else
       hipLaunchKernelGGL(groups_global_kernel<double>, grid, dim3(GRP_THREADS), 0, stream, a);
   }
+  return hipGetLastError();
+}
+
+/* Per-station ensemble statistics of the output rows (include/roadsurf.h, rs_hip_outputs_ens; the definition is
+ * roadsurf_amd/ensstats.py, reduce_members): the third reducer over the slots of a row, and of another shape than the
+ * group series - a mean, a spread and quantiles equal their definition only if a station's members are summed in one
+ * fixed order, which rules atomics out.  A workgroup takes 64 consecutive stations; the member list of the table gives
+ * it one contiguous segment of at most 64 * max_members entries, which it resolves ONCE to slots (entry -> point ->
+ * inv[point]) and keeps in LDS, each beside its place in a wavefront's row.  Each wavefront then takes rows of its own
+ * (only wave-level synchronisation from there on): per row and variable its lanes run over the segment's ENTRIES and
+ * load win[row][slot] - whole lines while members sit side by side, gathers after a re-sort - into the wavefront's LDS
+ * row, which is MEMBER-major: position j of station g at j * ENS_ROW + g.  Then lane g owns station g and walks its
+ * column in table order, the 64 lanes on 64 consecutive doubles; ENS_ROW = 65, one double of padding, keeps the
+ * staging's scattered writes - consecutive entries are consecutive members of ONE station - out of each other's
+ * banks too.  The Tsurf pass builds the used mask (64 bits: at most 64 members), compacts the used values to the top
+ * of the column and sums them on the way, forms mean and squared deviations, sorts the column in place (insertion
+ * sort: at most 64 values) and takes the quantiles; the five storage passes re-stage and sum under the mask.  No
+ * member value lives in an indexed register array (it would be scratch), every offset is 64 bits, and a damaged table
+ * cannot lead outside the table, the window or LDS: a segment is clamped to max_members and to the member list, the
+ * workgroup's entries are laid out by a scan of the CLAMPED counts, and an entry or an inverse outside [0, npoints) is
+ * a slot of -1, which loads nothing. */
+namespace {
+constexpr int ENS_MAX_WAVES = 4;          /* rows in flight per workgroup */
+constexpr int ENS_LDS_BUDGET = 64 * 1024; /* per workgroup: two or more workgroups to a CU's 160 KiB */
+constexpr int ENS_LOADS = 16;             /* loads a lane has in flight while it stages a row */
+constexpr int ENS_ROW = 65;               /* doubles per member position of a wavefront's row: 64 stations, one pad */
+
+struct EnsArgs {
+  const void *src[6];   /* T[nrows][stride] each: Tsurf, Snow, Water, Ice, Deposit, Ice2 */
+  const int32_t *table; /* [ngroups + 1] starts, [npoints] entries (rs_ens_table.hpp) */
+  const int32_t *inv;   /* [npoints]: the slot of a point */
+  double *acc;          /* [nrows][ngroups][cols]: row acc_row0 of the caller's accumulator */
+  int64_t npoints, stride;
+  int32_t nrows, ngroups, max_members, nquant, cols, rows_per_block, waves;
+  double quant[RS_ENS_MAX_QUANT];
+};
+
+/* the lanes of ONE wavefront hand LDS values to each other: its LDS accesses execute in program order, so this orders
+ * them for the compiler and waits for nothing another wavefront did */
+__device__ __forceinline__ void ens_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+/* one variable of one row into the wavefront's LDS row, entry by entry, ENS_LOADS loads in flight per lane: the
+ * wavefronts of a CU are few (LDS), so the loads a lane keeps in flight are what hides the memory's latency - and
+ * with so few wavefronts the registers are there */
+template <typename T>
+__device__ __forceinline__ void ens_stage(const T *__restrict__ src, const int32_t *slot, const uint16_t *place,
+                                          int32_t total, int lane, double *val) {
+#pragma unroll 1
+  for (int32_t i0 = lane; i0 < total; i0 += 64 * ENS_LOADS) {
+    double v[ENS_LOADS];
+#pragma unroll
+    for (int q = 0; q < ENS_LOADS; ++q) {
+      const int32_t i = i0 + 64 * q;
+      const int32_t s = i < total ? slot[i] : -1;
+      v[q] = s >= 0 ? (double)src[s] : -9999.0; /* no such member: invalid, and under no mask */
+    }
+#pragma unroll
+    for (int q = 0; q < ENS_LOADS; ++q) {
+      const int32_t i = i0 + 64 * q;
+      if (i < total) val[place[i]] = v[q];
+    }
+  }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(64 * ENS_MAX_WAVES) ens_stats_kernel(const EnsArgs a) {
+  /* [waves][max_members][ENS_ROW] values; then per entry of the segment, [64 * max_members] each: its slot (int32)
+   * and its place in a wavefront's row (uint16) */
+  extern __shared__ double ens_lds[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int32_t seg = 64 * a.max_members, row_len = ENS_ROW * a.max_members;
+  double *val = ens_lds + (int64_t)wave * row_len;
+  int32_t *slot = reinterpret_cast<int32_t *>(ens_lds + (int64_t)a.waves * row_len);
+  uint16_t *place = reinterpret_cast<uint16_t *>(slot + seg);
+  const int64_t g = (int64_t)blockIdx.x * 64 + lane;
+  const bool live = g < a.ngroups;
+  /* the station's segment of the member list, clamped to max_members and to the list */
+  int32_t first = 0, cnt = 0;
+  if (live) {
+    const int64_t s0 = a.table[g], s1 = a.table[g + 1];
+    if (s0 >= 0 && s0 < a.npoints && s1 > s0) {
+      int64_t c = s1 - s0;
+      if (c > a.max_members) c = a.max_members;
+      if (c > a.npoints - s0) c = a.npoints - s0;
+      first = (int32_t)s0;
+      cnt = (int32_t)c;
+    }
+  }
+  /* where the station's entries begin in the workgroup's segment: the scan of the clamped counts (every wavefront
+   * of the workgroup reads the same table and gets the same layout) */
+  int32_t incl = cnt;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int32_t u = __shfl_up(incl, d, 64);
+    if (lane >= d) incl += u;
+  }
+  const int32_t off = incl - cnt, total = __shfl(incl, 63, 64);
+  /* entries to slots, once: wavefront w resolves the member positions w, w + waves, ... of every station */
+  const int32_t *entry = a.table + ((int64_t)a.ngroups + 1);
+  for (int32_t j = wave; j < cnt; j += a.waves) {
+    const int64_t p = entry[(int64_t)first + j];
+    int32_t s = -1;
+    if (p >= 0 && p < a.npoints) {
+      const int64_t q = a.inv[p];
+      if (q >= 0 && q < a.npoints) s = (int32_t)q;
+    }
+    slot[off + j] = s;
+    place[off + j] = (uint16_t)(j * ENS_ROW + lane);
+  }
+  __syncthreads();
+
+  const int32_t r_lo = (int32_t)blockIdx.y * a.rows_per_block,
+                r_hi = a.nrows - r_lo < a.rows_per_block ? a.nrows : r_lo + a.rows_per_block;
+  double *x = val + lane; /* the station's column: position j at x[j * ENS_ROW], cnt of them */
+#pragma unroll 1
+  for (int32_t r = r_lo + wave; r < r_hi; r += a.waves) {
+    double *cell = a.acc + ((int64_t)r * a.ngroups + g) * a.cols;
+    ens_wave_sync(); /* (every lane is done with the row before) */
+    ens_stage<T>(static_cast<const T *>(a.src[0]) + (int64_t)r * a.stride, slot, place, total, lane, val);
+    ens_wave_sync();
+    /* Tsurf: the used mask; the used values to the top of the column in table order, and their sum on the way */
+    uint64_t used = 0;
+    int32_t nvalid = 0, k = 0;
+    double sum = 0.0;
+    for (int32_t j = 0; j < cnt; ++j) {
+      const double t = x[j * ENS_ROW];
+      const bool ok = t != -9999.0;
+      nvalid += ok ? 1 : 0;
+      if (ok && t == t) {
+        used |= 1ull << j;
+        sum = k ? __dadd_rn(sum, t) : t;
+        x[k * ENS_ROW] = t;
+        ++k;
+      }
+    }
+    const double kd = (double)k;
+    double mean = -9999.0, spread = -9999.0;
+    if (k > 0) {
+      mean = sum / kd;
+      double d = __dsub_rn(x[0], mean);
+      double q = __dmul_rn(d, d);
+      for (int32_t j = 1; j < k; ++j) {
+        d = __dsub_rn(x[j * ENS_ROW], mean);
+        q = __dadd_rn(q, __dmul_rn(d, d));
+      }
+      spread = ::sqrt(q / kd);
+      for (int32_t i = 1; i < k; ++i) { /* ascending, in place */
+        const double v = x[i * ENS_ROW];
+        int32_t j = i;
+        while (j > 0 && x[(j - 1) * ENS_ROW] > v) {
+          x[j * ENS_ROW] = x[(j - 1) * ENS_ROW];
+          --j;
+        }
+        x[j * ENS_ROW] = v;
+      }
+    }
+    if (live) {
+      cell[0] = (double)nvalid;
+      cell[1] = kd;
+      cell[2] = mean;
+      cell[3] = spread;
+      for (int32_t c = 0; c < a.nquant; ++c) {
+        double v = -9999.0;
+        if (k > 0) {
+          const double h = __dmul_rn(a.quant[c], (double)(k - 1));
+          int32_t lo = (int32_t)h; /* floor: h >= 0 */
+          lo = lo < 0 ? 0 : lo > k - 1 ? k - 1 : lo;
+          const int32_t hi = lo + 1 < k - 1 ? lo + 1 : k - 1;
+          const double t = __dsub_rn(h, (double)lo);
+          const double ylo = x[lo * ENS_ROW];
+          v = __dadd_rn(ylo, __dmul_rn(t, __dsub_rn(x[hi * ENS_ROW], ylo)));
+        }
+        cell[RS_ENS_COLS + c] = v;
+      }
+    }
+    /* the storages of the used members, summed in table order */
+#pragma unroll 1
+    for (int f = 1; f < 6; ++f) {
+      ens_wave_sync();
+      ens_stage<T>(static_cast<const T *>(a.src[f]) + (int64_t)r * a.stride, slot, place, total, lane, val);
+      ens_wave_sync();
+      double m = -9999.0;
+      if (k > 0) {
+        double s = 0.0;
+        bool none = true;
+        for (int32_t j = 0; j < cnt; ++j) {
+          if (!((used >> j) & 1ull)) continue;
+          s = none ? x[j * ENS_ROW] : __dadd_rn(s, x[j * ENS_ROW]);
+          none = false;
+        }
+        m = s / kd;
+      }
+      if (live) cell[3 + f] = m;
+    }
+  }
+}
+}  // namespace
+
+int32_t rs_cluster_ens_waves(const RsEnsSpec *sp) {
+  if (rs_ens::cols(sp) < 0) return -1;
+  /* per entry of the 64 stations an int32 slot and a uint16 place; per wavefront a row of ENS_ROW * max_members */
+  const int32_t entries = 64 * sp->max_members * (int32_t)(sizeof(int32_t) + sizeof(uint16_t)),
+                row = ENS_ROW * sp->max_members * (int32_t)sizeof(double);
+  return std::max(1, std::min(ENS_MAX_WAVES, (ENS_LDS_BUDGET - entries) / row));
+}
+
+size_t rs_cluster_ens_lds_bytes(const RsEnsSpec *sp) {
+  const int32_t waves = rs_cluster_ens_waves(sp);
+  if (waves < 0) return 0;
+  return (size_t)sp->max_members * ((size_t)waves * ENS_ROW * sizeof(double) + 64 * (sizeof(int32_t) + sizeof(uint16_t)));
+}
+
+hipError_t rs_cluster_outputs_ens(const void *const src[6], bool f32, const int32_t *table, const int32_t *inv,
+                                  int64_t npoints, int64_t src_stride, int32_t nrows, const RsEnsSpec &spec,
+                                  double *acc_row0, hipStream_t stream) {
+  const int32_t waves = rs_cluster_ens_waves(&spec);
+  if (waves < 0 || nrows < 1 || npoints < 1) return hipErrorInvalidValue;
+  EnsArgs a;
+  for (int f = 0; f < 6; ++f) a.src[f] = src[f];
+  a.table = table;
+  a.inv = inv;
+  a.acc = acc_row0;
+  a.npoints = npoints;
+  a.stride = src_stride;
+  a.nrows = nrows;
+  a.ngroups = spec.ngroups;
+  a.max_members = spec.max_members;
+  a.nquant = spec.nquant;
+  a.cols = rs_ens::cols(&spec);
+  a.waves = waves;
+  for (int j = 0; j < RS_ENS_MAX_QUANT; ++j) a.quant[j] = j < spec.nquant ? spec.quant[j] : 0.0;
+  /* the stations give the grid's x, blocks of rows its y: about six thousand workgroups in all - several rounds of
+   * what the chip holds at once, so that the last round is a small part - each with a whole number of rows per
+   * wavefront, since it resolves its segment before its first row */
+  const int64_t station_blocks = ((int64_t)spec.ngroups + 63) / 64;
+  const int64_t want_row_blocks = std::max<int64_t>(1, 6144 / station_blocks);
+  const int64_t rows_each = std::max<int64_t>(1, ((int64_t)nrows + want_row_blocks - 1) / want_row_blocks);
+  a.rows_per_block = (int32_t)std::min<int64_t>(INT32_MAX / 2, (rows_each + waves - 1) / waves * waves);
+  const int64_t row_blocks = ((int64_t)nrows + a.rows_per_block - 1) / a.rows_per_block;
+  const dim3 grid((unsigned)station_blocks, (unsigned)row_blocks);
+  const size_t lds = rs_cluster_ens_lds_bytes(&spec);
+  if (f32)
+    hipLaunchKernelGGL(ens_stats_kernel<float>, grid, dim3(64 * waves), lds, stream, a);
+  else
+    hipLaunchKernelGGL(ens_stats_kernel<double>, grid, dim3(64 * waves), lds, stream, a);
   return hipGetLastError();
 }
 

@@ -187,6 +187,15 @@ hipError_t rs_cluster_group_reset(double *acc, int64_t acc_rows, const RsGroupSp
 hipError_t rs_cluster_outputs_groups(const void *const src[6], bool f32, const int32_t *order, const int32_t *group,
                                      int64_t npoints, int64_t src_stride, int32_t nrows, const RsGroupSpec &spec,
                                      double *acc_row0, hipStream_t stream);
+/* per-station ensemble statistics of output rows (rs_hip_outputs_ens): acc_row0[nrows][ngroups][cols] is WRITTEN;
+ * table[ngroups + 1 + npoints] as rs_ens_member_table makes it (rs_ens_table.hpp), inv[npoints] the inverse of the
+ * order row the window was stepped in (rs_cluster_inverse), src as above.  rs_cluster_ens_waves: the wavefronts per
+ * workgroup the host chooses from max_members alone (<0: bad spec), rs_cluster_ens_lds_bytes: the workgroup's LDS */
+int32_t rs_cluster_ens_waves(const RsEnsSpec *spec);
+size_t rs_cluster_ens_lds_bytes(const RsEnsSpec *spec);
+hipError_t rs_cluster_outputs_ens(const void *const src[6], bool f32, const int32_t *table, const int32_t *inv,
+                                  int64_t npoints, int64_t src_stride, int32_t nrows, const RsEnsSpec &spec,
+                                  double *acc_row0, hipStream_t stream);
 /* per-point threshold episodes of output rows (rs_hip_outputs_episodes): acc[cols][np_pad] in point order; src and
  * order as above, deficit: a seventh window of the same layout and type, or NULL.  rs_cluster_episode_cols checks the
  * spec (<0: bad) */

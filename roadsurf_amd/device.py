@@ -442,6 +442,65 @@ class Plan:
         assert spec is None or a.shape[1:] == (int(spec.ngroups), lib.group_cols(spec))
         return a
 
+    def _ens_spec(self, spec):
+        if not hasattr(self.L, "rs_hip_ens_cols"):
+            raise RuntimeError("this libroadsurf_hip.so has no ensemble statistics (rs_hip_ens_cols)")
+        sp = lib.ens_spec(spec)
+        return sp, lib.ens_cols(sp)
+
+    def ens_table(self, group, spec) -> torch.Tensor:
+        """The member table of ``group`` - int32 [npoints] on the HOST (numpy or a CPU tensor), every point's station
+        in POINT order - built by the library (rs_ens_member_table; roadsurf_amd/ensstats.py, member_table, defines
+        it) and uploaded: int32 [ngroups + 1 + npoints] on this device, what ``outputs_ens`` reads.  A station with
+        more than ``spec.max_members`` members is refused.  Also makes the plan's work row for ``outputs_ens``."""
+        import numpy as np
+        sp, _ = self._ens_spec(spec)
+        if torch.is_tensor(group):
+            if group.is_cuda:
+                raise ValueError("ens_table: group is a HOST array (numpy or a CPU tensor)")
+            group = group.numpy()
+        gid = np.asarray(group)
+        if gid.dtype.kind not in "iu" or gid.shape != (self.npoints,):
+            raise ValueError(f"ens_table: group must be {self.npoints} integers, one per point of this plan")
+        gid = np.ascontiguousarray(np.clip(gid, -1, 2**31 - 1), dtype=np.int32)   # (beyond int32: no station either)
+        table = np.empty(int(self.L.rs_ens_table_ints(self.npoints, C.byref(sp))), np.int32)
+        lib.check(self.L.rs_ens_member_table(self.npoints, C.c_void_p(gid.ctypes.data), C.byref(sp),
+                                             C.c_void_p(table.ctypes.data)), "rs_ens_member_table")
+        if getattr(self, "_ens_work", None) is None:
+            self._ens_work = torch.empty((self.np_pad,), dtype=torch.int32, device=self.device)
+        return torch.from_numpy(table).to(self.device)
+
+    def outputs_ens(self, out: "OutputWindow", nrows: int, table: torch.Tensor, spec, acc: torch.Tensor,
+                    acc_row0: int, order=None, stream: torch.cuda.Stream | None = None, row: int = 0,
+                    work: torch.Tensor | None = None) -> None:
+        """Rows ``row .. row + nrows - 1`` of the output window, [row][slot], reduced per station and WRITTEN to rows
+        ``acc_row0 ..`` of ``acc`` [rows, ngroups, cols] (rs_hip_outputs_ens; roadsurf_amd/ensstats.py defines the
+        cells).  ``table``: what ``ens_table`` returned; ``spec``: ensstats.EnsSpec; ``order`` and ``stream`` as for
+        ``outputs_by_point``.  ``work``: int32 [np_pad] scratch on this device, default the plan's own row (made by
+        ``ens_table``) - calls on different streams need a row each."""
+        sp, cols = self._ens_spec(spec)
+        assert acc.dtype == torch.float64 and acc.dim() == 3 and acc.is_contiguous()
+        assert acc.shape[1:] == (int(sp.ngroups), cols)
+        assert table.dtype == torch.int32 and table.is_contiguous()
+        assert table.numel() >= int(sp.ngroups) + 1 + self.npoints
+        if work is None:
+            if getattr(self, "_ens_work", None) is None:
+                self._ens_work = torch.empty((self.np_pad,), dtype=torch.int32, device=self.device)
+            work = self._ens_work
+        assert work.dtype == torch.int32 and work.numel() >= self.np_pad and work.is_contiguous()
+        o = out.struct_from(row)
+        lib.check(self.L.rs_hip_outputs_ens(self._h, C.byref(o), int(nrows), C.c_void_p(table.data_ptr()), _ptr(order),
+                                            C.byref(sp), C.c_void_p(acc.data_ptr()), int(acc.shape[0]), int(acc_row0),
+                                            C.c_void_p(work.data_ptr()), _stream_ptr(stream)), "rs_hip_outputs_ens")
+
+    def ens(self, acc: torch.Tensor, spec=None):
+        """``acc`` as the numpy array [rows, ngroups, cols] that ensstats.reduce_members returns (synchronises)."""
+        if not hasattr(self.L, "rs_hip_ens_cols"):
+            raise RuntimeError("this libroadsurf_hip.so has no ensemble statistics (rs_hip_ens_cols)")
+        a = acc.cpu().numpy()
+        assert spec is None or a.shape[1:] == (int(spec.ngroups), lib.ens_cols(spec))
+        return a
+
     def gather_nodes(self, src: torch.Tensor, node: torch.Tensor, weight: torch.Tensor, dst: torch.Tensor,
                      present_above: float, missing: float = -9999.9, n_nodes: int | None = None, order=None,
                      stream: torch.cuda.Stream | None = None) -> None:

@@ -79,7 +79,7 @@ def member_locals(station_local, member_local, parent):
     return out
 
 
-def check(S, L, B, settings, station_local, member_local, parent, precision=64, recluster=False) -> None:
+def check(S, L, B, settings, station_local, member_local, parent, precision=64, recluster=False, stats=None) -> None:
     """The refusals of ``run_ensemble`` (ValueError), all of them before any device work."""
     if not 1 <= B <= L - 1:
         raise ValueError(f"run_ensemble: B = {B} outside [1, L - 1 = {L - 1}]: both the analysis and the members "
@@ -89,6 +89,15 @@ def check(S, L, B, settings, station_local, member_local, parent, precision=64, 
         raise ValueError(f"run_ensemble: parent must name stations in [0, {S})")
     if precision not in (32, 64):
         raise ValueError("run_ensemble: precision is 32 or 64")
+    if stats is not None:
+        from . import ensstats
+        if int(stats.ngroups) != S:
+            raise ValueError(f"run_ensemble: stats.ngroups = {int(stats.ngroups)}, but there are S = {S} stations: the "
+                             "statistics are per station")
+        try:
+            ensstats.member_table(parent, stats)   # (and the spec's own limits)
+        except ValueError as e:
+            raise ValueError(f"run_ensemble: stats: {e}") from None
     coupled = settings.use_coupling == 1
     if coupled and precision == 32:
         raise ValueError("run_ensemble: coupling is fp64 only (the time-chunked coupling calls need the fp64 flavour)")
@@ -115,7 +124,7 @@ class _Leg:
     """One plan and the rows of forcing it steps: row r of its windows is time index ``first + r``."""
 
     def __init__(self, n, first, forcing, hour, settings, params, local, need_full, precision, variant, recluster,
-                 device, tbottom_date, groups=None, sky=None):
+                 device, tbottom_date, groups=None, sky=None, stats=None):
         import ctypes as C
         import torch
         from . import device as dv, lib
@@ -192,6 +201,12 @@ class _Leg:
             self.gid = torch.from_numpy(np.ascontiguousarray(groups[1], dtype=np.int32)).to(dev)
             assert self.gid.shape == (n,)
             self.gacc = plan.groups_reset(nrows, self.gspec)
+        self.espec = self.etab = self.eacc = None
+        if stats is not None:  # (stats: the spec and the station of every point; a cell is written, so no reset)
+            self.espec = stats[0]
+            self.etab = plan.ens_table(np.ascontiguousarray(stats[1], dtype=np.int32), self.espec)
+            self.eacc = torch.empty((nrows, int(self.espec.ngroups), lib.ens_cols(self.espec)), dtype=torch.float64,
+                                    device=dev)
 
     def _window(self, tens, hour, sun, nrows):
         tens = dict(tens, hour=hour)
@@ -233,6 +248,8 @@ class _Leg:
         getattr(plan, call)(win, out, pp, t0, ns, window_row=wrow, out_row0=orow0)
         if self.gacc is not None and call != "cpl_replay":
             plan.outputs_groups(out, ns, self.gid, self.gspec, self.gacc, r0, row=srow)
+        if self.eacc is not None and call != "cpl_replay":
+            plan.outputs_ens(out, ns, self.etab, self.espec, self.eacc, r0, row=srow)
         if self.recluster:
             for k in dv.OUT_FIELDS:
                 self.out.tensors[k][r0:r0 + ns].index_copy_(1, order, out.tensors[k])
@@ -253,7 +270,7 @@ class _Leg:
 def run_ensemble(station_forcing: dict, member_tail: dict, B: int, settings: abi.InputSettings,
                  params: abi.InputParameters, station_local, member_local=None, parent=None, chunk: int = 0,
                  variant: int = 0, precision: int = 64, recluster: bool = False, groups=None, device: int = 0,
-                 timing: dict | None = None):
+                 timing: dict | None = None, stats=None):
     """Step ``S`` stations over ``[1, B]``, fan their carried state out to ``len(parent)`` members on the device and
     step those over ``[B + 1, L]``: what ``device.run_points(replicate(...))`` returns for the members, bit for bit,
     without stepping any station's analysis more than once.
@@ -263,10 +280,13 @@ def run_ensemble(station_forcing: dict, member_tail: dict, B: int, settings: abi
     ``S`` of them; a member has its station's, except that ``member_local`` (one, or one per member) may give it
     relaxation targets of its own.  ``parent`` defaults to ``parents(S, len(tail) // S)``.  ``chunk``: indices per
     launch (0: a leg in one launch); ``recluster``: ``Plan.recluster()`` behind every launch; ``groups``:
-    ``(groups.GroupSpec, ids int32 [len(parent)])`` - the members' rows are also reduced per group on the device.
+    ``(groups.GroupSpec, ids int32 [len(parent)])`` - the members' rows are also reduced per group on the device;
+    ``stats``: an ``ensstats.EnsSpec`` with ``ngroups = S`` - the members' rows are also reduced per STATION on the
+    device (group = parent), behind every launch: mean, spread and quantiles of Tsurf, mean storages.
 
     Returns a dict: ``stations[name][S][B]``, ``members[name][len(parent)][L - B]`` (row r is time index
-    ``B + 1 + r``), ``failed`` = (stations, members) counts, and with ``groups`` the series ``[L - B, ngroups, cols]``.
+    ``B + 1 + r``), ``failed`` = (stations, members) counts, with ``groups`` the series ``[L - B, ngroups, cols]`` and
+    with ``stats`` the cells ``stats[L - B, S, cols]`` of ``ensstats.reduce_members`` (row r is time index ``B + 1 + r``).
     Raises ValueError - before any device work - where the analysis would not be shared (``check``)."""
     S = station_forcing["tair"].shape[0]
     nmem, tail_len = member_tail["tair"].shape
@@ -286,7 +306,7 @@ def run_ensemble(station_forcing: dict, member_tail: dict, B: int, settings: abi
     sl = _locals(station_local, S)
     if len(sl) != S:
         raise ValueError("run_ensemble: one LocalParameters, or one per station")
-    check(S, L, B, settings, sl, member_local, parent, precision, recluster)
+    check(S, L, B, settings, sl, member_local, parent, precision, recluster, stats)
     if station_forcing["tair"].shape[1] < B:
         raise ValueError(f"run_ensemble: the stations' forcing is shorter than B = {B}")
     ml = member_locals(sl, member_local, parent)
@@ -313,7 +333,7 @@ def run_ensemble(station_forcing: dict, member_tail: dict, B: int, settings: abi
     st = _Leg(S, 1, head, np.asarray(station_forcing["hour"])[:B], settings, params, sl, need_full, precision, variant,
               recluster, device, date, sky=sky_st)
     mem = _Leg(nmem, B + 1, member_tail, member_tail["hour"], settings, params, ml, need_full, precision, variant,
-               recluster, device, date, groups, sky=sky_mem)
+               recluster, device, date, groups, sky=sky_mem, stats=None if stats is None else (stats, parent))
     st.init()
     if coupled:
         # as device.run_points: lock-step chunks up to the last coupling-window end, the replay rounds over the block
@@ -346,6 +366,8 @@ def run_ensemble(station_forcing: dict, member_tail: dict, B: int, settings: abi
     res["failed"] = (st.plan.failed_count(), mem.plan.failed_count())
     if mem.gacc is not None:
         res["groups"] = mem.plan.groups(mem.gacc, mem.gspec)
+    if mem.eacc is not None:
+        res["stats"] = mem.plan.ens(mem.eacc, mem.espec)
     if ev:
         timing["fanout_ms"] = float(ev[0].elapsed_time(ev[1]))
     st.plan.close()

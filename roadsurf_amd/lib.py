@@ -102,6 +102,16 @@ class RsGroupSpec(C.Structure):
                 ("edges", C.c_double * RS_GRP_MAX_EDGES)]
 
 
+RS_ENS_MAX_MEMBERS = 64
+RS_ENS_MAX_QUANT = 8
+RS_ENS_COLS = 9
+
+
+class RsEnsSpec(C.Structure):
+    _fields_ = [("ngroups", C.c_int32), ("max_members", C.c_int32), ("nquant", C.c_int32),
+                ("quant", C.c_double * RS_ENS_MAX_QUANT)]
+
+
 RS_EPI_VARS = 7
 RS_EPI_MAX = 8
 RS_EPI_HEAD = 10
@@ -127,7 +137,7 @@ EXPORTS = (
     "rs_hip_plan_npoints", "rs_hip_plan_npoints_padded", "rs_hip_plan_state_bytes",
     "rs_hip_init_state", "rs_hip_step", "rs_hip_step_cpl", "rs_hip_cpl_replay", "rs_hip_set_output_by_point", "rs_hip_state_download", "rs_hip_state_upload", "rs_hip_state_fanout",
     "rs_hip_failed_count", "rs_hip_clock_probe", "rs_hip_first_failed_index", "rs_hip_set_diagnostics", "rs_hip_diagnostics", "rs_hip_sync", "rs_hip_synth_knots", "rs_hip_expand_forcing", "rs_hip_expand_forcing_ordered", "rs_hip_step_knots", "rs_hip_expand_forcing_on",
-    "rs_hip_plan_order", "rs_hip_recluster", "rs_hip_recluster_forecast", "rs_hip_set_history_score", "rs_hip_coupling_windows_closed", "rs_hip_set_writeback", "rs_hip_plan_order_copy", "rs_hip_outputs_by_point", "rs_hip_summary_cols", "rs_hip_summary_reset", "rs_hip_outputs_summary", "rs_hip_group_cols", "rs_hip_group_path", "rs_hip_group_reset", "rs_hip_outputs_groups", "rs_hip_episode_cols", "rs_hip_episodes_reset", "rs_hip_outputs_episodes", "rs_hip_episodes_finish", "rs_hip_grid_max_stencil", "rs_hip_gather_nodes", "rs_hip_plan_reset_order", "rs_hip_set_variant", "rs_hip_set_precision", "rs_hip_test_math", "rs_hip_division_mode", "rs_hip_div_mismatch_count", "rs_hip_div_special_count", "rs_hip_div_samples", "rs_hip_timing_reset", "rs_hip_timing_step_ms", "rs_hip_timing_intervals",
+    "rs_hip_plan_order", "rs_hip_recluster", "rs_hip_recluster_forecast", "rs_hip_set_history_score", "rs_hip_coupling_windows_closed", "rs_hip_set_writeback", "rs_hip_plan_order_copy", "rs_hip_outputs_by_point", "rs_hip_summary_cols", "rs_hip_summary_reset", "rs_hip_outputs_summary", "rs_hip_group_cols", "rs_hip_group_path", "rs_hip_group_reset", "rs_hip_outputs_groups", "rs_hip_ens_cols", "rs_ens_table_ints", "rs_ens_member_table", "rs_hip_outputs_ens", "rs_hip_episode_cols", "rs_hip_episodes_reset", "rs_hip_outputs_episodes", "rs_hip_episodes_finish", "rs_hip_grid_max_stencil", "rs_hip_gather_nodes", "rs_hip_plan_reset_order", "rs_hip_set_variant", "rs_hip_set_precision", "rs_hip_test_math", "rs_hip_division_mode", "rs_hip_div_mismatch_count", "rs_hip_div_special_count", "rs_hip_div_samples", "rs_hip_timing_reset", "rs_hip_timing_step_ms", "rs_hip_timing_intervals",
     "rs_host_run_batch", "rs_last_fanout", "rs_driver_run", "rs_driver_run_summary", "rs_driver_run_groups", "rs_driver_run_grid", "rs_driver_expand_grid", "rs_driver_run_kept", "rs_driver_kept_fields", "rs_driver_run_episodes", "rs_driver_last_tiles", "rs_driver_last_raw_launches", "rs_hip_bl_stats", "rs_compat_begin", "rs_compat_step", "rs_compat_replay", "rs_compat_failed_index", "rs_compat_last_state", "rs_compat_outputs", "rs_compat_end", "rs_driver_expand", "rs_driver_release_cache", "rs_abi_version", "rs_abi_sizeof", "rs_fortran_sizeof",
 )
 
@@ -233,6 +243,14 @@ def load() -> C.CDLL:
         L.rs_hip_group_reset.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, P(RsGroupSpec), C.c_void_p]
         L.rs_hip_outputs_groups.argtypes = [C.c_void_p, P(RsOutputs), C.c_int32, C.c_void_p, C.c_void_p, P(RsGroupSpec),
                                             C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
+    if hasattr(L, "rs_hip_ens_cols"):  # ... nor for the ensemble statistics
+        L.rs_hip_ens_cols.restype = C.c_int32
+        L.rs_hip_ens_cols.argtypes = [P(RsEnsSpec)]
+        L.rs_ens_table_ints.restype = C.c_int64
+        L.rs_ens_table_ints.argtypes = [C.c_int32, P(RsEnsSpec)]
+        L.rs_ens_member_table.argtypes = [C.c_int32, C.c_void_p, P(RsEnsSpec), C.c_void_p]
+        L.rs_hip_outputs_ens.argtypes = [C.c_void_p, P(RsOutputs), C.c_int32, C.c_void_p, C.c_void_p, P(RsEnsSpec),
+                                         C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
     if hasattr(L, "rs_hip_grid_max_stencil"):  # ... nor for the gridded sources
         L.rs_hip_grid_max_stencil.restype = C.c_int32
         L.rs_hip_gather_nodes.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
@@ -314,6 +332,33 @@ def group_path(spec) -> str:
     """Which kernel the host chooses for this spec (rs_hip_group_path): "lds" or "global"."""
     group_cols(spec)
     return {1: "lds", 2: "global"}[load().rs_hip_group_path(C.byref(group_spec(spec)))]
+
+
+def ens_spec(spec) -> RsEnsSpec:
+    """RsEnsSpec of anything with ``ngroups``, ``max_members`` and ``quantiles`` (ensstats.EnsSpec).  More quantiles
+    than the struct holds are cut to that many and their number kept: the library refuses the spec."""
+    if isinstance(spec, RsEnsSpec):
+        return spec
+    quant = [float(x) for x in spec.quantiles]
+    e = RsEnsSpec()
+    e.ngroups = int(spec.ngroups)
+    e.max_members = int(spec.max_members)
+    e.nquant = len(quant)
+    for i, q in enumerate(quant[:RS_ENS_MAX_QUANT]):
+        e.quant[i] = q
+    return e
+
+
+def ens_cols(spec) -> int:
+    """Numbers per cell of this spec as the library counts them (rs_hip_ens_cols); raises on a spec it refuses."""
+    L = load()
+    if not hasattr(L, "rs_hip_ens_cols"):
+        raise RuntimeError("this libroadsurf_hip.so has no ensemble statistics (rs_hip_ens_cols)")
+    n = L.rs_hip_ens_cols(C.byref(ens_spec(spec)))
+    if n < 0:
+        raise RuntimeError("rs_hip_ens_cols: bad spec (ngroups >= 1, 1 <= max_members <= RS_ENS_MAX_MEMBERS, at most "
+                           "RS_ENS_MAX_QUANT quantiles in [0, 1], strictly increasing)")
+    return n
 
 
 def episode_spec(spec) -> RsEpisodeSpec:

@@ -3,6 +3,7 @@
  * recompute every time step: the reciprocals of the uniform denominators (rs_math.hpp, rs_div_u)
  * and one uniform product.  Filled in C++ by rs_hip_plan_create; not part of the C-ABI. */
 #pragma once
+#include <cmath>
 #include <cstdlib>
 #include "../../include/roadsurf.h"
 
@@ -48,7 +49,20 @@ struct RsConstantsDev : RsConstants {
   struct LayerRow {
     double capDZF, condDZ, DyC, dryCap, WCont, pad[3];
   } lk[RS_MAX_LAYERS + 2];
+  /* The stability parameter above which the sign of calcRaero's numerator (logMom + PSIM)*(logHeat + PSIH) is known
+   * without the stability correction (rs_physics_body.inc, DRY TAIL): the Stab < 0 at which the exact
+   * PSIH = -2 ln((1 + sqrt(1 - 16 Stab))/2) equals -min(logHeat/2, logMom/1.2), so that above it logHeat + PSIH and
+   * logMom + 0.6 PSIH keep at least half of logHeat and logMom.  NaN where either logarithm is not positive and
+   * finite: no Stab compares above it.  (Defaults: logMom 3.26, logHeat 9.21, threshold -2.81.) */
+  double stabSafe;
 };
+
+static inline double rs_stab_safe(double logMom, double logHeat) {
+  if (!(logMom > 0.0 && logMom < HUGE_VAL && logHeat > 0.0 && logHeat < HUGE_VAL)) return NAN;
+  const double psih = std::fmin(logHeat / 2.0, logMom / 1.2); /* -PSIH at the threshold */
+  const double sq = 2.0 * std::exp(psih / 2.0) - 1.0;         /* sqrt(1 - 16 Stab) there */
+  return (1.0 - sq * sq) / 16.0;                              /* (-inf for huge logarithms: every finite Stab passes) */
+}
 
 static inline void rs_consts_dev_fill(const RsConstants &c, RsConstantsDev &d) {
   static_cast<RsConstants &>(d) = c;
@@ -92,6 +106,7 @@ static inline void rs_consts_dev_fill(const RsConstants &c, RsConstantsDev &d) {
       d.hs1F = num / c.twoDT;
     }
   }
+  d.stabSafe = rs_stab_safe(c.logMom, c.logHeat);
   d.bareFastOk = (c.MaxWatmms >= 0.0 && c.MaxSnowmms >= 0.0 && c.MaxIcemms >= 0.0 && c.MaxDepmms >= 0.0) ? 1 : 0;
   d.precFastOk = (c.MinPrecmm >= 0.0) ? 1 : 0;
 }

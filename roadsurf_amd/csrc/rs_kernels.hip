@@ -820,8 +820,13 @@ __global__ void __launch_bounds__(kBlock, 4) step_kernel_lds(const StepArgs a) {
  * step shrinks from ~1 460 to ~1 020 vector instructions and the shard occupies twice as many
  * wave slots.  Same arithmetic in the same order per point: same bits (layer_step is the one
  * function both flavours call).  LEAN feature set, NLayers = 15, 32-bit window offsets. */
-/* what a step needs of its forcing alone (ForcingPrep), [value][lane]: nine values, ten with the FULL feature set */
+/* what a step needs of its forcing alone (ForcingPrep), [value][lane]: eight values, nine with the FULL feature set
+ * (one more each where the air's vapour pressure is mailed: -DRS_NO_EAIR_SURFACE, rs_physics.hpp) */
+#ifdef RS_EAIR_SURFACE
+enum { PR_TAIR = 0, PR_VZ, PR_RHZ, PR_RAIN, PR_SNOW, PR_AVC, PR_SW, PR_LW, PR_OBS, PR_LEAN = PR_OBS, PR_FULL = PR_OBS + 1 };
+#else
 enum { PR_TAIR = 0, PR_VZ, PR_RHZ, PR_RAIN, PR_SNOW, PR_AVC, PR_EAIR, PR_SW, PR_LW, PR_OBS, PR_LEAN = PR_OBS, PR_FULL = PR_OBS + 1 };
+#endif
 template <int NPREP>
 struct DuoMailT {
   double v[2][2][64]; /* [buffer][0: Tmp(2) from the surface wave, 1: Tmp(3) from the ground wave][lane] */
@@ -833,7 +838,9 @@ struct DuoMailT {
    * are multiplications for the surface wave.  Round 6: the air's density and specific heat travel as their product
    * (all the surface wave ever forms of them; a product is the same bits in either order) and the psychrometric
    * constant is three operations on the air temperature the surface wave has anyway: nine values instead of eleven
-   * (+ 1.2 % at 1 M points; 16 192 B per workgroup of the LEAN instances, see RS_DUO_LEAN_WAVES). */
+   * (+ 1.2 % at 1 M points).  The air's vapour pressure left too (RS_EAIR_SURFACE, rs_physics.hpp): a Magnus
+   * quotient and an exp that the surface wave runs on the mailed tair and rhz, and only in a wavefront whose dry
+   * tail does not skip them - eight values, 15 168 B per workgroup of the LEAN instances (see RS_DUO_LEAN_WAVES). */
   double prep[2][NPREP][64];
   /* bit 0: CheckValues' verdict on the forcing; bit 1: the index falls in the night of
    * SetDayDependendVariables (src/BalanceModel.f90:354-387) - per LANE: with RsForcing::hour_pstride = 1
@@ -847,7 +854,9 @@ __device__ __forceinline__ void duo_put_prep(Mail &mail, int buf, uint32_t lane,
   w[PR_TAIR][lane] = q.tair; w[PR_VZ][lane] = q.vz; w[PR_RHZ][lane] = q.rhz; w[PR_RAIN][lane] = q.rain;
   w[PR_SNOW][lane] = q.snow;
   w[PR_AVC][lane] = q.AirHCap * q.AirDens; /* AirVCap, forcing_prep_tail's expression */
+#ifndef RS_EAIR_SURFACE
   w[PR_EAIR][lane] = q.EAir;
+#endif
   if (!SKYG) { /* (SKYG: the radiation is the sky wave's to hand over, duo_sky) */
     w[PR_SW][lane] = q.sw;
     w[PR_LW][lane] = q.lw;
@@ -864,7 +873,10 @@ __device__ __forceinline__ ForcingPrep duo_get_prep(const C &c, const Mail &mail
   q.snow = w[PR_SNOW][lane];
   const double AirVCap = w[PR_AVC][lane];
   q.AirVCap = AirVCap;
-  q.EAir = w[PR_EAIR][lane]; q.sw = w[PR_SW][lane]; q.lw = w[PR_LW][lane];
+#ifndef RS_EAIR_SURFACE
+  q.EAir = w[PR_EAIR][lane];
+#endif
+  q.sw = w[PR_SW][lane]; q.lw = w[PR_LW][lane];
   if (FULL) q.tsurfobs = w[PR_OBS][lane];
   uint32_t flags = mail.prep_bad[buf][lane];
   if (SKYG) flags |= skyfl[buf * 64 + lane]; /* the sky wave's share of CheckValues (bit 0) and its `stop` (bit 2) */
@@ -874,7 +886,9 @@ __device__ __forceinline__ ForcingPrep duo_get_prep(const C &c, const Mail &mail
     q.trffric = q.night ? fricN : fricD;
   }
   /* forcing_prep_tail's expressions on forcing_prep_tail's values */
+#ifndef RS_BL_LAST /* (with it: model_step_fluxes_prepped forms the psychrometric constant where a wavefront needs it) */
   q.PsychC = R4(0.1) * (R4(0.00063) * (q.tair + R4(273.15)) + R4(0.47496));
+#endif
   q.den0 = AirVCap * (q.tair + R4(273.15));
   q.vkvz = c.VK_Const * q.vz;
   q.avk = AirVCap * c.VK_Const;
@@ -1876,8 +1890,8 @@ __device__ __forceinline__ void duo_sky(DuoMailT<PR_FULL> &mail, uint32_t *skyfl
 template <int NL, bool SCORE, int SRC = SRC_WINDOW, bool FULL = false, bool SKY = false, bool CPL = false,
           bool REPLAY = false>
 #ifndef RS_DUO_LEAN_WAVES
-/* The LEAN instances' 16 192 B of LDS would let ten workgroups onto a CU, and at five wavefronts per SIMD they fit 96
- * registers with 9-14 spilled - measured (tools/experiments/r6_ab3.sh, profiles/r06_lean_waves_per_simd.txt): 1 M
+/* The LEAN instances' LDS (15 168 B; 16 192 B when this was measured) would let ten workgroups onto a CU, and at five
+ * wavefronts per SIMD they fit 96 registers with 9-14 spilled - measured (tools/experiments/r6_ab3.sh, profiles/r06_lean_waves_per_simd.txt): 1 M
  * points 2.513e10 at five against 2.560e10 at four (2.529e10 with round 5's mailbox of eleven values), level at
  * 250 000 and 125 000 points.  The pass is bound by what the wavefronts issue, not by how many of them wait. */
 #define RS_DUO_LEAN_WAVES 4

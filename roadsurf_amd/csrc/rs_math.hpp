@@ -131,8 +131,8 @@ static __device__ unsigned long long g_div_mismatch[3] = {0ull, 0ull, 0ull};
  * forcing_prep_tail: [17] wave-steps, [18] the precipitation branch taken; boundary-layer passes as wavefronts issue
  * them: [19] all, [20] with a lane on the unstable arm, [21] with lanes on both paths of its log, [22] with lanes on
  * both arms, [23] with a lane on log's table path; [48] lane-passes, [46] of them on the unstable arm, [47] on log's
- * table path; [49..52] CalcLE's dry tail (rs_physics_body.inc, dry_tail_count) */
-#define RS_BL_NSTATS 56 /* [24..31] wave-steps by the wavefront's trip count 5, 6, 7, 8, 9-12, 13-20, 21-39, 40; [32..39] lane-steps likewise; [40..45] wave-steps with 1, 2-3, 4-7, 8-15, 16-31, 32-64 lanes of more than 20 passes */
+ * table path; [49..52] CalcLE's dry tail (rs_physics_body.inc, dry_tail_count), [53..56] the last pass (bl_last_count) */
+#define RS_BL_NSTATS 57 /* [24..31] wave-steps by the wavefront's trip count 5, 6, 7, 8, 9-12, 13-20, 21-39, 40; [32..39] lane-steps likewise; [40..45] wave-steps with 1, 2-3, 4-7, 8-15, 16-31, 32-64 lanes of more than 20 passes */
 static __device__ unsigned long long g_bl_stats[RS_BL_NSTATS];
 /* the first RS_DIV_SAMPLES finite mismatches: {numerator (or sqrt argument), denominator (0 for
  * sqrt), IEEE result, bare result} */

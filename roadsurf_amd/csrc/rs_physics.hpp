@@ -69,11 +69,24 @@
 #define RS_STAB_UPPER(x) rs_min_one(x) /* bl_iteration: the stability parameter's upper clamp, one v_min_f64 in the stable arm */
 /* CalcLE's tail skipped for a wavefront in which the reference zeroes it in every point (rs_physics_body.inc, DRY
  * TAIL; the argument there rests on this flavour's correctly rounded arithmetic).  A/B builds: -DRS_NO_DRY_TAIL_SKIP
- * is the text without either stage, -DRS_NO_DRY_ESURF_SKIP the first stage alone. */
+ * is the text without either stage, -DRS_NO_DRY_ESURF_SKIP the first stage alone.
+ * On top of both stages, for the two-wavefront kernels (model_step_fluxes_prepped):
+ *   RS_BL_LAST       the boundary-layer loop carries Stab, and the stability correction of its exit pass is evaluated
+ *                    only where the tail is alive or Stab does not prove the sign it is needed for
+ *                    (-DRS_NO_BL_LAST_SKIP: the correction at the end of every pass, as it stood)
+ *   RS_EAIR_SURFACE  the air's vapour pressure is formed by the surface wave, where a wavefront needs it, instead of
+ *                    by the ground wave for every index (-DRS_NO_EAIR_SURFACE: worked out ahead and mailed)
+ * These two stay defined: rs_kernels.hip's mailbox follows them. */
 #ifndef RS_NO_DRY_TAIL_SKIP
 #define RS_DRY_TAIL 1
 #if !defined(RS_NO_DRY_ESURF_SKIP) && !defined(RS_EXP_SURFACE_LIGHT) && !defined(RS_EXP_PIPE1)
 #define RS_DRY_ESURF 1
+#if !defined(RS_NO_BL_LAST_SKIP) && !defined(RS_EXP_STAB_CHAIN)
+#define RS_BL_LAST 1
+#endif
+#ifndef RS_NO_EAIR_SURFACE
+#define RS_EAIR_SURFACE 1
+#endif
 #endif
 #endif
 #include "rs_physics_body.inc"

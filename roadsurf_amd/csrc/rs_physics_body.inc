@@ -149,10 +149,11 @@ __device__ __forceinline__ RS_REAL bl_stab_num(const RS_CONSTS &c) {
   return -c.VK_Const * c.ZRefT * c.Grav;
 }
 
+/* One pass is two halves: bl_pass (:66-80: UStar, BLCond, Stab, and the exit test of :92, which reads nothing of what
+ * follows) and bl_arm (:83-89: the stability correction from Stab, which only the NEXT pass and calcRaero read). */
 template <bool IEEE = false>
-__device__ __forceinline__ bool bl_iteration(const RS_CONSTS &c, const MathTab &mt,
-                                             const BlInv &v, BlVar &x, int j, RS_REAL stab_num,
-                                             bool *unstable = nullptr) {
+__device__ __forceinline__ bool bl_pass(const RS_CONSTS &c, const BlInv &v, BlVar &x, int j, RS_REAL stab_num,
+                                        RS_REAL &Stab) {
   const RS_REAL ConvLim = R4(0.001);
   const RS_REAL BLCond_Old = x.BLCond;
   RS_REAL UStar;
@@ -171,10 +172,15 @@ __device__ __forceinline__ bool bl_iteration(const RS_CONSTS &c, const MathTab &
    * a = logUstar + PSIM, known seven operations before UStar - here taken as the reciprocal itself (no Newton step,
    * no remainder, no correction: three levels fewer than the exact variant DESIGN.md 8 item 4 describes could have) */
   const RS_REAL a_ = (!IEEE && j == 1) ? c.logUstar : c.logUstar + x.PSIM;
-  RS_REAL Stab = (stab_num * x.BLCond * v.dT) * ((a_ * a_ * a_) * v.kinv);
+  Stab = (stab_num * x.BLCond * v.dT) * ((a_ * a_ * a_) * v.kinv);
 #else
-  RS_REAL Stab = rs_dvb<IEEE>(stab_num * x.BLCond * v.dT, v.den0 * (UStar * UStar * UStar));
+  Stab = rs_dvb<IEEE>(stab_num * x.BLCond * v.dT, v.den0 * (UStar * UStar * UStar));
 #endif
+  return (j >= 5) && (rs_fabs(x.BLCond - BLCond_Old) < ConvLim);
+}
+
+template <bool IEEE = false>
+__device__ __forceinline__ void bl_arm(const MathTab &mt, RS_REAL Stab, BlVar &x, bool *unstable = nullptr) {
   /* The clamp `if (Stab > 1) Stab = 1` (:80) only ever acts on a Stab that takes the stable arm: Stab > 1 is
    * Stab > 0, and a NaN fails both tests and goes on unclamped, as it must - the guard of boundary_layer() lives
    * on it.  RS_STAB_UPPER is that clamp inside the arm (rs_physics.hpp: one v_min_f64 instead of a compare, a
@@ -194,7 +200,16 @@ __device__ __forceinline__ bool bl_iteration(const RS_CONSTS &c, const MathTab &
     x.PSIM = R4(0.6) * x.PSIH;
     if (unstable) *unstable = true;
   }
-  return (j >= 5) && (rs_fabs(x.BLCond - BLCond_Old) < ConvLim);
+}
+
+template <bool IEEE = false>
+__device__ __forceinline__ bool bl_iteration(const RS_CONSTS &c, const MathTab &mt,
+                                             const BlInv &v, BlVar &x, int j, RS_REAL stab_num,
+                                             bool *unstable = nullptr) {
+  RS_REAL Stab;
+  const bool done = bl_pass<IEEE>(c, v, x, j, stab_num, Stab);
+  bl_arm<IEEE>(mt, Stab, x, unstable);
+  return done;
 }
 
 #ifdef RS_DRY_TAIL
@@ -227,7 +242,38 @@ __device__ __forceinline__ bool bl_iteration(const RS_CONSTS &c, const MathTab &
  * range of tair, AirDens is in (0.9, 2.1), AirHCap in [1005, 1010], PsychC in (0.058, 0.071) and ESurf - EAir >=
  * 3.6e-4 * 1e-6, so N is normal or +inf (EAir = -inf) and le = N/D positive or +inf as above: zeroed.  (With the
  * humidity's limit taken as the reference's MIN takes it - a NaN reads 1.0, forcing_prep_tail - EAir cannot be a
- * NaN on that range of tair; the test stands so that the argument does not lean on it.) */
+ * NaN on that range of tair; the test stands so that the argument does not lean on it.)
+ *
+ * THE LAST PASS (RS_BL_LAST, model_step_fluxes_prepped).  The stability correction at the end of the loop's exit pass
+ * (:83-89) is read once, by calcRaero, whose RAero feeds only le: where the rule fires it is computed for the sign of
+ * raNum alone.  The loop therefore carries Stab, a pass j >= 2 begins with bl_arm on the Stab of pass j-1 - the same
+ * operations on the same operands in the same order for every lane, minus the arm of its exit pass - and every test
+ * above that does not read raNum is made BEFORE the loop (dry_tail_dry, dry_tail_warm_t, and ESurf, N and PsychC where
+ * some lane is not warm).  Behind the loop the sign of raNum is PROVEN from Stab, no longer computed:
+ *   Stab > 0:  PSIH = PSIM = 4.7*min(Stab, 1) in (0, 4.7]; both factors are at least their logarithms.
+ *   stabSafe < Stab <= 0 (-0 included):  the exact PSIH(Stab) = -2 ln((1 + sqrt(1 - 16 Stab))/2) falls with -Stab and
+ *     equals -min(logHeat/2, logMom/1.2) at stabSafe (rs_consts_dev.h), so logHeat + PSIH >= logHeat/2 and logMom +
+ *     0.6 PSIH >= logMom/2 exactly; rs_sq and rs_log are within a few ulp, and the half that is left is 1e15 ulp.
+ * stabSafe exists only for logMom, logHeat positive and finite (a NaN otherwise: the compare fails in every lane), so
+ * both computed factors are positive and finite and their product is positive (at worst +inf, which dry_tail_signs
+ * allows) - what `raNum > 0` asked.  A NaN Stab compares false.  Everything else rests on what stood above: a lane's
+ * proof is its own, stage 1's or stage 2's, so a wavefront of both kinds skips too.  Where a lane is alive or its Stab
+ * is at or below stabSafe, the arm runs for the wavefront and the tail follows as the reference writes it, rule and
+ * all, with no second skip.  The GUARD sees le = +0.0 in a skipped wavefront and the blcond it always saw; a bare
+ * sequence's NaN in the final Stab fails the compare and arrives in le through the arm as before.
+ *
+ * EAIR ON DEMAND (RS_EAIR_SURFACE).  Stage 2's `EAir == EAir` is a statement about EAir's inputs: with -100 < tair <
+ * 100 (tair < tsurf < 100) the Magnus quotient is below 20 in magnitude and ESat is positive and finite;
+ * rs_min_num_one returns 1.0 for a NaN and never a NaN; so EAir = hum*ESat is a number or -inf (hum = -inf), the case
+ * the argument above covers - never a NaN.  The surface wave forms EAir from the mailed tair and rhz, by
+ * air_vapour_pressure as forcing_prep_tail did, only in a wavefront that needs it. */
+__device__ __forceinline__ bool dry_tail_dry(RS_REAL wat, RS_REAL raDen) {
+  return (wat <= R4(0.0)) && rs_is_pos_finite(raDen);
+}
+__device__ __forceinline__ bool dry_tail_warm_t(RS_REAL tsurf, RS_REAL tair) {
+  return (tair > R4(-100.0)) && (tsurf < R4(100.0)) && (tsurf >= tair + R4(0.01));
+}
+__device__ __forceinline__ bool dry_tail_psychc(RS_REAL PsychC) { return (PsychC > R4(0.0)) && (PsychC < R4(1.0)); }
 __device__ __forceinline__ bool dry_tail_signs(RS_REAL wat, RS_REAL raNum, RS_REAL raDen) {
   return (wat <= R4(0.0)) && (raNum > R4(0.0)) && rs_is_pos_finite(raDen);
 }
@@ -260,12 +306,19 @@ __device__ __forceinline__ void bl_finish(const RS_CONSTS &c, const MathTab &mt,
 #ifdef RS_DRY_TAIL
   /* the text below in the order the skips need: what the tests read first, what they skip last */
   const RS_REAL raNum = (c.logMom + x.PSIM) * (c.logHeat + x.PSIH), raDen = c.VK_Const * c.VK_Const * vz;
+  const bool signs = dry_tail_signs(wat, raNum, raDen); /* (IEEE: the guard's redo runs the whole text) */
+#if defined(RS_DRY_ESURF) && defined(RS_EAIR_SURFACE) /* (EAIR ON DEMAND: the air's vapour pressure behind the test) */
+  if (!IEEE && rs_wave_all(signs && dry_tail_warm_t(tsurf, tair))) {
+    le = R4(0.0);
+    evap = R4(0.0);
+    return;
+  }
+#endif
   const RS_REAL aa = (tair < 0) ? R4(21.875) : R4(17.269);
   const RS_REAL ba = (tair < 0) ? R4(265.5) : R4(237.3);
   const RS_REAL ESat = R4(0.61078) * rs_exp(mt, rs_dv<IEEE>(aa * tair, tair + ba));
   const RS_REAL EAir = rs_min_num_one(R4(0.01) * rhz) * ESat; /* (Min's NaN rule: forcing_prep_tail) */
-  const bool signs = dry_tail_signs(wat, raNum, raDen); /* (IEEE: the guard's redo runs the whole text) */
-#ifdef RS_DRY_ESURF
+#if defined(RS_DRY_ESURF) && !defined(RS_EAIR_SURFACE)
   if (!IEEE && rs_wave_all(dry_tail_warm(signs, tsurf, tair, EAir))) {
     le = R4(0.0);
     evap = R4(0.0);
@@ -777,7 +830,9 @@ struct ForcingPrep {
   RS_REAL trffric;
   RS_REAL AirDens, AirHCap, PsychC, den0, vkvz, avk;
   RS_REAL AirVCap = 0; /* AirHCap x AirDens: what the two-wavefront mailbox carries of the two (duo_get_prep) */
+#ifndef RS_EAIR_SURFACE /* (with it: air_vapour_pressure of tair and rhz, where model_step_fluxes_prepped needs it) */
   RS_REAL EAir;
+#endif
   RS_REAL sw, lw;
   bool bad; /* CheckValues' verdict on the forcing (the surface-temperature test is the surface wave's) */
   bool night = false; /* SetDayDependendVariables' branch: which traffic friction and calm limit the index gets */
@@ -816,6 +871,17 @@ __device__ __forceinline__ RS_REAL forcing_prep_head(const RS_CONSTS &c, const F
     if (has_tdew) bad = bad | (f.tdew < -90) | (f.tdew > R4(100.0));
   }
   return vz;
+}
+
+/* CalcLE's vapour pressure of the air (src/BoundaryLayer.f90:160-172), Magnus over ice or water at tair times the
+ * limited humidity */
+__device__ __forceinline__ RS_REAL air_vapour_pressure(const MathTab &mt, RS_REAL tair, RS_REAL rhz) {
+  const RS_REAL aa = (tair < 0) ? R4(21.875) : R4(17.269);
+  const RS_REAL ba = (tair < 0) ? R4(265.5) : R4(237.3);
+  const RS_REAL ESat = R4(0.61078) * rs_exp(mt, rs_dv<false>(aa * tair, tair + ba));
+  /* Min((0.01*Rhz), 1.0), src/BoundaryLayer.f90:172: the compiled reference's MIN returns the other operand where
+   * one is a NaN - a NaN humidity (CheckValues lets it through) reads as saturated air - and so does v_min_f64 */
+  return rs_min_num_one(R4(0.01) * rhz) * ESat;
 }
 
 /* Second half, from the air temperature, wind speed and humidity the step will use (the FULL feature
@@ -867,12 +933,9 @@ __device__ __forceinline__ ForcingPrep forcing_prep_tail(const RS_CONSTS &c, con
   q.den0 = AirVCap * (tair + R4(273.15));
   q.vkvz = c.VK_Const * vz;
   q.avk = AirVCap * c.VK_Const;
-  const RS_REAL aa = (tair < 0) ? R4(21.875) : R4(17.269);
-  const RS_REAL ba = (tair < 0) ? R4(265.5) : R4(237.3);
-  const RS_REAL ESat = R4(0.61078) * rs_exp(mt, rs_dv<false>(aa * tair, tair + ba));
-  /* Min((0.01*Rhz), 1.0), src/BoundaryLayer.f90:172: the compiled reference's MIN returns the other operand where
-   * one is a NaN - a NaN humidity (CheckValues lets it through) reads as saturated air - and so does v_min_f64 */
-  q.EAir = rs_min_num_one(R4(0.01) * rhz) * ESat;
+#ifndef RS_EAIR_SURFACE
+  q.EAir = air_vapour_pressure(mt, tair, rhz);
+#endif
   q.sw = f.sw;
   q.lw = f.lw;
   return q;
@@ -886,10 +949,217 @@ __device__ __forceinline__ ForcingPrep forcing_prep(const RS_CONSTS &c, const Ma
   return forcing_prep_tail<NIGHT_U>(c, mt, f, f.tair, vz, f.rhz, bad, night_u);
 }
 
+#ifdef RS_BL_STATS
+/* the boundary-layer loop's counters (rs_math.hpp g_bl_stats): the step, each pass, the trip counts */
+struct BlStatsStep {
+  unsigned long long act;
+  bool first;
+};
+__device__ __forceinline__ BlStatsStep bl_stats_step() {
+  const unsigned long long act = __builtin_amdgcn_ballot_w64(true);
+  const bool first = (unsigned long long)__builtin_ctzll(act) == (unsigned long long)(threadIdx.x & 63u);
+  if (first) {
+    atomicAdd(&rs::g_bl_stats[0], 1ull);
+    atomicAdd(&rs::g_bl_stats[1], (unsigned long long)__builtin_popcountll(act));
+  }
+  return BlStatsStep{act, first};
+}
+/* h0: PSIH before the pass; x: after the pass and its arm */
+__device__ __forceinline__ void bl_stats_pass(const BlStatsStep &st, int j, RS_REAL h0, const BlVar &x) {
+  const unsigned long long act = st.act;
+  const bool first = st.first;
+  { /* which arms of the pass ran: the stable one, the unstable one with log's polynomial / table path */
+    const bool uns = !(x.PSIH > R4(0.0)), far = x.PSIH < R4(-0.1254);
+    const unsigned long long mu = __builtin_amdgcn_ballot_w64(uns), mf = __builtin_amdgcn_ballot_w64(far),
+                             ma = __builtin_amdgcn_ballot_w64(true);
+    if ((unsigned long long)__builtin_ctzll(ma) == (unsigned long long)(threadIdx.x & 63u)) {
+      atomicAdd(&rs::g_bl_stats[19], 1ull);
+      atomicAdd(&rs::g_bl_stats[48], (unsigned long long)__builtin_popcountll(ma));
+      atomicAdd(&rs::g_bl_stats[46], (unsigned long long)__builtin_popcountll(mu));
+      atomicAdd(&rs::g_bl_stats[47], (unsigned long long)__builtin_popcountll(mf));
+      if (mu) atomicAdd(&rs::g_bl_stats[20], 1ull);
+      if (mf && (mu & ~mf)) atomicAdd(&rs::g_bl_stats[21], 1ull);
+      if (mu && (ma & ~mu)) atomicAdd(&rs::g_bl_stats[22], 1ull);
+      if (mf) atomicAdd(&rs::g_bl_stats[23], 1ull);
+    }
+  }
+  if (j >= 2 && j <= 4) {
+    const bool same = __double_as_longlong((double)h0) == __double_as_longlong((double)x.PSIH);
+    const unsigned long long ms = __builtin_amdgcn_ballot_w64(same);
+    if (first) {
+      if (ms == act) atomicAdd(&rs::g_bl_stats[j], 1ull);
+      atomicAdd(&rs::g_bl_stats[3 + j], (unsigned long long)__builtin_popcountll(ms));
+    }
+  }
+}
+__device__ __forceinline__ void bl_stats_trips(const BlStatsStep &st, int j) {
+  const bool first = st.first;
+  { /* trip counts: the lane's, and the wavefront's (how many passes it issued) */
+    const int trips = j > RS_BL_MAXIT ? RS_BL_MAXIT : j;
+    int wmax = trips, wsum = trips;
+    for (int o = 32; o > 0; o >>= 1) {
+      const int other = __shfl_xor(wmax, o, 64);
+      wmax = other > wmax ? other : wmax;
+      wsum += __shfl_xor(wsum, o, 64);
+    }
+    auto bin = [](int t) { return t <= 8 ? t - 5 : t <= 12 ? 4 : t <= 20 ? 5 : t < 40 ? 6 : 7; };
+    for (int b = 0; b < 8; ++b) {
+      const unsigned long long mb = __builtin_amdgcn_ballot_w64(bin(trips) == b);
+      if (first && mb) atomicAdd(&rs::g_bl_stats[32 + b], (unsigned long long)__builtin_popcountll(mb));
+    }
+    {
+      const int nh = __builtin_popcountll(__builtin_amdgcn_ballot_w64(trips > 20));
+      if (first && nh > 0) atomicAdd(&rs::g_bl_stats[40 + (nh == 1 ? 0 : nh <= 3 ? 1 : nh <= 7 ? 2 : nh <= 15 ? 3 : nh <= 31 ? 4 : 5)], 1ull);
+    }
+    if (first) {
+      atomicAdd(&rs::g_bl_stats[9], (unsigned long long)wsum);
+      atomicAdd(&rs::g_bl_stats[8], (unsigned long long)wmax);
+      atomicAdd(&rs::g_bl_stats[24 + bin(wmax)], 1ull);
+    }
+  }
+}
+#endif
+
 /* model_step_fluxes from a ForcingPrep: the storages take the precipitation, the boundary-layer loop
- * starts from the handed-over invariants, CalcLE from the handed-over vapour pressure of the air. */
+ * starts from the handed-over invariants, CalcLE from the handed-over vapour pressure of the air (or, EAIR ON DEMAND,
+ * from the handed-over air temperature and humidity). */
 /* TRIPS: 0 no scheduling hint, 1 the history score's (passes, +64 where a pass took the unstable branch), 2 the
  * pass count alone (the loop's own counter: nothing per pass) */
+#ifdef RS_BL_LAST
+/* CalcLE's numerator AirVCap*(ESurf - EAir) (src/BoundaryLayer.f90:160-176); the product AirDens x AirHCap arrives
+ * as AirVCap, EAir by the mailbox or from the mailed tair and rhz (EAIR ON DEMAND) */
+__device__ __forceinline__ RS_REAL le_numerator(const MathTab &mt, RS_REAL tsurf, const ForcingPrep &q) {
+  const RS_REAL as = (tsurf < 0) ? R4(21.875) : R4(17.269);
+  const RS_REAL bs = (tsurf < 0) ? R4(265.5) : R4(237.3);
+  const RS_REAL ESurf = R4(0.61078) * rs_exp(mt, rs_dv<false>(as * tsurf, tsurf + bs));
+#ifdef RS_EAIR_SURFACE
+  const RS_REAL EAir = air_vapour_pressure(mt, q.tair, q.rhz);
+#else
+  const RS_REAL EAir = q.EAir;
+#endif
+  return q.AirVCap * (ESurf - EAir);
+}
+/* forcing_prep_tail's expression on forcing_prep_tail's value: three operations where a wavefront needs them */
+__device__ __forceinline__ RS_REAL psychrometric(RS_REAL tair) {
+  return R4(0.1) * (R4(0.00063) * (tair + R4(273.15)) + R4(0.47496));
+}
+#ifdef RS_BL_STATS
+/* [53] wave-steps in which every active lane is dead by its own tests (the sign of raNum apart), [54] wave-steps in
+ * which the final stability correction is skipped, [55] of those, with a lane that left the loop on the unstable
+ * side (the sqrt and the log that are not evaluated), [56] wave-steps in which every lane is dry and warm */
+__device__ __forceinline__ void bl_last_count(bool dead, bool skip, bool all_warm, RS_REAL Stab) {
+  const unsigned long long act = __builtin_amdgcn_ballot_w64(true), mu = __builtin_amdgcn_ballot_w64(!(Stab > R4(0.0)));
+  if ((unsigned long long)__builtin_ctzll(act) == (unsigned long long)(threadIdx.x & 63u)) {
+    if (dead) atomicAdd(&rs::g_bl_stats[53], 1ull);
+    if (skip) atomicAdd(&rs::g_bl_stats[54], 1ull);
+    if (skip && mu) atomicAdd(&rs::g_bl_stats[55], 1ull);
+    if (all_warm) atomicAdd(&rs::g_bl_stats[56], 1ull);
+  }
+}
+#endif
+
+/* The flavour with THE LAST PASS (DRY TAIL): tests, loop on Stab, then the skip or the final correction and the tail */
+template <int TRIPS = 1>
+__device__ __forceinline__ Fluxes model_step_fluxes_prepped(const RS_CONSTS &c, const MathTab &mt,
+                                                            Scalars &s, const ForcingPrep &q,
+                                                            const CouplingInputs &cp = CouplingInputs()) {
+  Fluxes fx;
+  s.wat = s.wat + q.rain;
+  s.snow = s.snow + q.snow;
+  fx.trffric = q.trffric;
+  BlInv v;
+  BlVar x;
+  v.dT = s.tsurf - q.tair;
+  v.den0 = q.den0;
+  v.vkvz = q.vkvz;
+  v.avk = q.avk;
+  x.PSIM = R4(0.0);
+  x.PSIH = R4(0.0);
+  x.BLCond = 0.0;
+  const RS_REAL stab_num = bl_stab_num(c);
+  /* the dry-tail tests that do not read the loop's result: a lane is `dead` by stage 2 (warm) or by stage 1 */
+  const RS_REAL raDen = c.VK_Const * c.VK_Const * q.vz;
+  const bool dry = dry_tail_dry(s.wat, raDen);
+  const bool warm = dry && dry_tail_warm_t(s.tsurf, q.tair);
+  const bool all_warm = rs_wave_all(warm);
+  RS_REAL N = R4(0.0);
+  bool dead = true;
+#ifdef RS_BL_STATS
+  const bool need_n = true; /* (the counters of dry_tail_count want stage 1's verdict in every wave-step) */
+#else
+  const bool need_n = !all_warm;
+#endif
+  if (need_n) {
+    asm volatile(""); /* keeps the skip a branch, as in layer_vsh */
+    N = le_numerator(mt, s.tsurf, q);
+    dead = rs_wave_all(warm || (dry && rs_is_pos_normal(N) && dry_tail_psychc(psychrometric(q.tair))));
+  }
+  RS_REAL Stab = R4(0.0);
+  int j = 1;
+  bool unstable = false;
+#ifdef RS_BL_STATS
+  { /* (the arm at the end of every pass, as bl_iteration has it: the counters look at each pass's correction) */
+    const BlStatsStep st = bl_stats_step();
+    for (; j <= RS_BL_MAXIT; ++j) {
+      const RS_REAL h0 = x.PSIH;
+      const bool done = bl_pass<false>(c, v, x, j, stab_num, Stab);
+      bl_arm<false>(mt, Stab, x, TRIPS == 1 ? &unstable : nullptr);
+      bl_stats_pass(st, j, h0, x);
+      if (done) break;
+    }
+    bl_stats_trips(st, j);
+  }
+#else
+  for (; j <= RS_BL_MAXIT; ++j) {
+    if (j >= 2) bl_arm<false>(mt, Stab, x, TRIPS == 1 ? &unstable : nullptr);
+    if (bl_pass<false>(c, v, x, j, stab_num, Stab)) break;
+  }
+  if (TRIPS == 1 && !(Stab > R4(0.0))) unstable = true; /* the exit pass's branch, without taking it */
+#endif
+  fx.trips = TRIPS == 1 ? j + (unstable ? 64 : 0) : TRIPS == 2 ? (j > RS_BL_MAXIT ? RS_BL_MAXIT : j) : 5;
+  fx.blcond = x.BLCond;
+  const bool skip = dead && rs_wave_all(Stab > c.stabSafe);
+#ifdef RS_BL_STATS
+  {
+    const RS_REAL raNum = (c.logMom + x.PSIM) * (c.logHeat + x.PSIH);
+    dry_tail_count(dry_tail_le(dry_tail_signs(s.wat, raNum, raDen), N, psychrometric(q.tair)), warm && (raNum > R4(0.0)));
+    bl_last_count(dead, skip, all_warm, Stab);
+  }
+#endif
+  if (skip) {
+    fx.le = R4(0.0);
+    fx.evap = R4(0.0);
+  } else {
+    asm volatile(""); /* keeps the skip a branch, as in layer_vsh */
+#ifndef RS_BL_STATS
+    bl_arm<false>(mt, Stab, x);
+#endif
+    const RS_REAL raNum = (c.logMom + x.PSIM) * (c.logHeat + x.PSIH);
+    if (!need_n) N = le_numerator(mt, s.tsurf, q);
+    const RS_REAL WatDen = R4(-0.0050) * s.tsurf * s.tsurf + R4(0.0079) * s.tsurf + R4(1000.0028);
+    RS_REAL RAero = rs_dvb<false>(raNum, raDen);
+    if (RAero > R4(30.0)) RAero = R4(30.);
+    fx.le = rs_dvb<false>(N, psychrometric(q.tair) * RAero);
+    const RS_REAL lvap = c.LVap, lfus = c.LFus;
+    const RS_REAL lat = (s.tsurf >= R4(0.0)) ? lvap : lfus;
+    fx.evap = rs_dvb<false>(fx.le, lat * WatDen) * R4(1000.0) * c.DTSecs;
+    if ((fx.le > R4(0.0)) && (s.wat <= R4(0.0))) {
+      fx.le = R4(0.0);
+      fx.evap = R4(0.0);
+    }
+  }
+#if RS_BL_GUARD && !defined(RS_IEEE_DIV) && !defined(RS_DIV_CHECK) && !defined(RS_NO_BL_GUARD) && !defined(RS_BL_FIXUP)
+  if (!(rs_fabs(fx.blcond) < __builtin_inf()) || !(rs_fabs(fx.le) < __builtin_inf())) {
+    const BlOut o = boundary_layer_ieee(&c, mt.expT, mt.logT, mt.K, s.tsurf, q.tair, q.vz, q.rhz, s.wat);
+    fx.blcond = o.blcond;
+    fx.le = o.le;
+    fx.evap = o.evap;
+  }
+#endif
+  fluxes_post(c, s, q.sw, q.lw, cp, fx);
+  return fx;
+}
+#else
 template <int TRIPS = 1>
 __device__ __forceinline__ Fluxes model_step_fluxes_prepped(const RS_CONSTS &c, const MathTab &mt,
                                                             Scalars &s, const ForcingPrep &q,
@@ -920,63 +1190,14 @@ __device__ __forceinline__ Fluxes model_step_fluxes_prepped(const RS_CONSTS &c, 
   bool unstable = false;
 #ifdef RS_BL_STATS
   {
-    const unsigned long long act = __builtin_amdgcn_ballot_w64(true);
-    const bool first = (unsigned long long)__builtin_ctzll(act) == (unsigned long long)(threadIdx.x & 63u);
-    if (first) {
-      atomicAdd(&rs::g_bl_stats[0], 1ull);
-      atomicAdd(&rs::g_bl_stats[1], (unsigned long long)__builtin_popcountll(act));
-    }
+    const BlStatsStep st = bl_stats_step();
     for (; j <= RS_BL_MAXIT; ++j) {
       const RS_REAL h0 = x.PSIH;
       const bool done = bl_iteration<false>(c, mt, v, x, j, stab_num, TRIPS == 1 ? &unstable : nullptr);
-      { /* which arms of the pass ran: the stable one, the unstable one with log's polynomial / table path */
-        const bool uns = !(x.PSIH > R4(0.0)), far = x.PSIH < R4(-0.1254);
-        const unsigned long long mu = __builtin_amdgcn_ballot_w64(uns), mf = __builtin_amdgcn_ballot_w64(far),
-                                 ma = __builtin_amdgcn_ballot_w64(true);
-        if ((unsigned long long)__builtin_ctzll(ma) == (unsigned long long)(threadIdx.x & 63u)) {
-          atomicAdd(&rs::g_bl_stats[19], 1ull);
-          atomicAdd(&rs::g_bl_stats[48], (unsigned long long)__builtin_popcountll(ma));
-          atomicAdd(&rs::g_bl_stats[46], (unsigned long long)__builtin_popcountll(mu));
-          atomicAdd(&rs::g_bl_stats[47], (unsigned long long)__builtin_popcountll(mf));
-          if (mu) atomicAdd(&rs::g_bl_stats[20], 1ull);
-          if (mf && (mu & ~mf)) atomicAdd(&rs::g_bl_stats[21], 1ull);
-          if (mu && (ma & ~mu)) atomicAdd(&rs::g_bl_stats[22], 1ull);
-          if (mf) atomicAdd(&rs::g_bl_stats[23], 1ull);
-        }
-      }
-      if (j >= 2 && j <= 4) {
-        const bool same = __double_as_longlong((double)h0) == __double_as_longlong((double)x.PSIH);
-        const unsigned long long ms = __builtin_amdgcn_ballot_w64(same);
-        if (first) {
-          if (ms == act) atomicAdd(&rs::g_bl_stats[j], 1ull);
-          atomicAdd(&rs::g_bl_stats[3 + j], (unsigned long long)__builtin_popcountll(ms));
-        }
-      }
+      bl_stats_pass(st, j, h0, x);
       if (done) break;
     }
-    { /* trip counts: the lane's, and the wavefront's (how many passes it issued) */
-      const int trips = j > RS_BL_MAXIT ? RS_BL_MAXIT : j;
-      int wmax = trips, wsum = trips;
-      for (int o = 32; o > 0; o >>= 1) {
-        const int other = __shfl_xor(wmax, o, 64);
-        wmax = other > wmax ? other : wmax;
-        wsum += __shfl_xor(wsum, o, 64);
-      }
-      auto bin = [](int t) { return t <= 8 ? t - 5 : t <= 12 ? 4 : t <= 20 ? 5 : t < 40 ? 6 : 7; };
-      for (int b = 0; b < 8; ++b) {
-        const unsigned long long mb = __builtin_amdgcn_ballot_w64(bin(trips) == b);
-        if (first && mb) atomicAdd(&rs::g_bl_stats[32 + b], (unsigned long long)__builtin_popcountll(mb));
-      }
-      {
-        const int nh = __builtin_popcountll(__builtin_amdgcn_ballot_w64(trips > 20));
-        if (first && nh > 0) atomicAdd(&rs::g_bl_stats[40 + (nh == 1 ? 0 : nh <= 3 ? 1 : nh <= 7 ? 2 : nh <= 15 ? 3 : nh <= 31 ? 4 : 5)], 1ull);
-      }
-      if (first) {
-        atomicAdd(&rs::g_bl_stats[9], (unsigned long long)wsum);
-        atomicAdd(&rs::g_bl_stats[8], (unsigned long long)wmax);
-        atomicAdd(&rs::g_bl_stats[24 + bin(wmax)], 1ull);
-      }
-    }
+    bl_stats_trips(st, j);
   }
 #else
 #ifdef RS_EXP_PIPE1 /* (probe: the surface's vapour pressure - independent of the loop - in the block of the peeled first pass) */
@@ -997,7 +1218,11 @@ __device__ __forceinline__ Fluxes model_step_fluxes_prepped(const RS_CONSTS &c, 
     const bool signs = dry_tail_signs(s.wat, raNum, raDen);
 #endif
 #ifdef RS_DRY_ESURF
+#ifdef RS_EAIR_SURFACE
+    const bool warm = signs && dry_tail_warm_t(s.tsurf, q.tair);
+#else
     const bool warm = dry_tail_warm(signs, s.tsurf, q.tair, q.EAir);
+#endif
 #ifndef RS_BL_STATS
     if (rs_wave_all(warm)) {
       fx.le = R4(0.0);
@@ -1016,8 +1241,13 @@ __device__ __forceinline__ Fluxes model_step_fluxes_prepped(const RS_CONSTS &c, 
 #else
     const RS_REAL ESurf = R4(0.61078) * rs_exp(mt, rs_dv<false>(as * s.tsurf, s.tsurf + bs));
 #endif
+#ifdef RS_EAIR_SURFACE
+    const RS_REAL EAir = air_vapour_pressure(mt, q.tair, q.rhz);
+#else
+    const RS_REAL EAir = q.EAir;
+#endif
     /* (AirDens x AirHCap x (...) is (AirDens x AirHCap) x (...): the product arrives as AirVCap) */
-    const RS_REAL N = q.AirVCap * (ESurf - q.EAir);
+    const RS_REAL N = q.AirVCap * (ESurf - EAir);
 #ifdef RS_DRY_TAIL
     const bool le_dry = dry_tail_le(signs, N, a.PsychC);
 #if defined(RS_BL_STATS) && defined(RS_DRY_ESURF)
@@ -1053,6 +1283,7 @@ __device__ __forceinline__ Fluxes model_step_fluxes_prepped(const RS_CONSTS &c, 
   fluxes_post(c, s, q.sw, q.lw, cp, fx);
   return fx;
 }
+#endif /* RS_BL_LAST */
 
 /* One layer of CalcHCapHCond + calcCapDZCondDZ + calcProfile fused (src/BalanceModel.f90:189-251,
  * 132-155, 90-129): heat capacity from the (stale) TmpNw value, capDZ, the flux to the layer below,

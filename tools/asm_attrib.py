@@ -23,6 +23,11 @@ is a rule to repair.
 --check-thawed-skip: exit status 1 unless every select between layer_vsh's frozen constant and its polynomials
 (the v_mov_b32 of 0x413d7ae0, the high word of 920 x 2100, with its two v_cndmask_b32) stands in a block that a
 scalar branch (s_cbranch_scc*) jumps over - what the empty asm statement in layer_vsh is there to keep.
+
+--check-last-pass-skip (file.s with line tables, -gline-tables-only): exit status 1 unless the final stability
+correction of model_step_fluxes_prepped (the instructions inlined from its `bl_arm<false>(mt, Stab, x);`) begins in
+a block that a scalar branch (s_cbranch_scc*, s_cbranch_vcc*) jumps over - what the empty asm statement in front of
+it is there to keep.
 """
 import collections
 import os
@@ -73,6 +78,16 @@ def valu_class(op):
 # (function a frame lies in, substring of that frame's source line or None, wave or None) -> region; first match wins,
 # frames are tried from the innermost outwards.  wave: "surface" / "ground" = the frame chain passes through
 # duo_surface / duo_ground.
+FINAL_ARM = "bl_arm<false>(mt, Stab, x);"  # model_step_fluxes_prepped's final stability correction, by its source text
+FINAL_REGION = "boundary-layer: final correction (skipped where every lane is dead and Stab proves the sign)"
+EAIR_REGION = "CalcLE: EAir (skipped where every lane is dry and warmer than the air)"
+ESURF_REGION = "CalcLE: ESurf (skipped where every lane is dry and warmer than the air)"
+TAIL_REGION = "CalcLE: tail (skipped where every lane is dry and evaporating)"
+# (function, substring) that names the region from ANY frame of the chain, before the innermost-first rules below:
+# the final correction is bl_arm, rs_log and rs_sq like every pass's, told apart by the line it is inlined from
+OUTER = [
+    ("model_step_fluxes_prepped", FINAL_ARM, FINAL_REGION),
+]
 REGIONS = [
     ("boundary_layer_ieee", None, None, "guard (IEEE redo, out of line)"),
     ("knot_forcing", None, None, "knot interpolation"),
@@ -86,21 +101,30 @@ REGIONS = [
     ("duo_put_prep", None, None, "mailbox put"),
     ("duo_get_prep", None, None, "mailbox get"),
     ("check_values_tsurf", None, None, "CheckValues (surface temperature)"),
+    ("air_vapour_pressure", None, None, EAIR_REGION),
     ("rs_log", None, None, "boundary-layer pass: unstable arm, log (two paths, one taken)"),
     ("model_step_fluxes_prepped", "boundary_layer_ieee", None, "guard (IEEE redo, out of line)"),
     ("model_step_fluxes_prepped", "__builtin_inf", None, "ESurf / fluxes"),
     ("dry_tail_signs", None, None, "CalcLE: dry-tail tests"),
     ("dry_tail_le", None, None, "CalcLE: dry-tail tests"),
     ("dry_tail_warm", None, None, "CalcLE: dry-tail tests"),
+    ("dry_tail_dry", None, None, "CalcLE: dry-tail tests"),
+    ("dry_tail_warm_t", None, None, "CalcLE: dry-tail tests"),
+    ("dry_tail_psychc", None, None, "CalcLE: dry-tail tests"),
+    ("model_step_fluxes_prepped", "dry_tail_psychc", None, "CalcLE: dry-tail tests"),
+    ("le_numerator", None, None, ESURF_REGION),
+    ("model_step_fluxes_prepped", "psychrometric", None, TAIL_REGION),
     ("model_step_fluxes_prepped", "rs_wave_all", None, "CalcLE: dry-tail tests"),
-    ("model_step_fluxes_prepped", "RAero", None, "CalcLE: tail (skipped where every lane is dry and evaporating)"),
-    ("model_step_fluxes_prepped", "WatDen", None, "CalcLE: tail (skipped where every lane is dry and evaporating)"),
-    ("model_step_fluxes_prepped", "lfus", None, "CalcLE: tail (skipped where every lane is dry and evaporating)"),
-    ("model_step_fluxes_prepped", "fx.le > ", None, "CalcLE: tail (skipped where every lane is dry and evaporating)"),
-    ("model_step_fluxes_prepped", "ESurf", None, "CalcLE: ESurf (skipped where every lane is dry and warmer than the air)"),
-    ("model_step_fluxes_prepped", "s.tsurf < 0", None, "CalcLE: ESurf (skipped where every lane is dry and warmer than the air)"),
-    ("bl_iteration", "rs_log", None, "boundary-layer pass: unstable arm"),
-    ("bl_iteration", "PSIM = R4(0.6)", None, "boundary-layer pass: unstable arm"),
+    ("model_step_fluxes_prepped", "RAero", None, TAIL_REGION),
+    ("model_step_fluxes_prepped", "WatDen", None, TAIL_REGION),
+    ("model_step_fluxes_prepped", "lfus", None, TAIL_REGION),
+    ("model_step_fluxes_prepped", "fx.le > ", None, TAIL_REGION),
+    ("model_step_fluxes_prepped", "ESurf", None, ESURF_REGION),
+    ("model_step_fluxes_prepped", "s.tsurf < 0", None, ESURF_REGION),
+    ("bl_arm", "rs_log", None, "boundary-layer pass: unstable arm"),
+    ("bl_arm", "PSIM = R4(0.6)", None, "boundary-layer pass: unstable arm"),
+    ("bl_arm", None, None, "boundary-layer pass"),
+    ("bl_pass", None, None, "boundary-layer pass"),
     ("bl_iteration", None, None, "boundary-layer pass"),
     ("fluxes_post", None, None, "ESurf / fluxes"),
     ("model_step_fluxes_prepped", None, None, "ESurf / fluxes"),
@@ -148,8 +172,14 @@ WEIGHTS = {
     "layers 1-2: frozen arm": 1.0 - THAWED, "layers 3-15: frozen arm": 1.0 - THAWED,
     # profiles/r09_dry_tail_counts.txt: every lane dry and evaporating in 0.6458 of the wave-steps, dry and warmer than
     # the air by the margin in 0.4406
-    "CalcLE: tail (skipped where every lane is dry and evaporating)": 1.0 - 0.6458,
-    "CalcLE: ESurf (skipped where every lane is dry and warmer than the air)": 1.0 - 0.4406,
+    # profiles/r10_last_pass_counts.txt: the final correction is skipped in 0.6458 of the wave-steps (every wave-step
+    # in which all lanes are dead: no Stab at or below stabSafe there), and the tail runs where it is not
+    TAIL_REGION: 1.0 - 0.6458,
+    FINAL_REGION: 1.0 - 0.6458,
+    # two copies each of ESurf's and EAir's code: in front of the loop (a wavefront that is not all-warm: 1 - 0.4406)
+    # and in the tail (all-warm and not skipped: no such wave-step on the bench workload) - the mean of the two
+    ESURF_REGION: 0.5 * (1.0 - 0.4406),
+    EAIR_REGION: 0.5 * (1.0 - 0.4406),
     "melting": 0.10,
     "storages": 1.0 - 0.615,            # the bare-road shortcut takes 61.5 % of the wave-steps
     "albedo": 1.0 - 0.615,
@@ -198,6 +228,11 @@ def region_of(frames, funcs):
         return None, info
     fns = [fn for fn, _ in info]
     wave = "surface" if "duo_surface" in fns else "ground" if "duo_ground" in fns else None
+    for fn, text in info:
+        for rfn, sub, region in OUTER:
+            if fn == rfn and sub in text:
+                MATCHED.add((rfn, sub, None, region))
+                return region, info
     for fn, text in info:
         for rule in REGIONS:
             rfn, sub, rwave, region = rule
@@ -299,7 +334,7 @@ def valu_table(path, kernel, src_dir):
             print(f"{region[:62]:62s} {w:6.3f} " + " ".join(f"{c[k]:7d}" for k in VALU_CLASSES) + f" {n:7d} {n * w:8.1f}")
     print(f"{'TOTAL (weighted by class; static; weighted)':62s} {'':6s} " + " ".join(f"{tot_c[k]:7.1f}" for k in VALU_CLASSES)
           + f" {tot_s:7d} {tot_w:8.1f}")
-    idle = [r for r in REGIONS if r not in MATCHED]
+    idle = [r for r in REGIONS + [(f, t, None, r) for f, t, r in OUTER] if r not in MATCHED]
     if idle:
         print("rules that matched no instruction of this kernel's time loops: "
               + "; ".join(f"{r[0]}{' ~ ' + repr(r[1]) if r[1] else ''}{' @' + r[2] if r[2] else ''}" for r in idle))
@@ -330,8 +365,47 @@ def check_thawed_skip(path, kernel):
     return found, bad
 
 
+def check_last_pass_skip(path, kernel, src_dir=None):
+    """(vector instructions of the final stability correction, True where the block its first one stands in is
+    jumped over by a scalar branch); path: assembly with line tables (tests/test_last_pass_skip_asm.py compiles the
+    kernels and calls this)"""
+    src_dir = src_dir or os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "roadsurf_amd", "csrc")
+    funcs = functions_of(src_dir)
+    inside, prev_op, block_guarded, frames, found, guarded = False, None, False, [], 0, False
+    for ln in open(path):
+        if ln.startswith(kernel + ":"):
+            inside = True
+            continue
+        if not inside:
+            continue
+        if ln.startswith(".Lfunc_end"):
+            break
+        if re.match(r"^(\.LBB\d+_\d+:|; %bb\.\d+:)", ln):
+            block_guarded = prev_op is not None and prev_op.startswith(("s_cbranch_scc", "s_cbranch_vcc"))
+            continue
+        m = re.match(r"\s*\.loc\s+\d+\s+\d+.*?;\s*(.*)$", ln)
+        if m:
+            frames = [(a, int(b)) for a, b in re.findall(r"([\w./+-]+):(\d+):\d+", m.group(1))]
+            continue
+        m = re.match(r"\s+([a-z_0-9]+)\s*(.*)", ln)
+        if not m or ln.lstrip().startswith((".", ";")):
+            continue
+        if m.group(1).startswith("v_") and any(fn == "model_step_fluxes_prepped" and FINAL_ARM in text
+                                               for fn, text in (frame_info(funcs, f, l) for f, l in frames if l > 0)):
+            if found == 0:
+                guarded = block_guarded
+            found += 1
+        prev_op = m.group(1)
+    return found, guarded
+
+
 def main():
     path, kernel = sys.argv[1], sys.argv[2]
+    if "--check-last-pass-skip" in sys.argv:
+        found, guarded = check_last_pass_skip(path, kernel)
+        print(f"{found} vector instructions of the final stability correction in {kernel}, "
+              f"{'behind' if guarded else 'NOT behind'} a scalar branch")
+        sys.exit(0 if found and guarded else 1)
     if "--check-thawed-skip" in sys.argv:
         found, bad = check_thawed_skip(path, kernel)
         print(f"{found} frozen/thawed selects in {kernel}, {bad} of them not behind a scalar branch")

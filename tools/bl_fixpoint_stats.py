@@ -19,7 +19,7 @@ run = workload.SyntheticRun(plan, 1, hours, 60, plan_order=True, forecast=True, 
 run.run_pass(None)
 torch.cuda.synchronize()
 L = lib.load()
-out = (C.c_int64 * 8)()
+out = (C.c_int64 * 57)()
 L.rs_hip_bl_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
 assert L.rs_hip_bl_stats(plan._h, out) == 0
 w, l = out[0], out[1]

@@ -30,7 +30,7 @@ else:
     run.run_pass(None)
 torch.cuda.synchronize()
 L = lib.load()
-out = (C.c_int64 * 56)()
+out = (C.c_int64 * 57)()
 L.rs_hip_bl_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
 assert L.rs_hip_bl_stats(plan._h, out) == 0
 ws, ls = max(out[0], 1), max(out[1], 1)
@@ -51,5 +51,9 @@ print(f"  road_condition: {out[10]} wave-steps; bare-road shortcut {out[11] / rc
       f"without snow, ice and deposit {out[16] / rc:.4f}")
 print(f"  CalcLE's tail: the reference zeroes le and evap by sign (dry_tail_le) in every lane of {out[49] / ws:.4f} of the wave-steps, "
       f"{out[50] / ls:.4f} of the lane-steps; warm dry surface (dry_tail_warm) in every lane of {out[51] / ws:.4f}, {out[52] / ls:.4f} of the lane-steps")
+sk = max(out[54], 1)
+print(f"  the loop's last pass: every lane dead by its own tests (the sign of raNum apart) in {out[53] / ws:.4f} of the wave-steps, "
+      f"every lane dry and warm in {out[56] / ws:.4f}; final stability correction skipped in {out[54] / ws:.4f}, "
+      f"{out[55] / sk:.4f} of those with a lane that left the loop on the unstable side")
 fp = max(out[17], 1)
 print(f"  forcing's share: {out[17]} wave-steps, precipitation branch in {out[18] / fp:.4f}")

@@ -13,6 +13,11 @@
 # is neither available here nor bit-reproducible; parity in this project is
 # defined against THIS build.
 #
+# Also built here, further down: libroadrunner_tools_ref.so (MeteorologyTools.cpp alone) and
+# libroadrunner_ref.so, the reference's whole example driver (its twelve .cpp files, compiled
+# where they lie with g++ over the stand-in headers of oracle/shim) behind
+# oracle/driver_ref_harness.cpp.
+#
 # One generated file: flang's preprocessor rejects `#pragma once`
 # (src/Constants.h:1), so the temp dir gets a Constants.h that is the
 # reference's with that one line filtered out (9 #defines, semantics unchanged).
@@ -109,9 +114,34 @@ fi
 
 # ---- the driver's one self-contained C++ file -----------------------------------------
 # examples/example1/src/MeteorologyTools.cpp (CalcTdewOrRH) needs only <cmath>; it pins
-# oracle/driver_oracle.c's restatement.  The rest of the driver (JsonSource.cpp,
-# roadrunner.cpp) needs jsoncpp, which this image lacks: unbuildable, see driver_oracle.c.
+# oracle/driver_oracle.c's restatement of that one function.
 # Strict flags (the reference's own are -funsafe-math-optimizations ..., Makefile:6).
 g++ -O2 -fPIC -shared -ffp-contract=off -I"$REF/examples/example1/src" \
     "$REF/examples/example1/src/MeteorologyTools.cpp" -o "$OUT/libroadrunner_tools_ref.so"
 echo "built $OUT/libroadrunner_tools_ref.so"
+
+# ---- the reference's whole example driver as a library -----------------------------------
+# All twelve .cpp of examples/example1/src, compiled where they lie, plus our
+# oracle/driver_ref_harness.cpp (an extern "C" surface over read_json, InputSettings,
+# DataHandler, InputParameters, SkyView, read_input and runsimulation).  The driver includes
+# <json/json.h> and <fmt/format.h>; oracle/shim holds our own stand-ins for the part of the
+# two libraries it uses.  roadrunner.cpp gets -Dmain=roadrunner_ref_main so that read_input,
+# get_times and `options` can be linked.  Same strict flags as above; runsimulation comes from
+# libroadsurf_ref_cpl.so beside it.  It pins oracle/driver_oracle.c, the device data path and
+# roadsurf_amd/roadrunner.py (tests/test_driver_reference.py, tests/test_hip_driver_reference.py).
+DRV="$REF/examples/example1/src"
+DRV_FLAGS="-std=c++17 -O2 -fPIC -ffp-contract=off -w -I$HERE/shim -I$DRV"
+mkdir -p "$TMP/drv"
+n_cpp=0
+for f in "$DRV"/*.cpp; do
+  b="$(basename "$f" .cpp)"
+  extra=""
+  [ "$b" = "roadrunner" ] && extra="-Dmain=roadrunner_ref_main"
+  g++ $DRV_FLAGS $extra -c "$f" -o "$TMP/drv/$b.o"
+  n_cpp=$((n_cpp + 1))
+done
+[ "$n_cpp" = "12" ] || { echo "build_ref: $n_cpp driver sources, 12 expected - reference changed?" >&2; exit 1; }
+g++ $DRV_FLAGS -Wall -c "$HERE/driver_ref_harness.cpp" -o "$TMP/drv/driver_ref_harness.o"
+g++ -shared -o "$OUT/libroadrunner_ref.so" "$TMP"/drv/*.o -L"$OUT" -lroadsurf_ref_cpl \
+    -Wl,-rpath,'$ORIGIN' -lpthread
+echo "built $OUT/libroadrunner_ref.so"

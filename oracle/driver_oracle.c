@@ -16,12 +16,17 @@
  * one InputData), NOT the way the device code is organised (time plan + per-variable
  * streaming), so the two are independent statements of the same behaviour.
  *
- * PINNING.  MeteorologyTools.cpp compiles on its own: oracle/build_ref.sh builds it with
- * g++ into oracle/_ref/libroadrunner_tools_ref.so and tests/test_driver_oracle.py holds
- * oracle_calc_tdew_or_rh to it bit for bit.  JsonSource.cpp and roadrunner.cpp need jsoncpp,
- * which this image does not have, and the reference ships no tests or fixtures for them:
- * for interpolate / GetWeather / read_input this restatement is PARITY UNPINNED (checked
- * only against hand-worked cases in tests/test_driver_oracle.py).
+ * PINNING.  oracle/build_ref.sh compiles the reference's whole example driver as it stands
+ * (g++ -std=c++17 -O2 -fPIC -ffp-contract=off, over our stand-ins for jsoncpp and fmt in
+ * oracle/shim) into oracle/_ref/libroadrunner_ref.so, with oracle/driver_ref_harness.cpp as
+ * its C surface.  tests/test_driver_reference.py holds this file to it bit for bit on
+ * generated configurations and input files: merged series, status, missing_index and the
+ * relaxation / coupling decisions against the reference's read_input, and whole runs against
+ * its read_input + runsimulation.  tests/test_driver_oracle.py keeps the hand-worked cases and
+ * holds oracle_calc_tdew_or_rh to MeteorologyTools.cpp on its own.  Not pinned: what depends
+ * on jsoncpp behaviour the stand-in only follows on paper (null entries in a value array,
+ * arrays shorter than "time"), and status 7, where the reference reads past its vectors
+ * (DESIGN.md 4).
  * The reference builds its C++ with -funsafe-math-optimizations -freciprocal-math
  * (examples/example1/Makefile:6); like the Fortran side, parity here is defined against the
  * strict evaluation of the source expressions (no reassociation, IEEE division).

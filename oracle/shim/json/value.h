@@ -1,0 +1,3 @@
+/* oracle/shim/json/value.h — TEST INFRASTRUCTURE: the whole stand-in lives in json/json.h (see there). */
+#pragma once
+#include "json.h"

@@ -2,9 +2,10 @@
 
 * CalcTdewOrRH restatement vs the reference's own MeteorologyTools.cpp compiled with g++
   (oracle/_ref/libroadrunner_tools_ref.so): bit for bit.
-* interpolate / GetWeather / read_input: the reference files need jsoncpp and cannot be built
-  here (PARITY UNPINNED, see oracle/driver_oracle.c); they are held to hand-worked cases
-  chosen so that every expected value is exact in binary."""
+* interpolate / GetWeather / read_input: hand-worked cases chosen so that every expected value is
+  exact in binary.  The same code is held to the reference's own C++ driver, compiled as it stands,
+  on generated inputs in tests/test_driver_reference.py; these cases stay as the readable statement
+  of each quirk."""
 import ctypes as C
 import os
 

@@ -1073,46 +1073,34 @@ typedef struct RsDriverOutput {
   int32_t *missing_index;       /* [n_points] 0-based index of the first missing value, else -1 */
 } RsDriverOutput;
 
-/* local[n_points]: in lat, lon, sky_view (others ignored); out InitLenI, tair_relax,
- * VZ_relax, RH_relax, couplingIndexI, couplingTsurf as read_input leaves them.
- * device >= 0: that device; device < 0: fan-out over the device list like rs_host_run_batch.
- * Returns 0 or <0 (rs_last_error). */
-int rs_driver_run(const RsDriverInput *in, const InputSettings *settings,
-                  const InputParameters *params, LocalParameters *local,
-                  const RsDriverOutput *out, int32_t device);
-/* The same with per-point summaries of the kept rows [first_row, last_row] of n_out (the caller passes the forecast
+/* What a call may ask for beside the six series, each an optional member of RsDriverRequest (below).  The ABI number
+ * did not move for any of them: every name is new, and a binding detects a call by looking for its symbol.
+ *
+ * RsDriverSummary: per-point summaries of the kept rows [first_row, last_row] of n_out (the caller passes the forecast
  * part): RS_SUM_COLS doubles per point as rs_hip_outputs_summary defines them, the time index of kept row r being
  * r*step + 1.  They are reduced on the device from the tile's result block, behind the blanking of rejected points
  * (whose summary is the empty one) and behind every coupling replay, and only n_points * RS_SUM_COLS doubles come
  * back for them.  The six series pointers of `out` may all be NULL: a call for the summaries alone transposes and
- * downloads no series.  `summary` NULL: rs_driver_run. */
+ * downloads no series. */
 typedef struct RsDriverSummary {
   RsSummarySpec spec;
   int32_t first_row, last_row;
   double *summary; /* host [n_points][RS_SUM_COLS] */
 } RsDriverSummary;
-int rs_driver_run_summary(const RsDriverInput *in, const InputSettings *settings,
-                          const InputParameters *params, LocalParameters *local,
-                          const RsDriverOutput *out, const RsDriverSummary *summary, int32_t device);
-/* ... and with per-group series of the kept rows [first_row, last_row] (rs_hip_outputs_groups defines the cells):
+/* RsDriverGroups: per-group series of the kept rows [first_row, last_row] (rs_hip_outputs_groups defines the cells):
  * group[n_points] gives every point's group, and series[r - first_row][g][col] is the cell of kept row r.  They are
  * reduced where the summaries are - from the tile's result block, behind the blanking of rejected points (whose rows
  * are -9999.0 and count nowhere) and behind every coupling replay.  A block of points keeps one accumulator on its
  * device across its tiles, and a tile's slice of `group` goes up with the tile; with device < 0 every block of the
  * fan-out reduces its own and the host merges them by the rule of the definition.  Only rows x ngroups x cols doubles
- * come home for them; the six series pointers of `out` may all be NULL.  `summary` may be NULL; `groups` NULL:
- * rs_driver_run_summary. */
+ * come home for them; the six series pointers of `out` may all be NULL. */
 typedef struct RsDriverGroups {
   RsGroupSpec spec;
   const int32_t *group; /* host [n_points] */
   int32_t first_row, last_row;
   double *series; /* host [last_row - first_row + 1][ngroups][cols] */
 } RsDriverGroups;
-int rs_driver_run_groups(const RsDriverInput *in, const InputSettings *settings,
-                         const InputParameters *params, LocalParameters *local,
-                         const RsDriverOutput *out, const RsDriverSummary *summary, const RsDriverGroups *groups,
-                         int32_t device);
-/* ... and with sources that arrive as the weather model delivers them: fields [n_times][n_nodes] plus one stencil per
+/* RsGridSource: a source that arrives as the weather model delivers it: fields [n_times][n_nodes] plus one stencil per
  * point (rs_hip_gather_nodes defines the gather; its presence threshold is the reference's own, `> -100.0`, for lw_net
  * `> -1000.0`, and its missing value -9999.9).  grids[s] != NULL makes source s a gridded one: in->sources[s] then
  * supplies n_times, times and is_observation only - a shared time axis, every field pointer and `lengths` NULL - and
@@ -1123,7 +1111,7 @@ int rs_driver_run_groups(const RsDriverInput *in, const InputSettings *settings,
  * columns [n_times][point] are filled by the gather kernel instead of a transpose; everything behind them runs as it
  * does for per-point sources.  Before any device work the host checks every gridded source - stencil in
  * 1..RS_GRID_MAX_STENCIL, finite weights, every node under a non-zero weight inside [0, n_nodes) - and refuses the
- * call with the first offending point named.  `grids` NULL, or all its entries NULL: rs_driver_run_groups. */
+ * call with the first offending point named.  `grids` NULL, or all its entries NULL: every source is per point. */
 typedef struct RsGridSource {
   int64_t n_nodes;
   const double *tair, *rhz, *tdew, *vz, *prec, *lw_net, *lw, *sw, *sw_dir, *tsurfobs; /* host [n_times][n_nodes]; NULL = absent */
@@ -1131,12 +1119,8 @@ typedef struct RsGridSource {
   const int32_t *node;  /* host [n_points][stencil] */
   const double *weight; /* host [n_points][stencil] */
 } RsGridSource;
-int rs_driver_run_grid(const RsDriverInput *in, const RsGridSource *const *grids /* [n_sources] */,
-                       const InputSettings *settings, const InputParameters *params, LocalParameters *local,
-                       const RsDriverOutput *out, const RsDriverSummary *summary, const RsDriverGroups *groups,
-                       int32_t device);
-/* ... and with the INPUTS the model saw at the kept rows, and the dew-point deficit there (the ABI number stays: every
- * name here is new, a binding detects them with rs_driver_kept_fields).  The reference's operational program stores,
+/* RsDriverKept: the INPUTS the model saw at the kept rows, and the dew-point deficit there (a binding checks the length
+ * of `merged` with rs_driver_kept_fields).  The reference's operational program stores,
  * per point and output time, the surface temperature, the air temperature, the dew point and their difference, the
  * hoar-frost and condensation indicator (examples/example2/src/QueryDataTools.cpp:285-296, 323-347); these are the
  * merged, interpolated, Tdew / RH-completed series read_input hands to runsimulation, which no other call returns
@@ -1156,20 +1140,16 @@ int rs_driver_run_grid(const RsDriverInput *in, const RsGridSource *const *grids
  * `kept`; the six series pointers of `out` may all be NULL.  A tile makes the wanted variables one at a time from its
  * raw columns and plans, which stay on the device for the whole tile, into ONE extra [n_out][points] buffer (0.2 GB for
  * 524 288 points and 49 rows), on the tile's stream, behind its time loop; columns at or beyond the tile's points are
- * never sent to the host.  With device < 0 every block writes its own points' rows.  `kept` NULL, or all its eleven
- * pointers NULL: rs_driver_run_grid.  tools/bench_kept_rows.py measures the cost (profiles/kept_rows.txt). */
+ * never sent to the host.  With device < 0 every block writes its own points' rows.  All its eleven pointers NULL: as
+ * without it.  tools/bench_kept_rows.py measures the cost (profiles/kept_rows.txt). */
 typedef struct RsDriverKept {
   double *merged[10]; /* host [n_points][n_out] each, order of rs_driver_expand's `merged`
                          (tair, tdew, VZ, Rhz, prec, SW, LW, SW_dir, LW_net, TSurfObs); NULL = not wanted */
   double *deficit;    /* host [n_points][n_out] or NULL */
 } RsDriverKept;
 int32_t rs_driver_kept_fields(void); /* 10: the length of RsDriverKept::merged in the library */
-int rs_driver_run_kept(const RsDriverInput *in, const RsGridSource *const *grids /* [n_sources] or NULL */,
-                       const InputSettings *settings, const InputParameters *params, LocalParameters *local,
-                       const RsDriverOutput *out, const RsDriverSummary *summary, const RsDriverGroups *groups,
-                       const RsDriverKept *kept, int32_t device);
-/* ... and with per-point threshold episodes of the kept rows [first_row, last_row] (rs_hip_outputs_episodes defines
- * them; the ABI number stays, a binding detects the call with rs_hip_episode_cols): cols = rs_hip_episode_cols(&spec)
+/* RsDriverEpisodes: per-point threshold episodes of the kept rows [first_row, last_row] (rs_hip_outputs_episodes defines
+ * them; a binding detects them with rs_hip_episode_cols): cols = rs_hip_episode_cols(&spec)
  * doubles per point, FINISHED, the time index of kept row r being r*step + 1.  Every tile resets its accumulator, feeds
  * the rows in one call from its result block - where the summaries are reduced: behind the blanking of rejected points,
  * whose episodes are the empty accumulator, and behind every coupling replay -, finishes, and only n_points * cols
@@ -1178,16 +1158,54 @@ int rs_driver_run_kept(const RsDriverInput *in, const RsGridSource *const *grids
  * the same call, made once per tile when both want them, in one further [n_out][points] buffer of the tile (0.2 GB for
  * 524 288 points and 49 rows).  With device < 0 every block writes its own points' rows.  The six series pointers of
  * `out` may all be NULL.  The six outputs, the summaries, the group series, the kept arrays, status, missing_index and
- * `local` of a call do not depend on `episodes`.  `episodes` NULL: rs_driver_run_kept. */
+ * `local` of a call do not depend on `episodes`. */
 typedef struct RsDriverEpisodes {
   RsEpisodeSpec spec;
   int32_t first_row, last_row;
   double *episodes; /* host [n_points][cols] */
 } RsDriverEpisodes;
+
+/* What one call wants beside the six series: any subset, a NULL member = not wanted.  A further product is a further
+ * member here, not a further entry. */
+typedef struct RsDriverRequest {
+  const RsGridSource *const *grids; /* [n_sources] or NULL */
+  const RsDriverSummary *summary;   /* or NULL */
+  const RsDriverGroups *groups;     /* or NULL */
+  const RsDriverKept *kept;         /* or NULL */
+  const RsDriverEpisodes *episodes; /* or NULL */
+} RsDriverRequest;
+/* local[n_points]: in lat, lon, sky_view (others ignored); out InitLenI, tair_relax,
+ * VZ_relax, RH_relax, couplingIndexI, couplingTsurf as read_input leaves them.
+ * device >= 0: that device; device < 0: fan-out over the device list like rs_host_run_batch.
+ * `request` NULL, or all its members NULL: the six series, status, missing_index and `local` alone.
+ * Returns 0 or <0 (rs_last_error; a refused member is named by the older entry that introduced it). */
+int rs_driver_run_request(const RsDriverInput *in, const InputSettings *settings, const InputParameters *params,
+                          LocalParameters *local, const RsDriverOutput *out, const RsDriverRequest *request /* or NULL */,
+                          int32_t device);
+/* The older entries, one per product as it arrived: each is rs_driver_run_request with the request shown. */
+int rs_driver_run(const RsDriverInput *in, const InputSettings *settings,
+                  const InputParameters *params, LocalParameters *local,
+                  const RsDriverOutput *out, int32_t device); /* request NULL */
+int rs_driver_run_summary(const RsDriverInput *in, const InputSettings *settings,
+                          const InputParameters *params, LocalParameters *local,
+                          const RsDriverOutput *out, const RsDriverSummary *summary, int32_t device); /* {NULL, summary} */
+int rs_driver_run_groups(const RsDriverInput *in, const InputSettings *settings,
+                         const InputParameters *params, LocalParameters *local,
+                         const RsDriverOutput *out, const RsDriverSummary *summary, const RsDriverGroups *groups,
+                         int32_t device); /* {NULL, summary, groups} */
+int rs_driver_run_grid(const RsDriverInput *in, const RsGridSource *const *grids /* [n_sources] */,
+                       const InputSettings *settings, const InputParameters *params, LocalParameters *local,
+                       const RsDriverOutput *out, const RsDriverSummary *summary, const RsDriverGroups *groups,
+                       int32_t device); /* {grids, summary, groups} */
+int rs_driver_run_kept(const RsDriverInput *in, const RsGridSource *const *grids /* [n_sources] or NULL */,
+                       const InputSettings *settings, const InputParameters *params, LocalParameters *local,
+                       const RsDriverOutput *out, const RsDriverSummary *summary, const RsDriverGroups *groups,
+                       const RsDriverKept *kept, int32_t device); /* {grids, summary, groups, kept} */
 int rs_driver_run_episodes(const RsDriverInput *in, const RsGridSource *const *grids /* [n_sources] or NULL */,
                            const InputSettings *settings, const InputParameters *params, LocalParameters *local,
                            const RsDriverOutput *out, const RsDriverSummary *summary, const RsDriverGroups *groups,
-                           const RsDriverKept *kept, const RsDriverEpisodes *episodes, int32_t device);
+                           const RsDriverKept *kept, const RsDriverEpisodes *episodes,
+                           int32_t device); /* {grids, summary, groups, kept, episodes} */
 /* Tiles: a call steps its points in tiles of ROADSURF_HIP_TILE_POINTS (default 524 288).  With
  * coupling the forcing windows of a tile span [first coupling-window start, last window end + 1]
  * of ITS points; a tile whose windows would exceed ROADSURF_HIP_WINDOW_BUDGET_MB (default 24 576)
@@ -1246,7 +1264,8 @@ const char *rs_build_sha16(void);
 int rs_abi_version(void);
 /* sizeof of the boundary structs as the C side / the Fortran side see them
  * (0 InputPointers, 1 OutputPointers, 2 InputSettings, 3 InputParameters,
- * 4 LocalParameters, 5 RsConstants); bindings assert that they agree. */
+ * 4 LocalParameters, 5 RsConstants; rs_abi_sizeof alone goes on through the structs of the device API and the
+ * driver, to 23 RsDriverRequest); bindings assert that they agree. */
 int64_t rs_abi_sizeof(int which);
 int64_t rs_fortran_sizeof(int which);
 

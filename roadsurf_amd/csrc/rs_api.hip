@@ -166,6 +166,11 @@ int64_t rs_abi_sizeof(int which) {
     case 16: return sizeof(RsDriverSummary);
     case 17: return sizeof(RsGroupSpec);
     case 18: return sizeof(RsDriverGroups);
+    case 19: return sizeof(RsEpisodeSpec);
+    case 20: return sizeof(RsGridSource);
+    case 21: return sizeof(RsDriverKept);
+    case 22: return sizeof(RsDriverEpisodes);
+    case 23: return sizeof(RsDriverRequest);
     default: return -1;
   }
 }

@@ -9,6 +9,7 @@
 #include <algorithm>
 
 #include "rs_ens_table.hpp"
+#include "rs_group_rule.hpp"
 #include "rs_kernels.h"
 #include "rs_state.h"
 
@@ -545,7 +546,7 @@ struct GroupArgs {
 
 /* the empty value of column c: counts 0, min +inf, maxima -inf */
 __device__ __forceinline__ double grp_empty(int c) {
-  return c == 1 ? __builtin_huge_val() : (c == 2 || (c >= 9 && c < RS_GRP_COLS)) ? -__builtin_huge_val() : 0.0;
+  return rs_grp::empty(c);
 }
 
 /* the group of slot s, or -1: no point, or a point of no group */

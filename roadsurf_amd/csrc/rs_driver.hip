@@ -44,6 +44,7 @@
 #include "rs_devutil.hpp"
 #include "rs_state.h"
 #include "rs_devices.hpp"
+#include "rs_group_rule.hpp"
 #include "rs_kernels.h"
 #include "rs_raw.hpp"
 
@@ -1537,11 +1538,8 @@ struct Run : Call {
   PhaseTimer &pt;
   WindowLease &win;
   size_t win_bytes; /* of the block `win` holds */
-  const RsDriverSummary *sum; /* NULL: no summaries (rs_driver_run) */
-  const RsDriverGroups *grp;  /* NULL: no group series */
-  double *grp_acc;            /* device [rows][ngroups][cols]: this block's cells, merged into by every tile */
-  const RsDriverKept *kept;   /* NULL: no kept input rows, no deficit */
-  const RsDriverEpisodes *epi; /* NULL: no threshold episodes */
+  const RsDriverRequest &q; /* what the call wants beside the series, normalised (driver_run); NULL member: not that */
+  double *grp_acc;          /* device [rows][ngroups][cols]: this block's group cells, merged into by every tile */
 };
 
 /* tiles the calling thread's last single-device rs_driver_run stepped (tests: the window budget), and how many
@@ -1981,49 +1979,52 @@ struct Tile : TileHead {
     }
     return 0;
   }
+  /* the six row pointers of the result block at kept row first_row: what the reducers of rs_cluster.hip read */
+  void result_rows(const void *in[6], int first_row) const {
+    for (int f = 0; f < 6; ++f) in[f] = d_out.as<double>() + (size_t)f * os + (size_t)first_row * mp;
+  }
+  /* a block [rows][mp] on the device -> [point][rows] in `pt` -> the tile's rows, from p0, of a host array
+   * [n_points][rows] */
+  int block_home(const double *block, double *pt, int rows, double *host) {
+    HOK(transpose(block, pt, rows, m, mp, rows, stream));
+    HOK(hipMemcpyAsync(host + (size_t)p0 * rows, pt, (size_t)m * rows * sizeof(double), hipMemcpyDeviceToHost, stream));
+    return 0;
+  }
   /* The summaries of the kept rows [first_row, last_row] (rs_driver_run_summary): reduced from the result block, which
    * is in point order, final (every coupling replay has rewritten its rows) and blanked where read_input rejected the
    * point; RS_SUM_COLS doubles per point come home for them. */
   int summaries_home() {
-    const RsDriverSummary &q = *r.sum;
+    const RsDriverSummary &q = *r.q.summary;
     HOK(d_sum.alloc((size_t)RS_SUM_COLS * mp * sizeof(double)));
     HOK(d_sumpt.alloc((size_t)m * RS_SUM_COLS * sizeof(double)));
     HOK(rs_cluster_summary_reset(d_sum.as<double>(), mp, stream));
     const void *in[6];
-    for (int f = 0; f < 6; ++f) in[f] = d_out.as<double>() + (size_t)f * os + (size_t)q.first_row * mp;
+    result_rows(in, q.first_row);
     HOK(rs_cluster_outputs_summary(in, false, nullptr, m, mp, q.last_row - q.first_row + 1, q.first_row * R.step + 1,
                                    R.step, q.spec, d_sum.as<double>(), mp, stream));
-    HOK(transpose((const double *)d_sum.as<double>(), d_sumpt.as<double>(), RS_SUM_COLS, m, mp, RS_SUM_COLS, stream));
-    HOK(hipMemcpyAsync(q.summary + (size_t)p0 * RS_SUM_COLS, d_sumpt.p, (size_t)m * RS_SUM_COLS * sizeof(double),
-                       hipMemcpyDeviceToHost, stream));
-    return 0;
+    return block_home(d_sum.as<double>(), d_sumpt.as<double>(), RS_SUM_COLS, q.summary);
   }
   /* The group series of the kept rows [first_row, last_row] (rs_driver_run_groups), from the same final, blanked
    * result block: the tile's points merge into the block's accumulator, which comes home behind the last tile. */
   int groups_home() {
-    const RsDriverGroups &q = *r.grp;
+    const RsDriverGroups &q = *r.q.groups;
     HOK(d_gid.alloc((size_t)m * sizeof(int32_t)));
     HOK(hipMemcpyAsync(d_gid.p, q.group + p0, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, stream));
     const void *in[6];
-    for (int f = 0; f < 6; ++f) in[f] = d_out.as<double>() + (size_t)f * os + (size_t)q.first_row * mp;
+    result_rows(in, q.first_row);
     HOK(rs_cluster_outputs_groups(in, false, nullptr, d_gid.as<int32_t>(), m, mp, q.last_row - q.first_row + 1, q.spec,
                                   r.grp_acc, stream));
     return 0;
   }
-  /* a block [n_out][mp] -> [point][row] -> the tile's rows of a host array [n_points][n_out] */
-  int kept_block_home(const double *block, double *host) {
-    HOK(transpose(block, d_outpt.as<double>(), R.n_out, m, mp, R.n_out, stream));
-    HOK(hipMemcpyAsync(host + (size_t)p0 * R.n_out, d_outpt.p, (size_t)m * R.n_out * sizeof(double), hipMemcpyDeviceToHost,
-                       stream));
-    return 0;
-  }
+  /* a block [n_out][mp] -> the tile's rows of a host array [n_points][n_out] */
+  int rows_home(const double *block, double *host) { return block_home(block, d_outpt.as<double>(), R.n_out, host); }
   /* The inputs at the kept rows and the dew-point deficit (rs_driver_run_kept): the wanted variables one at a time from
    * the tile's raw columns and plans through the one buffer - the dew point first, which the deficit then replaces in
    * place, reading the final, blanked surface temperature rows of the result block.  Where the episodes read the
    * deficit (rs_driver_run_episodes) the dew point's turn goes through a buffer of its own, which keeps the deficit
    * for episodes_home: it is made once, whoever wants it. */
   int kept_home() {
-    const RsDriverKept *q = r.kept;
+    const RsDriverKept *q = r.q.kept;
     if (q) HOK(d_kept.alloc(os * sizeof(double)));
     if (R.epi_deficit) HOK(d_epidef.alloc(os * sizeof(double)));
     KeptRowsArgs ka;
@@ -2051,13 +2052,13 @@ struct Tile : TileHead {
         hipLaunchKernelGGL(kept_rows_kernel<false>, g, b, 0, stream, ka);
       HOK(hipGetLastError());
       if (host)
-        if (int rc = kept_block_home(block, host)) return rc;
+        if (int rc = rows_home(block, host)) return rc;
       if (deficit) {
         hipLaunchKernelGGL(deficit_kernel, grid1(m), dim3(RS_BLOCK), 0, stream, (const double *)d_out.as<double>(), block,
                            (int64_t)mp, (int32_t)R.n_out, (int64_t)m);
         HOK(hipGetLastError());
         if (q && q->deficit)
-          if (int rc = kept_block_home(block, q->deficit)) return rc;
+          if (int rc = rows_home(block, q->deficit)) return rc;
       }
     }
     return 0;
@@ -2066,21 +2067,18 @@ struct Tile : TileHead {
    * result block as the summaries and - where the spec uses it - the deficit kept_home left in d_epidef: reset, one feed
    * of the rows in order, finish; cols doubles per point come home for them. */
   int episodes_home() {
-    const RsDriverEpisodes &q = *r.epi;
+    const RsDriverEpisodes &q = *r.q.episodes;
     const int cols = R.epi_cols;
     HOK(d_epi.alloc((size_t)cols * mp * sizeof(double)));
     HOK(d_epipt.alloc((size_t)m * cols * sizeof(double)));
     HOK(rs_cluster_episodes_reset(d_epi.as<double>(), mp, q.spec, stream));
     const void *in[6];
-    for (int f = 0; f < 6; ++f) in[f] = d_out.as<double>() + (size_t)f * os + (size_t)q.first_row * mp;
+    result_rows(in, q.first_row);
     const void *def = R.epi_deficit ? d_epidef.as<double>() + (size_t)q.first_row * mp : nullptr;
     HOK(rs_cluster_outputs_episodes(in, def, false, nullptr, m, mp, q.last_row - q.first_row + 1,
                                     q.first_row * R.step + 1, R.step, q.spec, d_epi.as<double>(), mp, stream));
     HOK(rs_cluster_episodes_finish(d_epi.as<double>(), m, mp, q.spec, stream));
-    HOK(transpose((const double *)d_epi.as<double>(), d_epipt.as<double>(), cols, m, mp, cols, stream));
-    HOK(hipMemcpyAsync(q.episodes + (size_t)p0 * cols, d_epipt.p, (size_t)m * cols * sizeof(double),
-                       hipMemcpyDeviceToHost, stream));
-    return 0;
+    return block_home(d_epi.as<double>(), d_epipt.as<double>(), cols, q.episodes);
   }
   /* blank what read_input rejected, then [row][point] -> [point][row] -> the caller's arrays */
   int outputs_home() {
@@ -2088,21 +2086,18 @@ struct Tile : TileHead {
     hipLaunchKernelGGL(blank_rejected_kernel, grid1(m), dim3(RS_BLOCK), 0, stream, ob, (int64_t)mp,
                        (int32_t)R.n_out, (int64_t)m, (const int32_t *)D.status.as<int32_t>());
     HOK(hipGetLastError());
-    if (r.sum)
+    if (r.q.summary)
       if (int rc = summaries_home()) return rc;
-    if (r.grp)
+    if (r.q.groups)
       if (int rc = groups_home()) return rc;
-    if (r.kept || R.epi_deficit)
+    if (r.q.kept || R.epi_deficit)
       if (int rc = kept_home()) return rc;
-    if (r.epi)
+    if (r.q.episodes)
       if (int rc = episodes_home()) return rc;
     double *dst[6] = {r.out->tsurf, r.out->snow, r.out->water, r.out->ice, r.out->deposit, r.out->ice2};
-    for (int f = 0; f < 6; ++f) {
-      if (!dst[f]) continue;
-      HOK(transpose((const double *)ob + (size_t)f * os, d_outpt.as<double>(), R.n_out, m, mp, R.n_out, stream));
-      HOK(hipMemcpyAsync(dst[f] + (size_t)p0 * R.n_out, d_outpt.p, (size_t)m * R.n_out * sizeof(double),
-                         hipMemcpyDeviceToHost, stream));
-    }
+    for (int f = 0; f < 6; ++f)
+      if (dst[f])
+        if (int rc = rows_home(ob + (size_t)f * os, dst[f])) return rc;
     HOK(hipStreamSynchronize(stream));
     r.pt.lap(5);
     for (Dev *d : {&d_phase, &d_outc, &d_pp_s, &d_geo_s, &d_out, &d_outpt, &d_prev, &d_sum, &d_sumpt, &d_gid, &d_kept, &d_epidef, &d_epi, &d_epipt}) d->release();
@@ -2180,32 +2175,41 @@ int upload_shared_axes(const Call &k, const RunPolicy &R, int64_t pbeg, int64_t 
  * (roadsurf_amd/groups.py, merge) */
 void merge_group_cells(double *a, const double *b, size_t ncells, int cols) {
   for (size_t i = 0; i < ncells; ++i, a += cols, b += cols)
-    for (int c = 0; c < cols; ++c) {
-      if (c == 1)
-        a[c] = b[c] < a[c] ? b[c] : a[c];
-      else if (c == 2 || (c >= 9 && c < RS_GRP_COLS))
-        a[c] = b[c] > a[c] ? b[c] : a[c];
-      else
-        a[c] += b[c];
-    }
+    for (int c = 0; c < cols; ++c) a[c] = rs_grp::merge(c, a[c], b[c]);
 }
 std::mutex g_group_merge; /* the blocks of a fan-out merge into the caller's one array */
 
-int check_groups(const RsDriverGroups *grp, int n_out) {
-  if (!grp) return 0;
-  if (rs_cluster_group_cols(&grp->spec) < 0)
-    return fail_msg("rs_driver_run_groups: bad spec (ngroups >= 1, nedges <= RS_GRP_MAX_EDGES, edges strictly increasing)", -1);
-  if (!grp->group || !grp->series || grp->first_row < 0 || grp->last_row < grp->first_row || grp->last_row >= n_out)
-    return fail_msg("rs_driver_run_groups: group and series are required, with 0 <= first_row <= last_row < n_out", -1);
+/* ---- the request's argument checks.  A message names the entry that introduced the member, whichever entry the call
+ * came in through.  What a caller can observe fixes their order: the episodes, then the groups, before anything else
+ * of the call (check_request, once, on the calling thread); the summary's rows behind the checks of the run's own
+ * arguments (check_summary, in every worker: n_out is only known to be the run's there). */
+bool rows_in(int first_row, int last_row, int n_out) { return first_row >= 0 && last_row >= first_row && last_row < n_out; }
+
+int check_request(RsDriverRequest &q, const RsDriverOutput *out) {
+  if ((q.episodes || q.groups) && !out) return fail_msg("rs_driver_run: bad arguments", -1);
+  if (const RsDriverEpisodes *e = q.episodes) {
+    if (rs_cluster_episode_cols(&e->spec) < 0)
+      return fail_msg("rs_driver_run_episodes: bad spec (use: bits 0..6, at least one; no NaN bound; peak 0..6; min_rows >= 1; max_episodes 1..RS_EPI_MAX)", -1);
+    if (!e->episodes || !rows_in(e->first_row, e->last_row, out->n_out))
+      return fail_msg("rs_driver_run_episodes: episodes is required, with 0 <= first_row <= last_row < n_out", -1);
+  }
+  if (const RsDriverKept *k = q.kept) { /* nothing wanted: as without */
+    bool any = k->deficit != nullptr;
+    for (int f = 0; f < NFLD; ++f) any = any || k->merged[f];
+    if (!any) q.kept = nullptr;
+  }
+  if (const RsDriverGroups *g = q.groups) {
+    if (rs_cluster_group_cols(&g->spec) < 0)
+      return fail_msg("rs_driver_run_groups: bad spec (ngroups >= 1, nedges <= RS_GRP_MAX_EDGES, edges strictly increasing)", -1);
+    if (!g->group || !g->series || !rows_in(g->first_row, g->last_row, out->n_out))
+      return fail_msg("rs_driver_run_groups: group and series are required, with 0 <= first_row <= last_row < n_out", -1);
+  }
   return 0;
 }
 
-int check_episodes(const RsDriverEpisodes *epi, int n_out) {
-  if (!epi) return 0;
-  if (rs_cluster_episode_cols(&epi->spec) < 0)
-    return fail_msg("rs_driver_run_episodes: bad spec (use: bits 0..6, at least one; no NaN bound; peak 0..6; min_rows >= 1; max_episodes 1..RS_EPI_MAX)", -1);
-  if (!epi->episodes || epi->first_row < 0 || epi->last_row < epi->first_row || epi->last_row >= n_out)
-    return fail_msg("rs_driver_run_episodes: episodes is required, with 0 <= first_row <= last_row < n_out", -1);
+int check_summary(const RsDriverSummary *sum, int n_out) {
+  if (sum && (!sum->summary || !rows_in(sum->first_row, sum->last_row, n_out)))
+    return fail_msg("rs_driver_run_summary: summary is required, with 0 <= first_row <= last_row < n_out", -1);
   return 0;
 }
 
@@ -2311,24 +2315,22 @@ int upload_grids(const RsDriverInput *in, const RsGridSource *const *grids, cons
 
 /* points [pbeg, pend) of the input on one device */
 int driver_run_range(const RsDriverInput *in, const InputSettings *st, const InputParameters *params,
-                     LocalParameters *local, const RsDriverOutput *out, const RsDriverSummary *sum,
-                     const RsDriverGroups *grp, const RsDriverKept *kept, const RsDriverEpisodes *epi, int32_t device,
+                     LocalParameters *local, const RsDriverOutput *out, const RsDriverRequest &q, int32_t device,
                      int64_t pbeg, int64_t pend, const GridView *gv = nullptr) {
   Common c;
   RunPolicy R;
   RsConstants consts;
   if (int rc = prepare(in, st, c, gv)) return rc;
   if (int rc = check_run_arguments(in, st, params, local, out, c, R, consts)) return rc;
-  if (sum && (!sum->summary || sum->first_row < 0 || sum->last_row < sum->first_row || sum->last_row >= R.n_out))
-    return fail_msg("rs_driver_run_summary: summary is required, with 0 <= first_row <= last_row < n_out", -1);
-  if (int rc = check_groups(grp, R.n_out)) return rc;
-  if (int rc = check_episodes(epi, R.n_out)) return rc;
+  if (int rc = check_summary(q.summary, R.n_out)) return rc;
   if (int rc = check_device(device)) return rc;
   HOK(hipSetDevice(device));
   StreamGuard sg; /* the worker's one stream: uploads, kernels and downloads of its tiles (upload_tile) */
   HOK(hipStreamCreate(&sg.s));
   const hipStream_t stream = sg.s;
   Dev d_grp; /* this block's group cells, kept across its tiles (its own allocation: the arena is the tiles') */
+  const RsDriverGroups *grp = q.groups;
+  const RsDriverEpisodes *epi = q.episodes;
   const size_t grp_cells = grp ? (size_t)(grp->last_row - grp->first_row + 1) * grp->spec.ngroups : 0;
   const int grp_cols = grp ? rs_cluster_group_cols(&grp->spec) : 0;
   if (grp) {
@@ -2336,7 +2338,7 @@ int driver_run_range(const RsDriverInput *in, const InputSettings *st, const Inp
     HOK(rs_cluster_group_reset(d_grp.as<double>(), grp->last_row - grp->first_row + 1, grp->spec, stream));
   }
   make_run_policy(st, consts, c, local, pbeg, pend, R);
-  R.kept = kept != nullptr;
+  R.kept = q.kept != nullptr;
   R.epi_cols = epi ? rs_cluster_episode_cols(&epi->spec) : 0;
   R.epi_deficit = epi && (((epi->spec.use >> 6) & 1) || epi->spec.peak == 6);
   const Call call{in, st, c, consts, device, stream, local, out->status, out->missing_index};
@@ -2365,7 +2367,7 @@ int driver_run_range(const RsDriverInput *in, const InputSettings *st, const Inp
   const int rows0 = R.cpl_chunked ? std::max(R.TC, std::min(c.L, c.cplLen + 2)) : R.TC;
   Run run{call, params, out, R, pbeg, pend,
           rs_bottom_temperature(params, &consts, in->year[0], in->month[0], in->day[0]), ax, pt, win,
-          R.use_raw ? 0 : (size_t)R.nwin * Ppad * rows0 * sizeof(double), sum, grp, d_grp.as<double>(), kept, epi};
+          R.use_raw ? 0 : (size_t)R.nwin * Ppad * rows0 * sizeof(double), q, d_grp.as<double>()};
   if (run.win_bytes) HOK(win.acquire(run.win_bytes, device));
   pt.lap(6);
 
@@ -2471,30 +2473,19 @@ int driver_expand(const RsDriverInput *in, const RsGridSource *const *grids, con
   return 0;
 }
 
-/* rs_driver_run and its kin: one device, or the fan-out */
-int driver_run(const RsDriverInput *in, const RsGridSource *const *grids, const InputSettings *st,
-               const InputParameters *params, LocalParameters *local, const RsDriverOutput *out,
-               const RsDriverSummary *sum, const RsDriverGroups *grp, const RsDriverKept *kept,
-               const RsDriverEpisodes *epi, int32_t device) {
+/* rs_driver_run_request and the older entries: one device, or the fan-out.  `q` is the call's own copy of the request:
+ * check_request normalises it (kept with nothing wanted becomes NULL), and the workers read nothing else. */
+int driver_run(const RsDriverInput *in, const InputSettings *st, const InputParameters *params, LocalParameters *local,
+               const RsDriverOutput *out, RsDriverRequest q, int32_t device) {
   if (!in || in->n_points < 1) return fail_msg("rs_driver_run: bad arguments", -1);
-  if (epi) {
-    if (!out) return fail_msg("rs_driver_run: bad arguments", -1);
-    if (int rc = check_episodes(epi, out->n_out)) return rc;
-  }
-  if (kept) { /* nothing wanted: as without */
-    bool any = kept->deficit != nullptr;
-    for (int f = 0; f < NFLD; ++f) any = any || kept->merged[f];
-    if (!any) kept = nullptr;
-  }
-  if (grp) {
-    if (!out) return fail_msg("rs_driver_run: bad arguments", -1);
-    if (int rc = check_groups(grp, out->n_out)) return rc;
+  if (int rc = check_request(q, out)) return rc;
+  if (const RsDriverGroups *grp = q.groups) { /* the empty cells: what merge_group_cells starts from */
     const int cols = rs_cluster_group_cols(&grp->spec);
     const size_t ncells = (size_t)(grp->last_row - grp->first_row + 1) * grp->spec.ngroups;
-    for (size_t i = 0; i < ncells; ++i) /* the empty cell: what merge_group_cells starts from */
-      for (int c = 0; c < cols; ++c)
-        grp->series[i * cols + c] = c == 1 ? HUGE_VAL : (c == 2 || (c >= 9 && c < RS_GRP_COLS)) ? -HUGE_VAL : 0.0;
+    for (size_t i = 0; i < ncells; ++i)
+      for (int c = 0; c < cols; ++c) grp->series[i * cols + c] = rs_grp::empty(c);
   }
+  const RsGridSource *const *grids = q.grids;
   const bool gridded = any_grid(in, grids);
   if (gridded)
     if (int rc = check_grids(in, grids)) return rc;
@@ -2506,8 +2497,7 @@ int driver_run(const RsDriverInput *in, const RsGridSource *const *grids, const 
       gv.dev = G.find(device);
     }
     rsu::g_last_fanout = 1;
-    return driver_run_range(in, st, params, local, out, sum, grp, kept, epi, device, 0, in->n_points,
-                            gridded ? &gv : nullptr);
+    return driver_run_range(in, st, params, local, out, q, device, 0, in->n_points, gridded ? &gv : nullptr);
   }
   /* four blocks per device.  (Six for batches with local horizons were 4 % faster while the horizon table
    * was transposed on the device, tools/experiments/r4_blocks.sh; with the table left in the caller's layout
@@ -2525,8 +2515,7 @@ int driver_run(const RsDriverInput *in, const RsGridSource *const *grids, const 
   }
   return rsu::fan_out(shards, [&](const rsu::Shard &sh, int) {
     const GridView v{grids, G.find(sh.device)};
-    return driver_run_range(in, st, params, local, out, sum, grp, kept, epi, sh.device, sh.off, sh.off + sh.cnt,
-                            gridded ? &v : nullptr);
+    return driver_run_range(in, st, params, local, out, q, sh.device, sh.off, sh.off + sh.cnt, gridded ? &v : nullptr);
   });
 }
 
@@ -2565,52 +2554,52 @@ int rs_driver_last_raw_launches(void) { return g_last_raw_launches; }
 /* device >= 0: that device.  device < 0: the points are cut into contiguous blocks over the
  * device list (rs_devices.hpp: ROADSURF_HIP_DEVICES, default every visible device), one host
  * thread + stream + plans per device, no collective - the in-process counterpart of the
- * reference driver's worker pool (examples/example1/src/roadrunner.cpp:423-501). */
-int rs_driver_run(const RsDriverInput *in, const InputSettings *st, const InputParameters *params,
-                  LocalParameters *local, const RsDriverOutput *out, int32_t device) {
-  return rs_driver_run_summary(in, st, params, local, out, nullptr, device);
+ * reference driver's worker pool (examples/example1/src/roadrunner.cpp:423-501).  What a request adds to it:
+ *   summary   every block fills its points' rows of the one host array
+ *   groups    every block reduces its points into cells of its own on its device, and merges them into the caller's
+ *             array when its last tile is home
+ *   grids     the calling thread checks them and puts their fields on every device of the call before the blocks start
+ *   kept      every tile makes them from its raw columns behind its time loop, every block fills its points' rows of the
+ *             host arrays
+ *   episodes  every tile feeds its result block's rows - and the deficit, where the spec uses it - to its points'
+ *             automata, every block fills its points' rows of the one host array */
+int rs_driver_run_request(const RsDriverInput *in, const InputSettings *st, const InputParameters *params,
+                          LocalParameters *local, const RsDriverOutput *out, const RsDriverRequest *request,
+                          int32_t device) {
+  return driver_run(in, st, params, local, out, request ? *request : RsDriverRequest{}, device);
 }
 
-/* ... and with the summaries of the kept rows beside (or instead of) the series: every block fills its points' rows
- * of the one host array */
+/* the older entries: the request each of them can express */
+int rs_driver_run(const RsDriverInput *in, const InputSettings *st, const InputParameters *params,
+                  LocalParameters *local, const RsDriverOutput *out, int32_t device) {
+  return driver_run(in, st, params, local, out, RsDriverRequest{}, device);
+}
 int rs_driver_run_summary(const RsDriverInput *in, const InputSettings *st, const InputParameters *params,
                           LocalParameters *local, const RsDriverOutput *out, const RsDriverSummary *sum,
                           int32_t device) {
-  return rs_driver_run_groups(in, st, params, local, out, sum, nullptr, device);
+  return driver_run(in, st, params, local, out, RsDriverRequest{nullptr, sum}, device);
 }
-
-/* ... and with the group series of the kept rows: every block reduces its points into cells of its own on its device,
- * and merges them into the caller's array when its last tile is home */
 int rs_driver_run_groups(const RsDriverInput *in, const InputSettings *st, const InputParameters *params,
                          LocalParameters *local, const RsDriverOutput *out, const RsDriverSummary *sum,
                          const RsDriverGroups *grp, int32_t device) {
-  return rs_driver_run_grid(in, nullptr, st, params, local, out, sum, grp, device);
+  return driver_run(in, st, params, local, out, RsDriverRequest{nullptr, sum, grp}, device);
 }
-
-/* ... and with sources that arrive as fields: the calling thread checks them and puts their fields on every device of
- * the call before the blocks start */
 int rs_driver_run_grid(const RsDriverInput *in, const RsGridSource *const *grids, const InputSettings *st,
                        const InputParameters *params, LocalParameters *local, const RsDriverOutput *out,
                        const RsDriverSummary *sum, const RsDriverGroups *grp, int32_t device) {
-  return rs_driver_run_kept(in, grids, st, params, local, out, sum, grp, nullptr, device);
+  return driver_run(in, st, params, local, out, RsDriverRequest{grids, sum, grp}, device);
 }
-
-/* ... and with the inputs the model saw at the kept rows and the dew-point deficit: every tile makes them from its raw
- * columns behind its time loop, every block fills its points' rows of the host arrays */
 int32_t rs_driver_kept_fields(void) { return NFLD; }
 int rs_driver_run_kept(const RsDriverInput *in, const RsGridSource *const *grids, const InputSettings *st,
                        const InputParameters *params, LocalParameters *local, const RsDriverOutput *out,
                        const RsDriverSummary *sum, const RsDriverGroups *grp, const RsDriverKept *kept, int32_t device) {
-  return rs_driver_run_episodes(in, grids, st, params, local, out, sum, grp, kept, nullptr, device);
+  return driver_run(in, st, params, local, out, RsDriverRequest{grids, sum, grp, kept}, device);
 }
-
-/* ... and with the threshold episodes of the kept rows: every tile feeds its result block's rows - and the deficit,
- * where the spec uses it - to its points' automata, every block fills its points' rows of the one host array */
 int rs_driver_run_episodes(const RsDriverInput *in, const RsGridSource *const *grids, const InputSettings *st,
                            const InputParameters *params, LocalParameters *local, const RsDriverOutput *out,
                            const RsDriverSummary *sum, const RsDriverGroups *grp, const RsDriverKept *kept,
                            const RsDriverEpisodes *epi, int32_t device) {
-  return driver_run(in, grids, st, params, local, out, sum, grp, kept, epi, device);
+  return driver_run(in, st, params, local, out, RsDriverRequest{grids, sum, grp, kept, epi}, device);
 }
 
 } /* extern "C" */

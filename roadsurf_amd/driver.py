@@ -83,6 +83,12 @@ class RsDriverEpisodes(C.Structure):
                 ("episodes", abi.c_double_p)]
 
 
+class RsDriverRequest(C.Structure):
+    _fields_ = [("grids", C.POINTER(C.POINTER(RsGridSource))), ("summary", C.POINTER(RsDriverSummary)),
+                ("groups", C.POINTER(RsDriverGroups)), ("kept", C.POINTER(RsDriverKept)),
+                ("episodes", C.POINTER(RsDriverEpisodes))]
+
+
 @dataclasses.dataclass
 class RawSource:
     """One data source: ``fields`` name -> [n_points][n_times] float64 (absent name = variable
@@ -189,7 +195,7 @@ def make_input(sources, start_time: int, forecast_time: int, cal: dict | None = 
 def make_grid_input(sources, start_time: int, forecast_time: int, cal: dict | None = None,
                     horizons: np.ndarray | None = None):
     """``make_input`` for a list that may hold ``grid.GridSource`` entries among the ``RawSource`` ones.  Returns
-    (RsDriverInput, grids, keepalive list): ``grids`` is the ``RsGridSource *[n_sources]`` rs_driver_run_grid takes
+    (RsDriverInput, grids, keepalive list): ``grids`` is the ``RsGridSource *[n_sources]`` of RsDriverRequest::grids
     (NULL entry = per-point source), or None when no source is gridded.  A gridded source's RsRawSource carries
     its time axis and is_observation only."""
     gridded = [isinstance(s, rsgrid.GridSource) for s in sources]
@@ -238,40 +244,29 @@ def _locals(n: int, local) -> C.Array:
 
 
 def _bind(L):
+    """Argument types of the driver's entries: rs_driver_run_request, and the older entries (the tests call them), each
+    of which is the run's five arguments, the members of RsDriverRequest it can express - the grids in front - and the
+    device."""
     P = C.POINTER
-    L.rs_driver_run.argtypes = [P(RsDriverInput), P(abi.InputSettings), P(abi.InputParameters),
-                                P(abi.LocalParameters), P(RsDriverOutput), C.c_int32]
-    if hasattr(L, "rs_driver_run_summary"):
-        L.rs_driver_run_summary.argtypes = [P(RsDriverInput), P(abi.InputSettings), P(abi.InputParameters),
-                                            P(abi.LocalParameters), P(RsDriverOutput), P(RsDriverSummary), C.c_int32]
-    if hasattr(L, "rs_driver_run_groups"):
-        L.rs_driver_run_groups.argtypes = [P(RsDriverInput), P(abi.InputSettings), P(abi.InputParameters),
-                                           P(abi.LocalParameters), P(RsDriverOutput), P(RsDriverSummary),
-                                           P(RsDriverGroups), C.c_int32]
-    L.rs_driver_expand.argtypes = [P(RsDriverInput), P(abi.InputSettings), P(abi.LocalParameters),
-                                   abi.c_double_p, abi.c_int32_p, abi.c_int32_p, C.c_int32]
-    if hasattr(L, "rs_driver_run_grid"):
-        L.rs_driver_run_grid.argtypes = [P(RsDriverInput), P(P(RsGridSource)), P(abi.InputSettings),
-                                         P(abi.InputParameters), P(abi.LocalParameters), P(RsDriverOutput),
-                                         P(RsDriverSummary), P(RsDriverGroups), C.c_int32]
-        L.rs_driver_expand_grid.argtypes = [P(RsDriverInput), P(P(RsGridSource)), P(abi.InputSettings),
-                                            P(abi.LocalParameters), abi.c_double_p, abi.c_int32_p, abi.c_int32_p,
-                                            C.c_int32]
-    if hasattr(L, "rs_driver_kept_fields"):
-        L.rs_driver_kept_fields.restype = C.c_int32
-        L.rs_driver_run_kept.argtypes = [P(RsDriverInput), P(P(RsGridSource)), P(abi.InputSettings),
-                                         P(abi.InputParameters), P(abi.LocalParameters), P(RsDriverOutput),
-                                         P(RsDriverSummary), P(RsDriverGroups), P(RsDriverKept), C.c_int32]
-    if hasattr(L, "rs_driver_run_episodes"):
-        L.rs_driver_run_episodes.argtypes = [P(RsDriverInput), P(P(RsGridSource)), P(abi.InputSettings),
-                                             P(abi.InputParameters), P(abi.LocalParameters), P(RsDriverOutput),
-                                             P(RsDriverSummary), P(RsDriverGroups), P(RsDriverKept),
-                                             P(RsDriverEpisodes), C.c_int32]
+    if not hasattr(L, "rs_driver_run_request"):
+        raise RuntimeError("this libroadsurf_hip.so has no request form of the driver (rs_driver_run_request)")
+    run = [P(RsDriverInput), P(abi.InputSettings), P(abi.InputParameters), P(abi.LocalParameters), P(RsDriverOutput)]
+    grids, s, g, k, e = P(P(RsGridSource)), P(RsDriverSummary), P(RsDriverGroups), P(RsDriverKept), P(RsDriverEpisodes)
+    L.rs_driver_run_request.argtypes = run + [P(RsDriverRequest), C.c_int32]
+    for name, front, members in (("rs_driver_run", [], []), ("rs_driver_run_summary", [], [s]),
+                                 ("rs_driver_run_groups", [], [s, g]), ("rs_driver_run_grid", [grids], [s, g]),
+                                 ("rs_driver_run_kept", [grids], [s, g, k]),
+                                 ("rs_driver_run_episodes", [grids], [s, g, k, e])):
+        getattr(L, name).argtypes = run[:1] + front + run[1:] + members + [C.c_int32]
+    expand = [P(abi.InputSettings), P(abi.LocalParameters), abi.c_double_p, abi.c_int32_p, abi.c_int32_p, C.c_int32]
+    L.rs_driver_expand.argtypes = run[:1] + expand
+    L.rs_driver_expand_grid.argtypes = run[:1] + [grids] + expand
+    L.rs_driver_kept_fields.restype = C.c_int32
     return L
 
 
 def _need_grids(L) -> None:
-    if not hasattr(L, "rs_driver_run_grid") or L.rs_hip_grid_max_stencil() != rsgrid.MAX_STENCIL:
+    if L.rs_hip_grid_max_stencil() != rsgrid.MAX_STENCIL:
         raise RuntimeError("this libroadsurf_hip.so has no gridded sources (rs_hip_grid_max_stencil)")
 
 
@@ -310,7 +305,8 @@ def run(sources, settings: abi.InputSettings, params: abi.InputParameters, start
         groups=None, group_of=None, group_rows: tuple[int, int] | None = None,
         kept=(), deficit: bool = False, episodes=None, episode_rows: tuple[int, int] | None = None) -> dict:
     """read_input + runsimulation + save_output's decimation for all points.  Returns the six
-    outputs as [n][n_out] arrays plus ``status``, ``missing_index``, ``local`` and ``step``.
+    outputs as [n][n_out] arrays plus ``status``, ``missing_index``, ``local`` and ``step``.  One call of
+    rs_driver_run_request, whatever is asked for: the entries named below are the older ones that take the same member.
     ``device`` < 0 fans the points out over ROADSURF_HIP_DEVICES; ``out`` = a result dict of an
     earlier call with the same shapes, whose arrays are written again (no fresh allocation; its ``kept`` and
     ``deficit`` arrays too).
@@ -341,7 +337,7 @@ def run(sources, settings: abi.InputSettings, params: abi.InputParameters, start
         if name not in MERGED_FIELDS:
             raise KeyError(name)
     want_kept = bool(kept) or bool(deficit)
-    if want_kept and (not hasattr(L, "rs_driver_kept_fields") or L.rs_driver_kept_fields() != len(MERGED_FIELDS)):
+    if want_kept and L.rs_driver_kept_fields() != len(MERGED_FIELDS):
         raise RuntimeError("this libroadsurf_hip.so has no kept input rows (rs_driver_kept_fields)")
     if cal is None:
         cal = calendar(start_time, settings.SimLen, int(settings.DTSecs))
@@ -371,32 +367,27 @@ def run(sources, settings: abi.InputSettings, params: abi.InputParameters, start
             setattr(out, k, res[k].ctypes.data_as(abi.c_double_p))
     out.status = res["status"].ctypes.data_as(abi.c_int32_p)
     out.missing_index = res["missing_index"].ctypes.data_as(abi.c_int32_p)
-    q = g = None
+    req = RsDriverRequest(grids=grids)  # (its members keep what they point to alive)
     if summary is not None:
-        if not hasattr(L, "rs_driver_run_summary") or L.rs_hip_summary_cols() != rslib.RS_SUM_COLS:
+        if L.rs_hip_summary_cols() != rslib.RS_SUM_COLS:
             raise RuntimeError("this libroadsurf_hip.so has no summaries (rs_hip_summary_cols)")
         first, last = (0, n_out - 1) if summary_rows is None else summary_rows
         res["summary"] = np.full((n, rslib.RS_SUM_COLS), np.nan)
-        q = RsDriverSummary(rslib.summary_spec(summary), int(first), int(last),
-                            res["summary"].ctypes.data_as(abi.c_double_p))
+        req.summary = C.pointer(RsDriverSummary(rslib.summary_spec(summary), int(first), int(last),
+                                                res["summary"].ctypes.data_as(abi.c_double_p)))
     if groups is not None:
-        if not hasattr(L, "rs_driver_run_groups"):
-            raise RuntimeError("this libroadsurf_hip.so has no group series (rs_driver_run_groups)")
         gfirst, glast = (0, n_out - 1) if group_rows is None else (int(group_rows[0]), int(group_rows[1]))
         gid = np.ascontiguousarray(group_of, dtype=np.int32)
         if gid.shape != (n,):
             raise ValueError("group_of: one group id per point")
         res["groups"] = np.full((max(glast - gfirst + 1, 1), int(groups.ngroups), rslib.group_cols(groups)), np.nan)
-        g = RsDriverGroups(rslib.group_spec(groups), gid.ctypes.data_as(abi.c_int32_p), gfirst, glast,
-                           res["groups"].ctypes.data_as(abi.c_double_p))
-    kq = e = None
+        req.groups = C.pointer(RsDriverGroups(rslib.group_spec(groups), gid.ctypes.data_as(abi.c_int32_p), gfirst, glast,
+                                              res["groups"].ctypes.data_as(abi.c_double_p)))
     if episodes is not None:
-        if not hasattr(L, "rs_driver_run_episodes"):
-            raise RuntimeError("this libroadsurf_hip.so has no threshold episodes (rs_driver_run_episodes)")
         efirst, elast = forecast_rows(settings, start_time, forecast_time) if episode_rows is None else episode_rows
         res["episodes"] = np.full((n, rslib.episode_cols(episodes)), np.nan)
-        e = RsDriverEpisodes(rslib.episode_spec(episodes), int(efirst), int(elast),
-                             res["episodes"].ctypes.data_as(abi.c_double_p))
+        req.episodes = C.pointer(RsDriverEpisodes(rslib.episode_spec(episodes), int(efirst), int(elast),
+                                                  res["episodes"].ctypes.data_as(abi.c_double_p)))
     if want_kept:
         kq = RsDriverKept()
         res["kept"] = {name: rows(earlier.get("kept", {}).get(name)) for name in kept}
@@ -405,30 +396,9 @@ def run(sources, settings: abi.InputSettings, params: abi.InputParameters, start
         if deficit:
             res["deficit"] = rows(earlier.get("deficit"))
             kq.deficit = res["deficit"].ctypes.data_as(abi.c_double_p)
-    if e is not None:
-        rslib.check(L.rs_driver_run_episodes(C.byref(inp), grids, C.byref(settings), C.byref(params), larr, C.byref(out),
-                                             C.byref(q) if q is not None else None,
-                                             C.byref(g) if g is not None else None,
-                                             C.byref(kq) if kq is not None else None, C.byref(e), device),
-                    "rs_driver_run_episodes")
-    elif want_kept:
-        rslib.check(L.rs_driver_run_kept(C.byref(inp), grids, C.byref(settings), C.byref(params), larr, C.byref(out),
-                                         C.byref(q) if q is not None else None,
-                                         C.byref(g) if g is not None else None, C.byref(kq), device), "rs_driver_run_kept")
-    elif grids is not None:
-        rslib.check(L.rs_driver_run_grid(C.byref(inp), grids, C.byref(settings), C.byref(params), larr, C.byref(out),
-                                         C.byref(q) if q is not None else None,
-                                         C.byref(g) if g is not None else None, device), "rs_driver_run_grid")
-    elif groups is not None:
-        rslib.check(L.rs_driver_run_groups(C.byref(inp), C.byref(settings), C.byref(params), larr, C.byref(out),
-                                           C.byref(q) if q is not None else None, C.byref(g), device),
-                    "rs_driver_run_groups")
-    elif summary is None:
-        rslib.check(L.rs_driver_run(C.byref(inp), C.byref(settings), C.byref(params), larr,
-                                    C.byref(out), device), "rs_driver_run")
-    else:
-        rslib.check(L.rs_driver_run_summary(C.byref(inp), C.byref(settings), C.byref(params), larr,
-                                            C.byref(out), C.byref(q), device), "rs_driver_run_summary")
+        req.kept = C.pointer(kq)
+    rslib.check(L.rs_driver_run_request(C.byref(inp), C.byref(settings), C.byref(params), larr, C.byref(out),
+                                        C.byref(req), device), "rs_driver_run_request")
     del keep
     res["local"] = larr
     res["step"] = step

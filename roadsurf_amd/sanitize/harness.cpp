@@ -6,7 +6,8 @@
 //            limited to ROADSURF_HIP_COALESCE_MAX callers per batch (set by the test: 5 < threads)
 //   phase 2  threads that come and go (thread-local caches adopted by later threads, rs_host.hip CallerCache)
 //   phase 3  four concurrent runsimulation_batch calls of different sizes (arena / plan bookkeeping)
-//   phase 4  rs_driver_run_episodes, which rs_driver_run and its kin are calls of, with and without the summaries from
+//   phase 4  rs_driver_run_episodes, the older entry that fills every member of an RsDriverRequest (rs_driver_run and
+//            its kin are wrappers of the same run with fewer members set), with and without the summaries from
 //            three threads (shards, segment table, per-block worker threads, the blocks' merge into the one array of
 //            group series, the blocks' rows of the kept inputs, the deficit and the threshold episodes)
 //   phase 5  the device API's answers to its arguments, single-threaded and independent of the two arguments below:

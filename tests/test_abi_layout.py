@@ -56,12 +56,22 @@ def test_c_fortran_ctypes_sizes_agree(hip_lib):
 
 def test_device_api_structs_have_the_size_the_binding_assumes(hip_lib):
     """The ctypes mirrors of the device-resident API's structs (roadsurf_amd/lib.py) against sizeof in the
-    library: a field added on one side only (RsPointParams grew twice in round 4) shows here, without a GPU."""
+    library: a field added on one side only (RsPointParams grew twice in round 4) shows here, without a GPU.  Every
+    struct of the driver's boundary (roadsurf_amd/driver.py) is among them."""
     from roadsurf_amd import driver
     py = [lib.RsForcing, lib.RsOutputs, lib.RsPointParams, lib.RsHostExtras, lib.RsPreview, lib.RsSynthSpec,
-          driver.RsRawSource, driver.RsDriverInput, driver.RsDriverOutput]
+          driver.RsRawSource, driver.RsDriverInput, driver.RsDriverOutput,
+          lib.RsSummarySpec, driver.RsDriverSummary, lib.RsGroupSpec, driver.RsDriverGroups,
+          lib.RsEpisodeSpec, driver.RsGridSource, driver.RsDriverKept, driver.RsDriverEpisodes, driver.RsDriverRequest]
     for i, cls in enumerate(py, start=6):
         assert hip_lib.rs_abi_sizeof(i) == C.sizeof(cls), cls.__name__
+    assert hip_lib.rs_abi_sizeof(6 + len(py)) == -1  # (no index of the library goes unasserted)
+
+
+def test_driver_request_is_five_pointers():
+    from roadsurf_amd import driver
+    assert _offsets(driver.RsDriverRequest) == dict(grids=0, summary=8, groups=16, kept=24, episodes=32)
+    assert C.sizeof(driver.RsDriverRequest) == 40
 
 
 def test_defaults_match_reference_headers(hip_lib):

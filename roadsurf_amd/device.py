@@ -599,154 +599,27 @@ def run_points(forcing: dict, settings: abi.InputSettings, params: abi.InputPara
     ``episodes``: an episodes.EpisodeSpec that does not need the deficit - every launch's rows are also fed to the
     per-point episodes (``Plan.outputs_episodes``) and the result has ``episodes`` [n, cols], finished; not with
     coupling either."""
-    import numpy as np
+    from . import legs  # (legs imports this module when a Leg is made)
 
     require_gpu()
     n, L = forcing["tair"].shape
     assert L == settings.SimLen
-    dev = torch.device("cuda", device)
-    plan = Plan(n, settings, params, device)
-    if variant:
-        plan.set_variant(variant)
-    if history_score is not None:
-        plan.set_history_score(history_score)
-    if precision == 32:  # the fp32 flavour: windows and outputs hold floats (rs_hip_set_precision)
-        plan.set_precision(32)
-    wdt = torch.float32 if precision == 32 else torch.float64
-    npad = plan.np_pad
     if isinstance(local, abi.LocalParameters):
         local = [local] * n
-    initlen = np.array([l.InitLenI for l in local], np.int32)
-    relax_on = settings.use_relaxation == 1
     coupled = settings.use_coupling == 1
-    skyv = np.array([l.sky_view for l in local])
-    sky_on = bool(((skyv < 1.0) & (skyv > -0.01)).any())
-    need_full = (not lean_if_possible) or initlen.max() > 1 or settings.force_tsurf == 1 or \
-        relax_on or coupled or sky_on or settings.tsurfOutputDepth >= 0 or (forcing["depth"] >= 0).any() \
-        or bool(((forcing["tdew"] < -90.0) | (forcing["tdew"] > 100.0)).any())  # the LEAN kernels skip the Tdew check
-
-    def pad_t(a, dtype):  # [n, L] -> device [L, npad]
-        t = torch.zeros((L, npad), dtype=dtype, device=dev)
-        t[:, :n] = torch.from_numpy(np.ascontiguousarray(a)).to(dev).T
-        return t
-
-    tens = {k: pad_t(forcing[k], wdt) for k in ("tair", "vz", "rhz", "prec", "sw", "lw")}
-    tens["tsurfobs"] = pad_t(forcing["tsurfobs"], wdt)
-    tens["tdew"] = pad_t(forcing["tdew"], wdt) if need_full else None
-    # no depth stream where no value of it can act (depth(i) >= 0 takes the surface temperature from the
-    # profile at that depth): the kernels read a missing stream as -9999.9, and the two-wavefront flavour
-    # has the FULL feature set only without one
-    tens["depth"] = pad_t(forcing["depth"], wdt) if need_full and bool((forcing["depth"] >= 0).any()) else None
-    tens["precphase"] = pad_t(forcing["precphase"], torch.int32)
-    tens["hour"] = torch.from_numpy(np.ascontiguousarray(forcing["hour"])).to(dev)
-    sky = None
-    if sky_on:
-        Lh = lib.load()
-        tens["sw_dir"] = pad_t(forcing["sw_dir"], wdt)  # (window streams: the plan's precision; the geometry stays fp64)
-        tens["lw_net"] = pad_t(forcing["lw_net"], wdt)
-        sun = np.zeros((L, 6))  # RS_SUN_COLS
-        ax = [np.ascontiguousarray(forcing[k], np.int32) for k in ("year", "month", "day", "hour", "minute", "second")]
-        Lh.rs_sun_table(L, *[C.c_void_p(a.ctypes.data) for a in ax], C.c_void_p(sun.ctypes.data))
-        tens["sun"] = torch.from_numpy(sun).to(dev)
-        larr = (abi.LocalParameters * n)(*local)
-        geo = [np.zeros(n) for _ in range(3)]
-        Lh.rs_point_geometry(n, larr, *[C.c_void_p(g.ctypes.data) for g in geo])
-
-        def vec(a):
-            t = torch.zeros((npad,), dtype=torch.float64, device=dev)
-            t[:n] = torch.from_numpy(np.ascontiguousarray(a))
-            return t
-        sky = {"sky_view": vec(skyv), "sin_lat": vec(geo[0]), "cos_lat": vec(geo[1]), "lon_rad": vec(geo[2])}
-        hz = forcing.get("local_horizons")
-        if hz is not None:
-            h = torch.zeros((360, npad), dtype=torch.float64, device=dev)
-            h[:, :n] = torch.from_numpy(np.ascontiguousarray(hz)).to(dev).T
-            sky["horizons"] = h
-            if horizon_index is not None:  # point i of this call reads column horizon_index[i] of local_horizons
-                hi = torch.zeros((npad,), dtype=torch.int32, device=dev)
-                hi[:n] = torch.from_numpy(np.ascontiguousarray(horizon_index, np.int32))
-                sky["horizon_index"] = hi
-    win = ForcingWindow(L, npad, tens)
+    for name, spec in (("summary", summary), ("groups", groups), ("episodes", episodes)):
+        if spec is not None and coupled:  # (the reducers are for the launches of an uncoupled run)
+            raise ValueError(f"run_points: no {name} with coupling")
     if year_month_day is None:
         year_month_day = (int(forcing["year"][0]), int(forcing["month"][0]), int(forcing["day"][0]))
-    tb = plan.uniform_tbottom(*year_month_day)
-
-    def pp_vec(vals, dtype):
-        t = torch.zeros((npad,), dtype=dtype, device=dev)
-        t[:n] = torch.tensor(vals, dtype=dtype)
-        return t
-
-    if need_full:
-        pp = plan.point_params(
-            tb, pp_vec(initlen.tolist(), torch.int32),
-            pp_vec([l.tair_relax for l in local], torch.float64) if relax_on else None,
-            pp_vec([l.VZ_relax for l in local], torch.float64) if relax_on else None,
-            pp_vec([l.RH_relax for l in local], torch.float64) if relax_on else None,
-            pp_vec([l.couplingIndexI for l in local], torch.int32) if coupled else None,
-            pp_vec([l.couplingTsurf for l in local], torch.float64) if coupled else None,
-            sky)
-    else:
-        pp = plan.point_params(tb)
-    out = OutputWindow.empty(L, npad, dev, dtype=wdt)
-    if summary is not None and coupled:
-        raise ValueError("run_points: no summary with coupling")
-    acc = plan.summary_reset() if summary is not None else None
-    if groups is not None and coupled:
-        raise ValueError("run_points: no groups with coupling")
-    gacc = gid = None
-    if groups is not None:
-        gid = torch.from_numpy(np.ascontiguousarray(groups[1], dtype=np.int32)).to(dev)
-        assert gid.shape == (n,)
-        gacc = plan.groups_reset(L, groups[0])
-    if episodes is not None and coupled:
-        raise ValueError("run_points: no episodes with coupling")
-    eacc = plan.episodes_reset(episodes) if episodes is not None else None
-    plan.init_state(win, pp)
-    if coupled and chunk:
-        # time-chunked coupling: lock-step chunks up to the last coupling-window end, the replay
-        # rounds over the window block, then the chunks from the first window end on (points whose
-        # window ends later wait there; include/roadsurf.h, rs_hip_step_cpl)
-        ci = np.array([l.couplingIndexI for l in local]); ct = np.array([l.couplingTsurf for l in local])
-        on = ~((ct < -100) | (ci < 1))
-        cpl_len = int(settings.coupling_minutes * 60 / settings.DTSecs)
-        cs = np.where(ci <= settings.coupling_minutes * 60 / settings.DTSecs, 1, ci - cpl_len)
-        stages = [(1, L)]
-        if on.any():
-            ce_max, ce_min, cs_min = int(ci[on].max()), int(ci[on].min()), int(cs[on].min())
-            # the replay window reaches one index beyond the last window end: a point that replays
-            # has CheckValues run on index couplingEndI+1 before it rewinds (Simulation.f90:59-66)
-            stages = [(1, min(ce_max, L)), ("replay", cs_min, min(ce_max + 1, L)), (ce_min + 1, L)]
-        for st in stages:
-            if st[0] == "replay":
-                plan.cpl_replay(win, out, pp, st[1], st[2] - st[1] + 1, window_row=st[1] - 1, out_row0=0)
-                continue
-            t0 = st[0]
-            while t0 <= st[1]:
-                ns = min(chunk, st[1] - t0 + 1)
-                plan.step_cpl(win, out, pp, t0, ns, window_row=t0 - 1, out_row0=0)
-                t0 += ns
-    else:
-        chunk = L if coupled else (chunk or L)
-        t0 = 1
-        while t0 <= L:
-            ns = min(chunk, L - t0 + 1)
-            plan.step(win, out, pp, t0, ns, window_row=t0 - 1, out_row0=0)
-            if acc is not None:  # the rows this launch wrote: time indices t0 ... t0 + ns - 1
-                plan.outputs_summary(out, ns, t0, 1, summary, acc, row=t0 - 1)
-            if gacc is not None:
-                plan.outputs_groups(out, ns, gid, groups[0], gacc, t0 - 1, row=t0 - 1)
-            if eacc is not None:
-                plan.outputs_episodes(out, ns, t0, 1, episodes, eacc, row=t0 - 1)
-            t0 += ns
-    plan.sync()
-    res = {k: out.tensors[k][:, :n].T.contiguous().double().cpu().numpy() for k in OUT_FIELDS}
-    if acc is not None:
-        res["summary"] = plan.summary(acc)
-    if gacc is not None:
-        res["groups"] = plan.groups(gacc, groups[0])
-    if eacc is not None:
-        plan.episodes_finish(episodes, eacc)
-        res["episodes"] = plan.episodes(eacc)
-    nfail = plan.failed_count()
-    plan.close()
+    need_full, sky_on = legs.feature_set(settings, local, [forcing], lean_if_possible)
+    leg = legs.Leg(forcing, settings, params, local, need_full=need_full, sky_on=sky_on, tbottom_date=year_month_day,
+                   precision=precision, variant=variant, history_score=history_score, horizon_index=horizon_index,
+                   device=device, summary=summary, groups=groups, episodes=episodes)
+    leg.init()
+    leg.run(legs.coupling_stages(settings, local, L, chunked=bool(chunk)), chunk)
+    res = leg.results()
+    res.update(leg.reduced())
+    nfail = leg.plan.failed_count()
+    leg.plan.close()
     return res, nfail

@@ -21,8 +21,8 @@ from __future__ import annotations
 import numpy as np
 
 from . import abi
+from .legs import RELAX_FIELDS, Leg, coupling_stages, feature_set
 
-RELAX_FIELDS = ("tair_relax", "VZ_relax", "RH_relax")
 SHARED_FIELDS = ("InitLenI", "couplingIndexI", "couplingTsurf", "lat", "lon", "sky_view")
 
 
@@ -120,153 +120,6 @@ def check(S, L, B, settings, station_local, member_local, parent, precision=64, 
                                      "index behind InitLenI, so the analysis would not be shared")
 
 
-class _Leg:
-    """One plan and the rows of forcing it steps: row r of its windows is time index ``first + r``."""
-
-    def __init__(self, n, first, forcing, hour, settings, params, local, need_full, precision, variant, recluster,
-                 device, tbottom_date, groups=None, sky=None, stats=None):
-        import ctypes as C
-        import torch
-        from . import device as dv, lib
-        self.dv, self.torch = dv, torch
-        self.n, self.first, self.recluster = n, first, recluster
-        self.nrows = forcing["tair"].shape[1]
-        self.plan = plan = dv.Plan(n, settings, params, device)
-        if variant:
-            plan.set_variant(variant)
-        if precision == 32:
-            plan.set_precision(32)
-        self.wdt = wdt = torch.float32 if precision == 32 else torch.float64
-        self.dev = dev = plan.device
-        self.npad = npad = plan.np_pad
-        nrows = self.nrows
-
-        def pad_t(a, dtype):  # [n, nrows] -> device [nrows, npad]
-            t = torch.zeros((nrows, npad), dtype=dtype, device=dev)
-            t[:, :n] = torch.from_numpy(np.ascontiguousarray(a)).to(dev).T
-            return t
-
-        nat = {k: pad_t(forcing[k], wdt) for k in ("tair", "vz", "rhz", "prec", "sw", "lw", "tsurfobs")}
-        nat["tdew"] = pad_t(forcing["tdew"], wdt) if need_full else None
-        nat["depth"] = pad_t(forcing["depth"], wdt) if need_full and bool((forcing["depth"] >= 0).any()) else None
-        nat["precphase"] = pad_t(forcing["precphase"], torch.int32)
-        self.nat = nat
-        self.hour = torch.from_numpy(np.ascontiguousarray(hour, np.int32)).to(dev)
-
-        def pp_vec(vals, dtype):
-            t = torch.zeros((npad,), dtype=dtype, device=dev)
-            t[:n] = torch.tensor(vals, dtype=dtype)
-            return t
-
-        relax_on = settings.use_relaxation == 1
-        coupled = settings.use_coupling == 1
-        # (one tensor for every RsPointParams of the leg: Plan.point_params keeps only its latest arguments alive)
-        self.tb = torch.full((npad,), float(plan.uniform_tbottom(*tbottom_date)), dtype=torch.float64, device=dev)
-        self.pvec = None
-        if need_full:
-            self.pvec = [pp_vec([l.InitLenI for l in local], torch.int32)]
-            self.pvec += [pp_vec([getattr(l, k) for l in local], torch.float64) if relax_on else None
-                          for k in RELAX_FIELDS]
-            self.pvec += [pp_vec([l.couplingIndexI for l in local], torch.int32) if coupled else None,
-                          pp_vec([l.couplingTsurf for l in local], torch.float64) if coupled else None]
-        # sky view (sky: the leg's six time axes and the points' local horizons [n][360] or None): the two radiation
-        # streams in the plan's precision, the sun rows of the leg's indices, the points' geometry in fp64
-        self.sun = self.sky = None
-        if sky is not None:
-            Lh = lib.load()
-            nat["sw_dir"] = pad_t(forcing["sw_dir"], wdt)
-            nat["lw_net"] = pad_t(forcing["lw_net"], wdt)
-            sun = np.zeros((nrows, 6))  # RS_SUN_COLS
-            ax = [np.ascontiguousarray(sky["axes"][k], np.int32) for k in ("year", "month", "day", "hour", "minute", "second")]
-            assert all(a.shape == (nrows,) for a in ax)
-            Lh.rs_sun_table(nrows, *[C.c_void_p(a.ctypes.data) for a in ax], C.c_void_p(sun.ctypes.data))
-            self.sun = torch.from_numpy(sun).to(dev)
-            larr = (abi.LocalParameters * n)(*local)
-            geo = [np.zeros(n) for _ in range(3)]
-            Lh.rs_point_geometry(n, larr, *[C.c_void_p(g.ctypes.data) for g in geo])
-            self.sky = {"sky_view": pp_vec([l.sky_view for l in local], torch.float64)}
-            for k, g in zip(("sin_lat", "cos_lat", "lon_rad"), geo):
-                self.sky[k] = pp_vec(g.tolist(), torch.float64)
-            if sky.get("horizons") is not None:
-                h = torch.zeros((360, npad), dtype=torch.float64, device=dev)
-                h[:, :n] = torch.from_numpy(np.ascontiguousarray(sky["horizons"], np.float64)).to(dev).T
-                self.sky["horizons"] = h
-        self.out = dv.OutputWindow.empty(nrows, npad, dev, dtype=wdt)
-        if not recluster:
-            self.win = self._window(nat, self.hour, self.sun, nrows)
-            self.pp = self._pp(None)
-        self.gspec = self.gid = self.gacc = None
-        if groups is not None:
-            self.gspec = groups[0]
-            self.gid = torch.from_numpy(np.ascontiguousarray(groups[1], dtype=np.int32)).to(dev)
-            assert self.gid.shape == (n,)
-            self.gacc = plan.groups_reset(nrows, self.gspec)
-        self.espec = self.etab = self.eacc = None
-        if stats is not None:  # (stats: the spec and the station of every point; a cell is written, so no reset)
-            self.espec = stats[0]
-            self.etab = plan.ens_table(np.ascontiguousarray(stats[1], dtype=np.int32), self.espec)
-            self.eacc = torch.empty((nrows, int(self.espec.ngroups), lib.ens_cols(self.espec)), dtype=torch.float64,
-                                    device=dev)
-
-    def _window(self, tens, hour, sun, nrows):
-        tens = dict(tens, hour=hour)
-        if sun is not None:
-            tens["sun"] = sun
-        return self.dv.ForcingWindow(nrows, self.npad, tens)
-
-    def _pp(self, order):
-        if self.pvec is None:
-            return self.plan.point_params(self.tb)
-        vecs = self.pvec if order is None else [None if v is None else v.index_select(0, order) for v in self.pvec]
-        sky = self.sky
-        if sky is not None and order is not None:  # the vectors by slot; the horizons stay, slot s reads column order[s]
-            sky = {k: (v if k == "horizons" else v.index_select(0, order)) for k, v in self.sky.items()}
-            if "horizons" in sky:
-                sky["horizon_index"] = order.to(self.torch.int32)
-        return self.plan.point_params(self.tb, *vecs, sky)
-
-    def init(self):
-        # (before any re-sort: slot order is point order)
-        self.plan.init_state(self._window(self.nat, self.hour, self.sun, self.nrows), self._pp(None))
-
-    def launch(self, t0, ns, call="step"):
-        """Time indices [t0, t0 + ns) through Plan.step / step_cpl / cpl_replay; with ``recluster`` the window and the
-        per-point parameters go in the plan's current slot order, the rows come back through the kept order row, and
-        the plan is re-sorted behind the launch."""
-        dv, plan, r0 = self.dv, self.plan, t0 - self.first
-        assert 0 <= r0 and r0 + ns <= self.nrows
-        if self.recluster:
-            order = plan.order().clone().long()
-            tens = {k: (None if v is None else v[r0:r0 + ns].index_select(1, order)) for k, v in self.nat.items()}
-            win = self._window(tens, self.hour[r0:r0 + ns].contiguous(),
-                               None if self.sun is None else self.sun[r0:r0 + ns].contiguous(), ns)
-            wrow = 0
-            out, orow0, srow = dv.OutputWindow.empty(ns, self.npad, self.dev, dtype=self.wdt), t0 - 1, 0
-            pp = self._pp(order)
-        else:
-            win, wrow, out, orow0, srow, pp = self.win, r0, self.out, self.first - 1, r0, self.pp
-        getattr(plan, call)(win, out, pp, t0, ns, window_row=wrow, out_row0=orow0)
-        if self.gacc is not None and call != "cpl_replay":
-            plan.outputs_groups(out, ns, self.gid, self.gspec, self.gacc, r0, row=srow)
-        if self.eacc is not None and call != "cpl_replay":
-            plan.outputs_ens(out, ns, self.etab, self.espec, self.eacc, r0, row=srow)
-        if self.recluster:
-            for k in dv.OUT_FIELDS:
-                self.out.tensors[k][r0:r0 + ns].index_copy_(1, order, out.tensors[k])
-            plan.recluster()
-
-    def chunks(self, lo, hi, chunk, call="step"):
-        t0 = lo
-        while t0 <= hi:
-            ns = min(chunk or hi - lo + 1, hi - t0 + 1)
-            self.launch(t0, ns, call)
-            t0 += ns
-
-    def results(self):
-        self.plan.sync()
-        return {k: self.out.tensors[k][:, :self.n].T.contiguous().double().cpu().numpy() for k in self.dv.OUT_FIELDS}
-
-
 def run_ensemble(station_forcing: dict, member_tail: dict, B: int, settings: abi.InputSettings,
                  params: abi.InputParameters, station_local, member_local=None, parent=None, chunk: int = 0,
                  variant: int = 0, precision: int = 64, recluster: bool = False, groups=None, device: int = 0,
@@ -310,50 +163,25 @@ def run_ensemble(station_forcing: dict, member_tail: dict, B: int, settings: abi
     if station_forcing["tair"].shape[1] < B:
         raise ValueError(f"run_ensemble: the stations' forcing is shorter than B = {B}")
     ml = member_locals(sl, member_local, parent)
-    head = {k: np.asarray(v)[:, :B] for k, v in station_forcing.items()
-            if np.asarray(v).ndim == 2 and k != "local_horizons"}
+    # the stations' leg reads the first B columns and axis entries; a member has its station's horizons
+    head = {k: np.asarray(v)[..., :B] for k, v in station_forcing.items() if k != "local_horizons"}
+    tail = dict(member_tail)
+    hz = station_forcing.get("local_horizons")
+    if hz is not None:
+        head["local_horizons"], tail["local_horizons"] = hz, np.asarray(hz)[parent]
     coupled = settings.use_coupling == 1
-    # one feature set for both legs, chosen as device.run_points chooses it for the replicated input
-    initlen = np.array([l.InitLenI for l in sl])
-    skyv = np.array([l.sky_view for l in sl])
-    sky_on = bool(((skyv < 1.0) & (skyv > -0.01)).any())
-    need_full = bool(initlen.max() > 1 or settings.force_tsurf == 1 or settings.use_relaxation == 1 or coupled
-                     or sky_on or settings.tsurfOutputDepth >= 0
-                     or any((f["depth"] >= 0).any() or ((f["tdew"] < -90.0) | (f["tdew"] > 100.0)).any()
-                            for f in (head, member_tail)))
-    date = tuple(int(station_forcing[k][0]) for k in ("year", "month", "day"))
+    need_full, sky_on = feature_set(settings, sl, [head, member_tail])  # one feature set for both legs
     from . import device as dv
     dv.require_gpu()
-    sky_st = sky_mem = None
-    if sky_on:  # a member has its station's geometry and horizons
-        hz = station_forcing.get("local_horizons")
-        axes = ("year", "month", "day", "hour", "minute", "second")
-        sky_st = {"axes": {k: np.asarray(station_forcing[k])[:B] for k in axes}, "horizons": hz}
-        sky_mem = {"axes": {k: member_tail[k] for k in axes}, "horizons": None if hz is None else np.asarray(hz)[parent]}
-    st = _Leg(S, 1, head, np.asarray(station_forcing["hour"])[:B], settings, params, sl, need_full, precision, variant,
-              recluster, device, date, sky=sky_st)
-    mem = _Leg(nmem, B + 1, member_tail, member_tail["hour"], settings, params, ml, need_full, precision, variant,
-               recluster, device, date, groups, sky=sky_mem, stats=None if stats is None else (stats, parent))
+    common = dict(need_full=need_full, sky_on=sky_on, precision=precision, variant=variant, recluster=recluster,
+                  device=device, tbottom_date=tuple(int(station_forcing[k][0]) for k in ("year", "month", "day")))
+    st = Leg(head, settings, params, sl, first=1, **common)
+    mem = Leg(tail, settings, params, ml, first=B + 1, groups=groups,
+              stats=None if stats is None else (stats, parent), **common)
     st.init()
-    if coupled:
-        # as device.run_points: lock-step chunks up to the last coupling-window end, the replay rounds over the block
-        # of windows (to the index behind the last one, <= B), the chunks from the first window end on - then every
-        # window is closed, and the members go on in lock step from where every point resumes, B + 1
-        ci = np.array([l.couplingIndexI for l in sl])
-        ct = np.array([l.couplingTsurf for l in sl])
-        on = ~((ct < -100) | (ci < 1))
-        cpl_len = int(settings.coupling_minutes * 60 / settings.DTSecs)
-        cs = np.where(ci <= settings.coupling_minutes * 60 / settings.DTSecs, 1, ci - cpl_len)
-        if on.any():
-            ce_max, ce_min, cs_min = int(ci[on].max()), int(ci[on].min()), int(cs[on].min())
-            st.chunks(1, ce_max, chunk, "step_cpl")
-            st.launch(cs_min, ce_max + 1 - cs_min + 1, "cpl_replay")
-            st.chunks(ce_min + 1, B, chunk, "step_cpl")
-        else:
-            st.chunks(1, B, chunk, "step_cpl")
+    st.run(coupling_stages(settings, sl, B, chunked=True), chunk)
+    if coupled:  # every window is closed, and the members go on in lock step from where every point resumes, B + 1
         st.plan.coupling_windows_closed(True)
-    else:
-        st.chunks(1, B, chunk)
     ev = None
     if timing is not None:
         ev = [st.torch.cuda.Event(enable_timing=True) for _ in range(2)]
@@ -364,10 +192,7 @@ def run_ensemble(station_forcing: dict, member_tail: dict, B: int, settings: abi
     mem.chunks(B + 1, L, chunk, "step_cpl" if coupled else "step")
     res = {"stations": st.results(), "members": mem.results()}
     res["failed"] = (st.plan.failed_count(), mem.plan.failed_count())
-    if mem.gacc is not None:
-        res["groups"] = mem.plan.groups(mem.gacc, mem.gspec)
-    if mem.eacc is not None:
-        res["stats"] = mem.plan.ens(mem.eacc, mem.espec)
+    res.update(mem.reduced())
     if ev:
         timing["fanout_ms"] = float(ev[0].elapsed_time(ev[1]))
     st.plan.close()

@@ -22,7 +22,7 @@ import torch
 
 import golden_helpers as gh
 import oracle_helpers as oh
-from roadsurf_amd import abi, device, lib
+from roadsurf_amd import abi, device, legs, lib
 
 GUARD = 64
 SIMLEN = 241
@@ -371,19 +371,11 @@ def make_knots(plan, arena: Arena, seed: int, wave: int):
 
 
 def sky_params(arena: Arena, f, ls, n):
-    Lh = lib.load()
-    sun = np.zeros((SIMLEN, 6))  # RS_SUN_COLS
-    ax = [np.ascontiguousarray(f[k], np.int32) for k in ("year", "month", "day", "hour", "minute", "second")]
-    Lh.rs_sun_table(SIMLEN, *[C.c_void_p(a.ctypes.data) for a in ax], C.c_void_p(sun.ctypes.data))
-    larr = (abi.LocalParameters * n)(*ls)
-    geo = [np.zeros(n) for _ in range(3)]
-    Lh.rs_point_geometry(n, larr, *[C.c_void_p(g.ctypes.data) for g in geo])
-    sky = {"sky_view": arena.vec("sky_view", np.array([l.sky_view for l in ls]), torch.float64),
-           "sin_lat": arena.vec("sin_lat", geo[0], torch.float64),
-           "cos_lat": arena.vec("cos_lat", geo[1], torch.float64),
-           "lon_rad": arena.vec("lon_rad", geo[2], torch.float64),
-           "horizons": arena.table("horizons", f["local_horizons"], torch.float64),
-           "horizon_index": arena.vec("horizon_index", np.arange(n, dtype=np.int32), torch.int32)}
+    sun, *geo = legs.sky_tables(f, ls)
+    assert sun.shape == (SIMLEN, 6)  # RS_SUN_COLS
+    sky = {k: arena.vec(k, g, torch.float64) for k, g in zip(("sky_view", "sin_lat", "cos_lat", "lon_rad"), geo)}
+    sky["horizons"] = arena.table("horizons", f["local_horizons"], torch.float64)
+    sky["horizon_index"] = arena.vec("horizon_index", np.arange(n, dtype=np.int32), torch.int32)
     return sky, sun
 
 
@@ -455,24 +447,11 @@ def run_case(case: Case, n: int, seed: int, cls: str | None, failing: bool = Fal
     elif case.cpl == "general":
         plan.step(win, out, pp, 1, L, window_row=0, out_row0=0)
     elif case.cpl == "chunk":
-        # device.run_points' stages: lock-step chunks up to the last coupling-window end, the replay rounds over the
-        # window block, then the chunks from the first window end on
-        ci = np.array([l.couplingIndexI for l in ls]); ct = np.array([l.couplingTsurf for l in ls])
-        on = ~((ct < -100) | (ci < 1))
-        cpl_len = int(s.coupling_minutes * 60 / s.DTSecs)
-        cs = np.where(ci <= cpl_len, 1, ci - cpl_len)
-        stages = [(1, L)]
-        if on.any():
-            ce_max, ce_min, cs_min = int(ci[on].max()), int(ci[on].min()), int(cs[on].min())
-            stages = [(1, min(ce_max, L)), ("replay", cs_min, min(ce_max + 1, L)), (ce_min + 1, L)]
-        for st in stages:
-            if st[0] == "replay":
-                plan.cpl_replay(win, out, pp, st[1], st[2] - st[1] + 1, window_row=st[1] - 1, out_row0=0)
-                continue
-            t0_ = st[0]
-            while t0_ <= st[1]:
-                ns = min(97, st[1] - t0_ + 1)
-                plan.step_cpl(win, out, pp, t0_, ns, window_row=t0_ - 1, out_row0=0)
+        for call, lo, hi in legs.coupling_stages(s, ls, L, chunked=True):  # lock-step chunks of 97, a replay whole
+            t0_ = lo
+            while t0_ <= hi:
+                ns = hi - t0_ + 1 if call == "cpl_replay" else min(97, hi - t0_ + 1)
+                getattr(plan, call)(win, out, pp, t0_, ns, window_row=t0_ - 1, out_row0=0)
                 t0_ += ns
     else:
         launches = ((1, 120), (121, 120), (241, 1))  # the series ends in a launch of one index

@@ -9,7 +9,7 @@ import pytest
 
 import ensemble_helpers as eh
 import oracle_helpers as oh
-from roadsurf_amd import abi, ensemble, groups, lib
+from roadsurf_amd import abi, ensemble, groups, legs, lib
 from test_hip_parity import _compare
 
 pytestmark = pytest.mark.gpu
@@ -63,9 +63,9 @@ def test_the_copy_itself_between_two_resorted_plans(precision):
     c = eh.lean_case()
     s, p, date = c["settings"], c["params"], (2024, 1, 10)
     own = oh.synth_forcing(350, 150, seed=13, point_offset=5000)
-    src = ensemble._Leg(70, 1, {k: v[:, :200] for k, v in c["stations"].items() if v.ndim == 2},
-                        c["stations"]["hour"][:200], s, p, [c["local"]] * 70, False, precision, 0, True, 0, date)
-    dst = ensemble._Leg(350, 1, own, own["hour"], s, p, [c["local"]] * 350, False, precision, 0, True, 0, date)
+    kw = dict(need_full=False, precision=precision, recluster=True, tbottom_date=date)
+    src = legs.Leg({k: v[..., :200] for k, v in c["stations"].items()}, s, p, c["local"], **kw)
+    dst = legs.Leg(own, s, p, c["local"], **kw)
     src.init(); src.chunks(1, 200, 100)
     dst.init(); dst.chunks(1, 150, 75)
     src.plan.sync(); dst.plan.sync()

@@ -188,10 +188,20 @@ def test_bit_identity_at_scale_8192_points():
         assert nonident == 0
 
 
+def _lean_window(f, stride, dev):
+    """The LEAN forcing window of the host arrays f[name][n, L]: rows of `stride` columns (>= n), as Leg pads them."""
+    import torch
+    from roadsurf_amd import device, legs
+    tens = {q: legs.pad_rows(f[q], stride, torch.float64, dev) for q in ("tair", "vz", "rhz", "prec", "sw", "lw", "tsurfobs")}
+    tens["tdew"] = tens["depth"] = None
+    tens["precphase"] = legs.pad_rows(f["precphase"], stride, torch.int32, dev)
+    tens["hour"] = torch.from_numpy(np.ascontiguousarray(f["hour"])).to(dev)
+    return device.ForcingWindow(f["tair"].shape[1], stride, tens)
+
+
 def test_output_decimation_matches_driver_semantics():
     """decimate = k keeps indices 1, 1+k, 1+2k, ... (what the reference driver writes with
     outputStep, examples/example1/src/roadrunner.cpp:290,303) and equals the full series there."""
-    import torch
     from roadsurf_amd import device
     n, L, k = 300, 1441, 120
     f = oh.synth_forcing(n, L, seed=21)
@@ -200,16 +210,7 @@ def test_output_decimation_matches_driver_semantics():
     plan = device.Plan(n, s, p, 0)
     dev = plan.device
     npad = plan.np_pad
-
-    def pad_t(a, dtype):
-        t = torch.zeros((L, npad), dtype=dtype, device=dev)
-        t[:, :n] = torch.from_numpy(np.ascontiguousarray(a)).to(dev).T
-        return t
-    tens = {q: pad_t(f[q], torch.float64) for q in ("tair", "vz", "rhz", "prec", "sw", "lw", "tsurfobs")}
-    tens["tdew"] = None; tens["depth"] = None
-    tens["precphase"] = pad_t(f["precphase"], torch.int32)
-    tens["hour"] = torch.from_numpy(f["hour"]).to(dev)
-    win = device.ForcingWindow(L, npad, tens)
+    win = _lean_window(f, npad, dev)
     nrows = (L - 1) // k + 1
     out = device.OutputWindow.empty(nrows, npad, dev, decimate=k)
     pp = plan.point_params(plan.uniform_tbottom(2024, 1, 10))
@@ -228,22 +229,12 @@ def _stepwise(f, s, p, n, variant, chunks, t_stride):
     """Step host arrays through the device API with windows whose row stride is `t_stride` columns
     (>= n: include/roadsurf.h only asks for that), in launches of the given lengths; returns the
     outputs [n, L] and the carried state block."""
-    import torch
     from roadsurf_amd import device
     L = s.SimLen
     plan = device.Plan(n, s, p, 0)
     plan.set_variant(variant)
     dev = plan.device
-
-    def rows(a, dtype):
-        t = torch.zeros((L, t_stride), dtype=dtype, device=dev)
-        t[:, :n] = torch.from_numpy(np.ascontiguousarray(a)).to(dev).T
-        return t
-    tens = {k: rows(f[k], torch.float64) for k in ("tair", "vz", "rhz", "prec", "sw", "lw", "tsurfobs")}
-    tens["tdew"] = tens["depth"] = None
-    tens["precphase"] = rows(f["precphase"], torch.int32)
-    tens["hour"] = torch.from_numpy(np.ascontiguousarray(f["hour"])).to(dev)
-    win = device.ForcingWindow(L, t_stride, tens)
+    win = _lean_window(f, t_stride, dev)
     out = device.OutputWindow.empty(L, t_stride, dev)
     pp = plan.point_params(plan.uniform_tbottom(int(f["year"][0]), int(f["month"][0]), int(f["day"][0])))
     plan.init_state(win, pp)

@@ -47,6 +47,26 @@ def test_sky_view_matches_reference_bitwise(summer, world):
     assert np.abs(plain["tsurf"] - ora["tsurf"]).max() > 0.5  # the branch really changes the result
 
 
+def test_sky_view_without_local_horizons():
+    """No ``local_horizons`` in the forcing: RsPointParams::horizons stays NULL, every horizon is 0 - as the
+    reference's driver leaves the table of a point without one.  One launch and chunks of 97, a June morning, against
+    the reference bit for bit."""
+    from roadsurf_amd import device
+    n, L = 203, 241
+    f, ls = _sky_case(n, L, 5)
+    f.update(oh.time_axis(L, 30.0, (2024, 6, 20, 9, 0, 0)))  # the sun is up
+    del f["local_horizons"]
+    s = abi.default_settings(L); p = abi.default_parameters()
+    ora, _, _ = oh.run_oracle("ref" if oh.have_ref() else "port", f, s, p, ls)
+    for chunk in (0, 97):
+        res, nfail = device.run_points(f, s, p, ls, chunk=chunk)
+        assert nfail == 0
+        for k in oh.F64_OUT:
+            assert np.array_equal(res[k], ora[k]), (chunk, k)
+    plain, _, _ = oh.run_oracle("port", f, s, p, abi.default_local())
+    assert (plain["tsurf"] != ora["tsurf"]).any()  # the sky view acts
+
+
 def test_sky_view_with_coupling_and_c_abi():
     L_ = lib.load()
     n, SL = 200, 1441

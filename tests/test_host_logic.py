@@ -76,13 +76,10 @@ def test_shards_partition_the_points():
     assert sharding.weak_shard(1000, 3) == (3000, 1000)
 
 
-def test_fortran_sun_table_against_oracle_solar_position():
-    """rs_sun_table + rs_point_geometry (Fortran host) recombine to the oracle's elevation:
-    cos(zenith) = sin(decl) sin(lat) + cos(decl) cos(lat) cos(stG + lon - ra)."""
-    import oracle_helpers as oh
+def sun_case():
+    """200 random instants and 200 random places, with rs_sun_table of the instants and rs_point_geometry of the
+    places: (y, mo, d, h, mi, se), ls, tab [200, RS_SUN_COLS], g = [sin_lat, cos_lat, lon_rad]."""
     L = lib.load()
-    port = oh.load("port")
-    port.oracle_probe_sun.argtypes = [C.c_int] * 6 + [C.c_double] * 2 + [abi.c_double_p] * 3
     rs = np.random.RandomState(0)
     n = 200
     y = np.full(n, 2024, np.int32); mo = rs.randint(1, 13, n).astype(np.int32)
@@ -96,6 +93,17 @@ def test_fortran_sun_table_against_oracle_solar_position():
     larr = (abi.LocalParameters * n)(*ls)
     g = [np.zeros(n) for _ in range(3)]
     L.rs_point_geometry(n, larr, *[C.c_void_p(a.ctypes.data) for a in g])
+    return (y, mo, d, h, mi, se), ls, tab, g
+
+
+def test_fortran_sun_table_against_oracle_solar_position():
+    """rs_sun_table + rs_point_geometry (Fortran host) recombine to the oracle's elevation:
+    cos(zenith) = sin(decl) sin(lat) + cos(decl) cos(lat) cos(stG + lon - ra)."""
+    import oracle_helpers as oh
+    port = oh.load("port")
+    port.oracle_probe_sun.argtypes = [C.c_int] * 6 + [C.c_double] * 2 + [abi.c_double_p] * 3
+    (y, mo, d, h, mi, se), ls, tab, g = sun_case()
+    n = len(ls)
     for k in range(n):
         el, az, jde = C.c_double(), C.c_double(), C.c_double()
         assert port.oracle_probe_sun(int(y[k]), int(mo[k]), int(d[k]), int(h[k]), int(mi[k]), int(se[k]),

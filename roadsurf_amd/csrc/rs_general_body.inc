@@ -1,6 +1,7 @@
-/* rs_general_body.inc - what the kernels say about the state block, coupling (src/Coupling.f90), the general
- * time loop with a time index per lane and the initial state, written once and compiled per arithmetic type like
- * rs_physics_body.inc.  Unlike that file it is included INSIDE the flavour's namespace (rs in rs_kernels.hip, rs32 in
+/* rs_general_body.inc - what the kernels say about the state block, coupling (src/Coupling.f90), the rules of
+ * runsimulation's loop between two steps (sky view, coupling window, relaxation, observation forcing: "the rules
+ * between the steps" below, called by every loop shape), the general time loop with a time index per lane and the
+ * initial state, written once and compiled per arithmetic type like rs_physics_body.inc.  Unlike that file it is included INSIDE the flavour's namespace (rs in rs_kernels.hip, rs32 in
  * rs_kernels_f32.hip), behind the flavour's own helpers, because it stands on them:
  *   kBlock, ConstsAS, consts_of, KernArgs, MathTab                     types of the flavour
  *   gather_forcing(ka, p, i, t0), gather_sky(ka, p, i, t0, sw_dir, lw_net), store_point(ka, row, p, s, valid)
@@ -8,7 +9,7 @@
  *   sky_view_radiation(...)             on the flavour's reals (rs_skyview.hpp is fp64)
  *   bl_diagnose(...)                    fp64 only (RS_GEN_FP64_FEATURES)
  * and on the flavour macros RS_REAL, R4(x), RS_DIVC, RS_SECANT_DIV, RS_PROFILE_PIN, RS_CPL_SLOTS(c),
- * RS_CPL_DECAY_TABLE, RS_GEN_PREFETCH, RS_GEN_FP64_FEATURES, RS_INIT_KERNEL, RS_INIT_ANCHOR, RS_INIT_ZERO_TAIL
+ * RS_CPL_DECAY_TABLE, RS_RELAX_TABLE, RS_GEN_PREFETCH, RS_GEN_FP64_FEATURES, RS_INIT_KERNEL, RS_INIT_ANCHOR, RS_INIT_ZERO_TAIL
  * (rs_physics.hpp; the head of rs_kernels_f32.hip), each of which says there which flavour has what. */
 
 /* Output row of time index i: false when the decimation skips it.  UNI: the index is the same in
@@ -271,6 +272,232 @@ __device__ __forceinline__ RS_REAL cpl_decay(const ConstsAS &c, const MathTab &m
   return rs_exp(mt, rs_div(-((c.DTSecs * i) - (c.DTSecs * ce)), c.cplReduction));
 }
 
+/* ---- the rules between the steps: what runsimulation's loop decides per point and per index, each stated once --------
+ * The loop shapes call these: the lock-step loop (time_loop), the surface and sky wavefronts of the two- and
+ * three-wavefront one (duo_surface, duo_sky) and the general loop below.  A point is addressed as (row0, lane) - base[row0 + lane] with the
+ * row base on the scalar unit - or as (p, 0) where the loop has no uniform base.
+ * Sites that keep their own spelling, because the shared one costs machine code that does not come back
+ * (tools/compare_device_code.py against the text before):
+ *   - duo_ground, the ground wavefront: its relaxation, observation forcing and window start (relax_targets,
+ *     relax_valid, relax_factor, relax_apply, obs_forced, cpl_window): through them step_kernel_duo<15, ., SRC_RAW, FULL> grew by 26 instructions and the driver path's
+ *     relaxation leg measured 0.1 % under the slowest of ten runs of the text before (median of ten, alternating);
+ *   - relax_valid and obs_forced in time_loop: as functions of values they are simplified before they are inlined
+ *     and every FULL one-point-per-lane kernel came out in another instruction order;
+ *   - x2d_ground (rs_kernels_f32.hip), the fp32 two-points-per-lane ground wave: sky_point, horizon_row,
+ *     sky_limits_bad, relax_valid and obs_forced fit a component of its f2 forms, but with them the FULL instances
+ *     spill two to twelve registers more and the LEAN knot-reading ones allocate differently; it reads as before;
+ *   - the horizon row of the general loop (time_loop_coupled): formed inside the loop from the point's own index -
+ *     with SkyPoint::hcol carried across the loop step_kernel_coupled spilled four registers more;
+ *   - cpl_window_bounds_kernel: see cpl_window. */
+
+/* Sky view.  The point's set-up, examples/example1/src/Simulation.f90:154-156: fp64 arithmetic in both flavours (the
+ * sun's position decides which degree of the horizon is read: rs_skyview.hpp; sky_view_radiation on floats converts in
+ * and out), the limits are REAL(4) literals.  sin / cos of the longitude once per launch: the addition theorem's point
+ * half.  hcol: the point's column of the local-horizon table (RsPointParams::horizon_index).  The caller has checked
+ * that the plan carries sky view (ka->pp.sky_view). */
+struct SkyPoint {
+  double skyv = R4(1.0), sinlat = 0, coslat = 0, lonrad = 0, coslon = 1.0, sinlon = 0;
+  uint32_t hcol = 0;
+  bool on = false;
+};
+__device__ __forceinline__ SkyPoint sky_point(KernArgs ka, int64_t row0, uint32_t lane = 0u) {
+  SkyPoint k;
+  k.skyv = (ka->pp.sky_view + row0)[lane];
+  k.on = (k.skyv < R4(1.0) && k.skyv > R4(-0.01));
+  if (k.on) {
+    k.sinlat = (ka->pp.sin_lat + row0)[lane];
+    k.coslat = (ka->pp.cos_lat + row0)[lane];
+    k.lonrad = (ka->pp.lon_rad + row0)[lane];
+    k.coslon = ::cos(k.lonrad);
+    k.sinlon = ::sin(k.lonrad);
+  }
+  k.hcol = ka->pp.horizon_index ? (uint32_t)(ka->pp.horizon_index + row0)[lane] : (uint32_t)row0 + lane;
+  return k;
+}
+/* the horizon row of column hcol and the stride between its degrees: [point][360] or [360][np_pad] */
+__device__ __forceinline__ const double *horizon_row(KernArgs ka, int64_t hcol, int64_t &stride) {
+  const double *row = ka->pp.horizons ? ka->pp.horizons + (ka->pp.horizons_by_point ? hcol * 360 : hcol) : nullptr;
+  stride = ka->pp.horizons_by_point ? (int64_t)1 : ka->np_pad;
+  return row;
+}
+/* CheckValues with sky view, src/InputOutput.f90:68-74: the limits of SW_dir and LW_net; :75-77: SW_dir <= SW */
+__device__ __forceinline__ bool sky_limits_bad(RS_REAL sw_dir, RS_REAL lw_net) {
+  return sw_dir < R4(-0.1) || sw_dir > R4(4000.0) || lw_net < R4(-1000.0) || lw_net > R4(1000.0);
+}
+__device__ __forceinline__ RS_REAL sky_clamp_direct(RS_REAL sw_dir, RS_REAL sw) { return sw_dir > sw ? sw : sw_dir; }
+/* The caller's arrays as the reference leaves them, where the launch asks for that (StepArgs::wb): SW_dir clamped by
+ * CheckValues, SW / SW_dir / LW edited by ModRadiationBySurroundings (src/ModRadiation.f90:57-71); a replay overwrites
+ * them.  k: the window row; put(base, v): the loop's own store of its point's element of the row at base. */
+template <class Put>
+__device__ __forceinline__ void sky_write_back(KernArgs ka, int32_t k, int64_t row0, bool sky_on, double sw_dir,
+                                               double sw, double lw, Put put) {
+  if (ka->wb.sw_dir) {
+    const int64_t wrow = (int64_t)k * ka->wb.t_stride + row0;
+    put(ka->wb.sw_dir + wrow, sw_dir);
+    if (sky_on) {
+      put(ka->wb.sw + wrow, sw);
+      put(ka->wb.lw + wrow, lw);
+    }
+  }
+}
+
+/* Coupling.  The window's times: setInputParam + initCouplingTimes, src/InputOutput.f90:30-36, src/Coupling.f90:486-534.
+ * (Filled through a reference: returned by value, step_kernel_cpl_replay<false> spilled five scalar registers fewer -
+ * a difference all the same, tools/compare_device_code.py.  Kept spelled out: cpl_window_bounds_kernel, the replay
+ * call's coverage check, which knows the plan is coupled - through this function its register count changed, 8 -> 6.) */
+struct CplWindow {
+  int32_t cs = -99, ce = -99; /* couplingStartI, couplingEndI */
+  bool on = false;
+};
+__device__ __forceinline__ void cpl_window(KernArgs ka, const ConstsAS &c, int64_t row0, uint32_t lane, CplWindow &w) {
+  const int32_t cidx = ka->pp.coupling_index ? (ka->pp.coupling_index + row0)[lane] : 0;
+  w.on = c.use_coupling && ka->pp.coupling_index && !((ka->pp.coupling_tsurf + row0)[lane] < -100 || cidx < 1);
+  if (w.on) {
+    w.ce = cidx;
+    w.cs = ((RS_REAL)cidx <= c.cplLenR) ? 1 : cidx - c.cplLenI;
+  }
+}
+/* saveDataForCoupling, src/Coupling.f90:172-210: the surface scalars, VeryCold in bit 2 of the flag word.  The layers
+ * (RS_ST_CPL_SAVE_TMP0 ...) are the caller's: each wavefront saves and restores the ones it owns. */
+__device__ __forceinline__ void cpl_save_surface(RS_REAL *st, int64_t np, int64_t p, const Scalars &s) {
+  st[(int64_t)RS_ST_CPL_SAVE_TSURF * np + p] = s.tsurf;
+  st[(int64_t)RS_ST_CPL_SAVE_WAT * np + p] = s.wat;
+  st[(int64_t)RS_ST_CPL_SAVE_ICE2 * np + p] = s.ice2;
+  st[(int64_t)RS_ST_CPL_SAVE_DEP * np + p] = s.dep;
+  st[(int64_t)RS_ST_CPL_SAVE_SNOW * np + p] = s.snow;
+  st[(int64_t)RS_ST_CPL_SAVE_ALBEDO * np + p] = s.albedo;
+  const int32_t fl = ((int32_t)st[(int64_t)RS_ST_CPL_FLAGS * np + p]) & (3 | RS_CPL_MSG_SMALL | RS_CPL_MSG_BIG);
+  st[(int64_t)RS_ST_CPL_FLAGS * np + p] = (RS_REAL)(fl | (s.verycold ? 4 : 0));
+}
+/* uploadDataForCoupling, src/Coupling.f90:213-255: SrfIcemms, Q2Melt, T4Melt and TmpNw are NOT restored (TmpNw keeps
+ * the end-of-window profile for the first step).  CLEAR_AGAIN: start_coupling_again = .false. goes to the flag word
+ * here (the lock-step loops; the general loop carries the flag in its Coupling and stores it at its end). */
+template <bool CLEAR_AGAIN>
+__device__ __forceinline__ void cpl_restore_surface(RS_REAL *st, int64_t np, int64_t p, Scalars &s) {
+  s.tsurf = st[(int64_t)RS_ST_CPL_SAVE_TSURF * np + p];
+  s.wat = st[(int64_t)RS_ST_CPL_SAVE_WAT * np + p];
+  s.ice2 = st[(int64_t)RS_ST_CPL_SAVE_ICE2 * np + p];
+  s.dep = st[(int64_t)RS_ST_CPL_SAVE_DEP * np + p];
+  s.snow = st[(int64_t)RS_ST_CPL_SAVE_SNOW * np + p];
+  s.albedo = st[(int64_t)RS_ST_CPL_SAVE_ALBEDO * np + p];
+  const int32_t fl = (int32_t)st[(int64_t)RS_ST_CPL_FLAGS * np + p];
+  s.verycold = (fl & 4) != 0;
+  if (CLEAR_AGAIN) st[(int64_t)RS_ST_CPL_FLAGS * np + p] = (RS_REAL)(fl & ~1);
+}
+/* SWRadCof / LWRadCof of a replay, src/Coupling.f90:68-76: short-wave scaling by day, long-wave by night - and always
+ * with sky view */
+__device__ __forceinline__ void cpl_rewind_coefs(RS_REAL radcoeff, RS_REAL sw, RS_REAL lw, bool sky_on, RS_REAL &swcof,
+                                                 RS_REAL &lwcof) {
+  if (sw > lw && !sky_on) {
+    swcof = radcoeff;
+    lwcof = R4(1.0);
+  } else {
+    swcof = R4(1.0);
+    lwcof = radcoeff;
+  }
+}
+/* behind the window the corrections decay, :80-88 */
+__device__ __forceinline__ void cpl_decayed_coefs(const ConstsAS &c, const MathTab &mt, int32_t i, int32_t ce,
+                                                  RS_REAL swcorr, RS_REAL lwcorr, RS_REAL &swcof, RS_REAL &lwcof) {
+  const RS_REAL e = cpl_decay(c, mt, i, ce);
+  swcof = R4(1.0) + swcorr * e;
+  lwcof = R4(1.0) + lwcorr * e;
+}
+/* lastValues (src/InputOutput.f90:169-198) runs no CouplingOperations1: coupling%inCouplingPhase and SW/LWRadCof keep
+ * the values of index SimLen - 1 - decayed behind the window; where the window reaches the end of the series, as the
+ * last pass left them in the state block.  (The general loop carries the coefficients and needs the phase only.) */
+__device__ __forceinline__ void cpl_last_values(const ConstsAS &c, const MathTab &mt, const CplWindow &w, RS_REAL swcorr,
+                                                RS_REAL lwcorr, const RS_REAL *st, int64_t np, int64_t p,
+                                                CouplingInputs &cp) {
+  const int32_t j = c.SimLen - 1;
+  cp.in_phase = (j >= w.cs && j <= w.ce);
+  if (j > w.ce) {
+    cpl_decayed_coefs(c, mt, j, w.ce, swcorr, lwcorr, cp.sw_cof, cp.lw_cof);
+  } else if (j >= w.cs) {
+    cp.sw_cof = st[(int64_t)RS_ST_CPL_SWCOF * np + p];
+    cp.lw_cof = st[(int64_t)RS_ST_CPL_LWCOF * np + p];
+  }
+}
+/* snowIceCheck, src/Coupling.f90:259-289 (in the coupling phase) */
+__device__ __forceinline__ void snow_ice_check(const ConstsAS &c, RS_REAL lastobs, Scalars &s) {
+  if (lastobs > c.TLimMeltSnow && s.snow > R4(0.00)) { s.wat = s.wat + s.snow; s.snow = R4(0.00); }
+  if (lastobs > c.TLimMeltIce && s.ice > R4(0.00)) { s.wat = s.wat + s.ice; s.ice = R4(0.00); }
+  if (lastobs > c.TLimMeltIce && s.ice2 > R4(0.00)) s.ice2 = R4(0.00);
+  if (lastobs > c.TLimMeltDep && s.dep > R4(0.00)) { s.wat = s.wat + s.dep; s.dep = R4(0.00); }
+}
+/* CheckEndCoupling + CouplingOperations2 at the window end, src/Coupling.f90:98-141, for a point whose coupling has not
+ * failed.  A point that failed CheckValues at this very index still runs Coupling_control (CheckEndCoupling does not
+ * look at simulation_failed), but its loop exits before any rewind: it asks for no replay - the rows behind its window
+ * stay -9999.0 - and is not listed. */
+__device__ __forceinline__ void cpl_decide(Coupling &q, Scalars &s) {
+  if (q.iter == 0) q.tend1 = s.tsurf;
+  coupling_control(q, s.tsurf);
+  q.iter = q.iter + 1;
+  if (s.failed) q.again = false;
+}
+/* ... where CouplingVariables live in the state block (the lock-step loops: Coupling_failed is .false. before the first
+ * decision).  The corrections and the observation - which went to Kelvin and back in Coupling_control - return to the
+ * caller's registers; parked: the point replays its window in the rounds (RS_ST_CPL_RESUME = i + 1). */
+__device__ __forceinline__ void cpl_window_end(RS_REAL *st, int64_t np, int64_t p, const CplWindow &w, Scalars &s,
+                                               RS_REAL &swcorr, RS_REAL &lwcorr, RS_REAL &lastobs, bool &parked) {
+  Coupling q;
+  load_coupling(st, np, p, q);
+  q.cs = w.cs; q.ce = w.ce; q.on = true;
+  if (!q.failed) {
+    cpl_decide(q, s);
+    store_coupling(st, np, p, q);
+    swcorr = q.swcorr;
+    lwcorr = q.lwcorr;
+    lastobs = q.lastobs;
+    parked = q.again;
+  }
+}
+
+/* Relaxation, src/Relaxation.f90:10-47.  The targets pass through REAL(4) (setInputParam, src/InputOutput.f90:19-26);
+ * RelaxationOperations (:34-43) only ever uses target - anchor, the anchors being the forcing of index InitLenI. */
+__device__ __forceinline__ void relax_targets(KernArgs ka, int64_t row0, uint32_t lane, RS_REAL &tairR, RS_REAL &vzR,
+                                              RS_REAL &rhR) {
+  tairR = (RS_REAL)(float)(ka->pp.tair_relax + row0)[lane];
+  vzR = (RS_REAL)(float)(ka->pp.vz_relax + row0)[lane];
+  rhR = (RS_REAL)(float)(ka->pp.rh_relax + row0)[lane];
+}
+__device__ __forceinline__ bool relax_valid(RS_REAL tairR, RS_REAL vzR, RS_REAL rhR) {
+  return !(tairR < R4(-100.0) || tairR > R4(100.0) || vzR < R4(0.0) || vzR > R4(100.0) || rhR < R4(0.0) || rhR > 110);
+}
+/* exp(-(DT*i - DT*InitLenI)/14400), i > InitLenI: for an integral time step the argument is a function of i - InitLenI
+ * alone and the plan holds the table (rs_consts_dev.h, host libm = the bits rs_exp returns); otherwise evaluated here.
+ * TABLE = false: the general loop, which has never read the table, in either flavour. */
+template <bool TABLE = (RS_RELAX_TABLE != 0)>
+__device__ __forceinline__ RS_REAL relax_factor(const ConstsAS &c, const MathTab &mt, int32_t i, int32_t initlen) {
+  RS_REAL e;
+#if RS_RELAX_TABLE
+  const uint32_t d = (uint32_t)(i - initlen);
+  if (TABLE && c.relax_tab && d <= (uint32_t)c.SimLen) {
+    e = ((const double *)c.relax_tab)[d];
+  } else
+#endif
+  {
+    const RS_REAL den = (RS_REAL)(4.f * 3600.f);
+    e = rs_exp(mt, rs_div(-((c.DTSecs * i) - (c.DTSecs * initlen)), den));
+  }
+  return e;
+}
+/* d*: target - anchor */
+__device__ __forceinline__ void relax_apply(RS_REAL e, RS_REAL dt, RS_REAL dv, RS_REAL dr, RS_REAL &tair, RS_REAL &vz,
+                                            RS_REAL &rhz) {
+  tair = tair - dt * e;
+  vz = vz - dv * e;
+  rhz = rhz - dr * e;
+  if (rhz > R4(100.)) rhz = R4(100.0);
+}
+
+/* SetCurrentValues' observation forcing, src/InputOutput.f90:116-148: the observation goes on Tmp(1:2) during the
+ * initialization phase (force_tsurf: always), but never from the start of the point's coupling window on (:120-121) */
+__device__ __forceinline__ bool obs_forced(const ConstsAS &c, int32_t i, int32_t initlen, RS_REAL obs, bool cpl_on,
+                                           int32_t cs) {
+  return (i <= initlen || c.force_tsurf) && obs > R4(-100.0) && (!cpl_on || i < cs);
+}
+
 /* runsimulation's loop with coupling (examples/example1/src/Simulation.f90:57-115):
  * CheckValues -> CouplingOperations1 (may rewind i) -> SetCurrentValues -> relaxation ->
  * roadModelOneStep -> SaveOutput -> CheckEndCoupling. */
@@ -286,37 +513,15 @@ __device__ __forceinline__ void time_loop_coupled(const MathTab &mt, Prof &T, Sc
   bool relax = false;
   RS_REAL tairR = 0, vzR = 0, rhR = 0;
   if (c.use_relaxation && ka->pp.tair_relax) {
-    tairR = (RS_REAL)(float)ka->pp.tair_relax[p];
-    vzR = (RS_REAL)(float)ka->pp.vz_relax[p];
-    rhR = (RS_REAL)(float)ka->pp.rh_relax[p];
-    relax = !(tairR < R4(-100.0) || tairR > R4(100.0) || vzR < R4(0.0) || vzR > R4(100.0) ||
-              rhR < R4(0.0) || rhR > 110);
+    relax_targets(ka, p, 0u, tairR, vzR, rhR);
+    relax = relax_valid(tairR, vzR, rhR);
   }
-  /* setInputParam + initCouplingTimes, src/InputOutput.f90:30-36, src/Coupling.f90:486-534 */
-  const int32_t cidx = ka->pp.coupling_index ? ka->pp.coupling_index[p] : 0;
-  q.on = c.use_coupling && ka->pp.coupling_index &&
-         !(ka->pp.coupling_tsurf[p] < -100 || cidx < 1);
-  q.cs = -99; q.ce = -99;
-  if (q.on) {
-    q.ce = cidx;
-    q.cs = ((RS_REAL)cidx <= c.cplLenR) ? 1 : cidx - c.cplLenI;
-  }
-  /* sky view, examples/example1/src/Simulation.f90:154-156: fp64 arithmetic in both flavours (the sun's position
-   * decides which degree of the horizon is read: rs_skyview.hpp; sky_view_radiation on floats converts in and out),
-   * the limits are REAL(4) literals */
-  double skyv = R4(1.0), sinlat = 0, coslat = 0, lonrad = 0, coslon = 1.0, sinlon = 0;
-  bool sky_on = false;
-  if (ka->pp.sky_view) {
-    skyv = ka->pp.sky_view[p];
-    sky_on = (skyv < R4(1.0) && skyv > R4(-0.01));
-    if (sky_on) {
-      sinlat = ka->pp.sin_lat[p];
-      coslat = ka->pp.cos_lat[p];
-      lonrad = ka->pp.lon_rad[p];
-      coslon = ::cos(lonrad);
-      sinlon = ::sin(lonrad);
-    }
-  }
+  CplWindow w;
+  cpl_window(ka, c, p, 0u, w);
+  q.on = w.on; q.cs = w.cs; q.ce = w.ce;
+  SkyPoint sky;
+  if (ka->pp.sky_view) sky = sky_point(ka, p);
+  const bool sky_on = sky.on;
 
   auto fail_at = [&](int32_t idx) {
     s.failed = true;
@@ -353,39 +558,20 @@ __device__ __forceinline__ void time_loop_coupled(const MathTab &mt, Prof &T, Sc
     if (ka->f.sw_dir) gather_sky(ka, p, i, t0, sw_dir, lw_net);
     if (i < c.SimLen) {
       if (check_values(c, f, s.tsurf, ka->f.tdew != nullptr)) fail_at(i);
-      if (sky_on && (sw_dir < R4(-0.1) || sw_dir > R4(4000.0) || lw_net < R4(-1000.0) ||
-                     lw_net > R4(1000.0)))
-        fail_at(i); /* src/InputOutput.f90:68-74 */
-      if (sw_dir > f.sw) sw_dir = f.sw; /* :75-77 */
+      if (sky_on && sky_limits_bad(sw_dir, lw_net)) fail_at(i);
+      sw_dir = sky_clamp_direct(sw_dir, f.sw);
       if (q.on) {
         /* CouplingOperations1, src/Coupling.f90:10-96 */
         bool in_phase = (i >= q.cs && i <= q.ce);
         if (i == q.cs && q.iter == 0) {
-          /* saveDataForCoupling :172-210 */
-          st[(int64_t)RS_ST_CPL_SAVE_TSURF * np + p] = s.tsurf;
-          st[(int64_t)RS_ST_CPL_SAVE_WAT * np + p] = s.wat;
-          st[(int64_t)RS_ST_CPL_SAVE_ICE2 * np + p] = s.ice2;
-          st[(int64_t)RS_ST_CPL_SAVE_DEP * np + p] = s.dep;
-          st[(int64_t)RS_ST_CPL_SAVE_SNOW * np + p] = s.snow;
-          st[(int64_t)RS_ST_CPL_SAVE_ALBEDO * np + p] = s.albedo;
-          const int32_t fl = ((int32_t)st[(int64_t)RS_ST_CPL_FLAGS * np + p]) & (3 | RS_CPL_MSG_SMALL | RS_CPL_MSG_BIG);
-          st[(int64_t)RS_ST_CPL_FLAGS * np + p] = (RS_REAL)(fl | (s.verycold ? 4 : 0));
+          cpl_save_surface(st, np, p, s);
           for (int j = 1; j <= N; ++j) st[(int64_t)(RS_ST_CPL_SAVE_TMP0 + j - 1) * np + p] = T.get(j);
           q.swcof = R4(1.0); q.lwcof = R4(1.0); q.swcorr = R4(0.0); q.lwcorr = R4(0.0);
         }
-        if (q.again) {
-          /* uploadDataForCoupling :213-255: back to the window start; SrfIcemms, Q2Melt,
-           * T4Melt and TmpNw are NOT restored */
+        if (q.again) { /* back to the window start */
           i = q.cs;
-          s.tsurf = st[(int64_t)RS_ST_CPL_SAVE_TSURF * np + p];
-          s.wat = st[(int64_t)RS_ST_CPL_SAVE_WAT * np + p];
-          s.ice2 = st[(int64_t)RS_ST_CPL_SAVE_ICE2 * np + p];
-          s.dep = st[(int64_t)RS_ST_CPL_SAVE_DEP * np + p];
-          s.snow = st[(int64_t)RS_ST_CPL_SAVE_SNOW * np + p];
-          s.albedo = st[(int64_t)RS_ST_CPL_SAVE_ALBEDO * np + p];
-          s.verycold = (((int32_t)st[(int64_t)RS_ST_CPL_FLAGS * np + p]) & 4) != 0;
+          cpl_restore_surface<false>(st, np, p, s);
           for (int j = 1; j <= N; ++j) {
-            /* TmpNw keeps the end-of-window profile */
             st[(int64_t)(RS_ST_CPL_STALE_TMP0 + j - 1) * np + p] = T.get(j);
             T.set(j, st[(int64_t)(RS_ST_CPL_SAVE_TMP0 + j - 1) * np + p]);
           }
@@ -397,33 +583,15 @@ __device__ __forceinline__ void time_loop_coupled(const MathTab &mt, Prof &T, Sc
             /* the restored window holds the arrays as CheckValues left them in the first
              * pass: SW_dir already clamped to SW (src/Coupling.f90:204-208,249-253) */
             gather_sky(ka, p, i, t0, sw_dir, lw_net);
-            if (sw_dir > f.sw) sw_dir = f.sw;
+            sw_dir = sky_clamp_direct(sw_dir, f.sw);
           }
-          /* short-wave scaling only without sky view (:68-76) */
-          if (f.sw > f.lw && !sky_on) {
-            q.swcof = q.radcoeff;
-            q.lwcof = R4(1.0);
-          } else {
-            q.swcof = R4(1.0);
-            q.lwcof = q.radcoeff;
-          }
+          cpl_rewind_coefs(q.radcoeff, f.sw, f.lw, sky_on, q.swcof, q.lwcof);
         }
-        if (i > q.ce) {
-          const RS_REAL e = cpl_decay(c, mt, i, q.ce);
-          q.swcof = R4(1.0) + q.swcorr * e;
-          q.lwcof = R4(1.0) + q.lwcorr * e;
-        }
-        if (in_phase) {
-          /* snowIceCheck :259-289 */
-          if (q.lastobs > c.TLimMeltSnow && s.snow > R4(0.00)) { s.wat = s.wat + s.snow; s.snow = R4(0.00); }
-          if (q.lastobs > c.TLimMeltIce && s.ice > R4(0.00)) { s.wat = s.wat + s.ice; s.ice = R4(0.00); }
-          if (q.lastobs > c.TLimMeltIce && s.ice2 > R4(0.00)) s.ice2 = R4(0.00);
-          if (q.lastobs > c.TLimMeltDep && s.dep > R4(0.00)) { s.wat = s.wat + s.dep; s.dep = R4(0.00); }
-        }
+        if (i > q.ce) cpl_decayed_coefs(c, mt, i, q.ce, q.swcorr, q.lwcorr, q.swcof, q.lwcof);
+        if (in_phase) snow_ice_check(c, q.lastobs, s);
         cp.in_phase = in_phase;
       }
-      /* SetCurrentValues obs forcing, src/InputOutput.f90:116-148 */
-      if ((i <= initlen || c.force_tsurf) && f.tsurfobs > R4(-100.0) && (!q.on || i < q.cs)) {
+      if (obs_forced(c, i, initlen, f.tsurfobs, q.on, q.cs)) {
         T.set(1, f.tsurfobs);
         T.set(2, f.tsurfobs);
         const RS_REAL depth = (c.tsurfOutputDepth >= R4(0.0)) ? c.tsurfOutputDepth : f.depth;
@@ -437,16 +605,11 @@ __device__ __forceinline__ void time_loop_coupled(const MathTab &mt, Prof &T, Sc
     }
     RS_REAL tair = f.tair, vz = f.vz, rhz = f.rhz;
     const RS_REAL prec_ts = RS_DIVC(f.prec, R4(3600.0), r_3600) * c.DTSecs;
-    if (i < c.SimLen && relax) { /* RelaxationOperations, src/Relaxation.f90:10-47 */
-      if (i == initlen) { s.tair_end = tair; s.vz_end = vz; s.rh_end = rhz; }
-      if (i > initlen) {
-        const RS_REAL den = (RS_REAL)(4.f * 3600.f);
-        const RS_REAL e = rs_exp(mt, rs_div(-((c.DTSecs * i) - (c.DTSecs * initlen)), den));
-        tair = tair - (tairR - s.tair_end) * e;
-        vz = vz - (vzR - s.vz_end) * e;
-        rhz = rhz - (rhR - s.rh_end) * e;
-        if (rhz > R4(100.)) rhz = R4(100.0);
-      }
+    if (i < c.SimLen && relax) {
+      if (i == initlen) { s.tair_end = tair; s.vz_end = vz; s.rh_end = rhz; } /* the anchors: part of this loop's Scalars */
+      if (i > initlen)
+        relax_apply(relax_factor<false>(c, mt, i, initlen), tairR - s.tair_end, vzR - s.vz_end, rhR - s.rh_end, tair, vz,
+                    rhz);
     }
     cp.sw_cof = q.swcof; cp.lw_cof = q.lwcof; cp.last_tsurf_obs = q.lastobs;
     RS_REAL sw_in = f.sw, lw_in = f.lw;
@@ -456,8 +619,8 @@ __device__ __forceinline__ void time_loop_coupled(const MathTab &mt, Prof &T, Sc
        * sky_view_radiation and, below, output_row + store_point spelled out here: with the conversions to double
        * or SaveOutput as one function in this text, step_kernel_coupled's machine code changed -
        * tools/compare_device_code.py) */
-      if (!sky_view_radiation(ka->f.sun + (int64_t)(i - t0) * RS_SUN_COLS, sinlat, coslat, lonrad, coslon, sinlon, skyv,
-                              ka->pp.albedo_surroundings,
+      if (!sky_view_radiation(ka->f.sun + (int64_t)(i - t0) * RS_SUN_COLS, sky.sinlat, sky.coslat, sky.lonrad, sky.coslon,
+                              sky.sinlon, sky.skyv, ka->pp.albedo_surroundings,
                               ka->pp.horizons
                                   ? ka->pp.horizons + (ka->pp.horizon_index ? (int64_t)ka->pp.horizon_index[p] : p) *
                                                           (ka->pp.horizons_by_point ? 360 : 1)
@@ -466,14 +629,7 @@ __device__ __forceinline__ void time_loop_coupled(const MathTab &mt, Prof &T, Sc
         fail_at(i); /* the reference would `stop` the process here */
     }
 #if RS_GEN_FP64_FEATURES
-    if (ka->wb.sw_dir) { /* in-place input edits of the reference; a replay overwrites them */
-      const int64_t woff = (int64_t)(i - t0) * ka->wb.t_stride + p;
-      ka->wb.sw_dir[woff] = sw_dir;
-      if (sky_on) {
-        ka->wb.sw[woff] = sw_in;
-        ka->wb.lw[woff] = lw_in;
-      }
-    }
+    sky_write_back(ka, i - t0, p, sky_on, sw_dir, sw_in, lw_in, [](double *base, double v) { *base = v; });
     if (DIAG) bl_diagnose(&c, mt.expT, mt.logT, mt.K, s.tsurf, tair, vz, rhz, f.hour, i, ka->diag, np, p);
 #endif
     const Fluxes fx = model_step_fluxes(c, mt, s, tair, vz, rhz, prec_ts, sw_in, lw_in, f.phase,
@@ -494,12 +650,8 @@ __device__ __forceinline__ void time_loop_coupled(const MathTab &mt, Prof &T, Sc
     int64_t orow;
     if (output_row<false>(ka, i, orow)) store_point(ka, orow, p, s, true);
     if (i > written_hi) written_hi = i;
-    /* CheckEndCoupling + CouplingOperations2, src/Coupling.f90:98-141 */
     if (i < c.SimLen && q.on && i == q.ce && !q.failed) {
-      if (q.iter == 0) q.tend1 = s.tsurf;
-      coupling_control(q, s.tsurf);
-      q.iter = q.iter + 1;
-      if (s.failed) q.again = false; /* failed at this index: the loop exits, no rewind, not listed */
+      cpl_decide(q, s);
 #if RS_GEN_FP64_FEATURES
       if (ka->cpl_stop) { /* park: the next round decides between a replay and going on */
         ++i;

@@ -340,40 +340,21 @@ __device__ __forceinline__ void time_loop(const MathTab &mt, Prof &T, Scalars &s
   const int64_t row0 = REPLAY ? 0 : (int64_t)blockIdx.x * kBlock; /* first point of this workgroup */
   const int32_t nsteps = ka->nsteps, t0 = ka->t0;
   const double tbot = (ka->pp.tbottom + row0)[lane];
-  double skyv = R4(1.0), sinlat = 0, coslat = 0, lonrad = 0, coslon = 1.0, sinlon = 0;
-  bool sky_on = false;
-  uint32_t hcol = 0; /* the point's column of the local-horizon table (RsPointParams::horizon_index) */
-  if (SKY) {
-    skyv = (ka->pp.sky_view + row0)[lane];
-    sky_on = (skyv < R4(1.0) && skyv > R4(-0.01));
-    if (sky_on) {
-      sinlat = (ka->pp.sin_lat + row0)[lane];
-      coslat = (ka->pp.cos_lat + row0)[lane];
-      lonrad = (ka->pp.lon_rad + row0)[lane];
-      coslon = ::cos(lonrad); /* once per launch: the addition theorem's point half (sky_view_radiation) */
-      sinlon = ::sin(lonrad);
-    }
-    hcol = ka->pp.horizon_index ? (uint32_t)(ka->pp.horizon_index + row0)[lane] : (uint32_t)row0 + lane;
-  }
+  SkyPoint sky;
+  if (SKY) sky = sky_point(ka, row0, lane);
+  const bool sky_on = sky.on;
   int32_t initlen = 0;
   bool relax = false;
-  /* RelaxationOperations (src/Relaxation.f90:34-43) only ever uses target - anchor: the three
-   * differences are what the loop carries (the targets are read again at the one index that sets
-   * the anchors, the anchors go to the state block there and then) */
+  /* relaxation: the three differences target - anchor are what the loop carries (the targets are read again at
+   * the one index that sets the anchors, the anchors go to the state block there and then) */
   double relax_dt = 0, relax_dv = 0, relax_dr = 0;
-  auto relax_targets = [&](double &tairR, double &vzR, double &rhR) {
-    /* setInputParam, src/InputOutput.f90:19-26: targets pass through REAL(4) */
-    tairR = (double)(float)(ka->pp.tair_relax + row0)[lane];
-    vzR = (double)(float)(ka->pp.vz_relax + row0)[lane];
-    rhR = (double)(float)(ka->pp.rh_relax + row0)[lane];
-  };
   if (FULL) {
     initlen = ka->pp.initlen ? (ka->pp.initlen + row0)[lane] : 0;
     if (consts_of(ka).use_relaxation && ka->pp.tair_relax) {
       double tairR, vzR, rhR;
-      relax_targets(tairR, vzR, rhR);
+      relax_targets(ka, row0, lane, tairR, vzR, rhR);
       relax = !(tairR < R4(-100.0) || tairR > R4(100.0) || vzR < R4(0.0) || vzR > R4(100.0) ||
-                rhR < R4(0.0) || rhR > 110);
+                rhR < R4(0.0) || rhR > 110); /* (relax_valid, spelled out: see rs_general_body.inc) */
       relax_dt = tairR - s.tair_end;
       relax_dv = vzR - s.vz_end;
       relax_dr = rhR - s.rh_end;
@@ -388,20 +369,16 @@ __device__ __forceinline__ void time_loop(const MathTab &mt, Prof &T, Scalars &s
   };
   /* coupling, lock-step part: what a lane needs every step stays in registers, the rest of
    * CouplingVariables lives in the state block and is touched at the two events only */
-  bool cpl_on = false, parked = false;
-  int32_t cpl_cs = -99, cpl_ce = -99, next_i = t0;
+  CplWindow cw;
+  if (CPL) cpl_window(ka, consts_of(ka), row0, lane, cw);
+  const bool cpl_on = cw.on;
+  const int32_t cpl_cs = cw.cs, cpl_ce = cw.ce;
+  bool parked = false;
+  int32_t next_i = t0;
   double cpl_lastobs = 0.0, cpl_swcorr = 0.0, cpl_lwcorr = 0.0;
   if (CPL) {
     double *st = ka->state;
     const int64_t np = ka->np_pad, p = row0 + lane;
-    const int32_t cidx = ka->pp.coupling_index ? (ka->pp.coupling_index + row0)[lane] : 0;
-    /* setInputParam + initCouplingTimes, src/InputOutput.f90:30-36, src/Coupling.f90:486-534 */
-    cpl_on = consts_of(ka).use_coupling && ka->pp.coupling_index &&
-             !((ka->pp.coupling_tsurf + row0)[lane] < -100 || cidx < 1);
-    if (cpl_on) {
-      cpl_ce = cidx;
-      cpl_cs = ((double)cidx <= consts_of(ka).cplLenR) ? 1 : cidx - consts_of(ka).cplLenI;
-    }
     cpl_lastobs = st[(int64_t)RS_ST_CPL_LASTOBS * np + p];
     cpl_swcorr = st[(int64_t)RS_ST_CPL_SWCORR * np + p];
     cpl_lwcorr = st[(int64_t)RS_ST_CPL_LWCORR * np + p];
@@ -489,13 +466,11 @@ __device__ __forceinline__ void time_loop(const MathTab &mt, Prof &T, Scalars &s
           /* the rewind: CheckValues has just seen the index behind the window end (above) */
           if (sky_on) {
             const int64_t off = (int64_t)(cpl_ce + 1 - t0) * ka->f.t_stride + row0 + lane;
-            const double sd = ka->f.sw_dir[off], ln = ka->f.lw_net[off];
-            if (sd < R4(-0.1) || sd > R4(4000.0) || ln < R4(-1000.0) || ln > R4(1000.0)) fail_at(cpl_ce + 1);
+            if (sky_limits_bad(ka->f.sw_dir[off], ka->f.lw_net[off])) fail_at(cpl_ce + 1);
           }
-        } else if (sky_on && (sw_dir < R4(-0.1) || sw_dir > R4(4000.0) || lw_net < R4(-1000.0) ||
-                              lw_net > R4(1000.0)))
-          fail_at(i);                           /* src/InputOutput.f90:68-74 */
-        if (sw_dir > f.sw) sw_dir = f.sw;       /* :75-77 */
+        } else if (sky_on && sky_limits_bad(sw_dir, lw_net))
+          fail_at(i);
+        sw_dir = sky_clamp_direct(sw_dir, f.sw);
       }
       if (CPL && cpl_on) {
         /* CouplingOperations1, src/Coupling.f90:10-96, first pass of the window */
@@ -504,71 +479,36 @@ __device__ __forceinline__ void time_loop(const MathTab &mt, Prof &T, Scalars &s
          * :61-66): the step at the window start of a replay runs outside the coupling phase */
         if (REPLAY && i == cpl_cs) cp.in_phase = false;
         if (REPLAY && i == cpl_cs) {
-          /* uploadDataForCoupling :213-255: SrfIcemms, Q2Melt, T4Melt and TmpNw are NOT restored;
-           * TmpNw keeps the end-of-window profile for the first step */
           double *st = ka->state;
           const int64_t np = ka->np_pad, p = row0 + lane;
-          s.tsurf = st[(int64_t)RS_ST_CPL_SAVE_TSURF * np + p];
-          s.wat = st[(int64_t)RS_ST_CPL_SAVE_WAT * np + p];
-          s.ice2 = st[(int64_t)RS_ST_CPL_SAVE_ICE2 * np + p];
-          s.dep = st[(int64_t)RS_ST_CPL_SAVE_DEP * np + p];
-          s.snow = st[(int64_t)RS_ST_CPL_SAVE_SNOW * np + p];
-          s.albedo = st[(int64_t)RS_ST_CPL_SAVE_ALBEDO * np + p];
-          const int32_t fl = (int32_t)st[(int64_t)RS_ST_CPL_FLAGS * np + p];
-          s.verycold = (fl & 4) != 0;
-          st[(int64_t)RS_ST_CPL_FLAGS * np + p] = (double)(fl & ~1); /* start_coupling_again = .false. */
+          cpl_restore_surface<true>(st, np, p, s);
           const int N = T.nlayers();
           for (int j = 1; j <= N; ++j) {
             st[(int64_t)(RS_ST_CPL_STALE_TMP0 + j - 1) * np + p] = T.get(j);
             T.set(j, st[(int64_t)(RS_ST_CPL_SAVE_TMP0 + j - 1) * np + p]);
           }
           stale_now = true;
-          /* short-wave scaling by day, long-wave by night - and always with sky view (:68-76) */
-          const double radcoeff = st[(int64_t)RS_ST_CPL_RADCOEFF * np + p];
-          if (f.sw > f.lw && !(SKY && sky_on)) {
-            r_swcof = radcoeff;
-            r_lwcof = R4(1.0);
-          } else {
-            r_swcof = R4(1.0);
-            r_lwcof = radcoeff;
-          }
+          cpl_rewind_coefs(st[(int64_t)RS_ST_CPL_RADCOEFF * np + p], f.sw, f.lw, SKY && sky_on, r_swcof, r_lwcof);
           st[(int64_t)RS_ST_CPL_SWCOF * np + p] = r_swcof; /* Coupling_control reads them at the end */
           st[(int64_t)RS_ST_CPL_LWCOF * np + p] = r_lwcof;
         }
-        if (!REPLAY && i == cpl_cs) { /* Coupling_iterations == 0 here: saveDataForCoupling :172-210 */
+        if (!REPLAY && i == cpl_cs) { /* Coupling_iterations == 0 here */
           double *st = ka->state;
           const int64_t np = ka->np_pad, p = row0 + lane;
-          st[(int64_t)RS_ST_CPL_SAVE_TSURF * np + p] = s.tsurf;
-          st[(int64_t)RS_ST_CPL_SAVE_WAT * np + p] = s.wat;
-          st[(int64_t)RS_ST_CPL_SAVE_ICE2 * np + p] = s.ice2;
-          st[(int64_t)RS_ST_CPL_SAVE_DEP * np + p] = s.dep;
-          st[(int64_t)RS_ST_CPL_SAVE_SNOW * np + p] = s.snow;
-          st[(int64_t)RS_ST_CPL_SAVE_ALBEDO * np + p] = s.albedo;
-          const int32_t fl = ((int32_t)st[(int64_t)RS_ST_CPL_FLAGS * np + p]) & (3 | RS_CPL_MSG_SMALL | RS_CPL_MSG_BIG);
-          st[(int64_t)RS_ST_CPL_FLAGS * np + p] = (double)(fl | (s.verycold ? 4 : 0));
+          cpl_save_surface(st, np, p, s);
           const int N = T.nlayers();
           for (int j = 1; j <= N; ++j) st[(int64_t)(RS_ST_CPL_SAVE_TMP0 + j - 1) * np + p] = T.get(j);
           /* SW/LWRadCof = 1, SW/LW_correction = 0: what the registers hold before the window end */
         }
-        if (i > cpl_ce) {
-          const double e = cpl_decay(c, mt, i, cpl_ce);
-          cp.sw_cof = R4(1.0) + cpl_swcorr * e;
-          cp.lw_cof = R4(1.0) + cpl_lwcorr * e;
-        }
+        if (i > cpl_ce) cpl_decayed_coefs(c, mt, i, cpl_ce, cpl_swcorr, cpl_lwcorr, cp.sw_cof, cp.lw_cof);
         if (REPLAY && i >= cpl_cs && i <= cpl_ce) {
           cp.sw_cof = r_swcof;
           cp.lw_cof = r_lwcof;
         }
-        if (cp.in_phase) {
-          /* snowIceCheck :259-289 */
-          if (cpl_lastobs > c.TLimMeltSnow && s.snow > R4(0.00)) { s.wat = s.wat + s.snow; s.snow = R4(0.00); }
-          if (cpl_lastobs > c.TLimMeltIce && s.ice > R4(0.00)) { s.wat = s.wat + s.ice; s.ice = R4(0.00); }
-          if (cpl_lastobs > c.TLimMeltIce && s.ice2 > R4(0.00)) s.ice2 = R4(0.00);
-          if (cpl_lastobs > c.TLimMeltDep && s.dep > R4(0.00)) { s.wat = s.wat + s.dep; s.dep = R4(0.00); }
-        }
+        if (cp.in_phase) snow_ice_check(c, cpl_lastobs, s);
       }
       if (FULL) {
-        /* SetCurrentValues obs forcing, src/InputOutput.f90:116-148 */
+        /* (obs_forced, spelled out: see rs_general_body.inc) */
         if ((i <= initlen || c.force_tsurf) && f.tsurfobs > R4(-100.0) &&
             (!CPL || !cpl_on || i < cpl_cs)) {
           T.set(1, f.tsurfobs);
@@ -576,11 +516,10 @@ __device__ __forceinline__ void time_loop(const MathTab &mt, Prof &T, Scalars &s
           const double depth = (c.tsurfOutputDepth >= R4(0.0)) ? c.tsurfOutputDepth : f.depth;
           s.tsurf = surface_temperature(c, T, tbot, depth);
         }
-        /* RelaxationOperations, src/Relaxation.f90:10-47 */
         if (relax) {
           if (i == initlen) { /* the anchors: once per point */
             double tairR, vzR, rhR;
-            relax_targets(tairR, vzR, rhR);
+            relax_targets(ka, row0, lane, tairR, vzR, rhR);
             relax_dt = tairR - tair;
             relax_dv = vzR - vz;
             relax_dr = rhR - rhz;
@@ -590,66 +529,27 @@ __device__ __forceinline__ void time_loop(const MathTab &mt, Prof &T, Scalars &s
             st[(int64_t)RS_ST_VZ_END * np + p] = vz;
             st[(int64_t)RS_ST_RH_END * np + p] = rhz;
           }
-          if (i > initlen) {
-            /* exp(-(DT*i - DT*InitLenI)/14400): for an integral time step the argument is a function
-             * of i - InitLenI alone and the plan holds the table (rs_consts_dev.h, host libm = the
-             * bits rs_exp returns); otherwise evaluated here */
-            double e;
-            const uint32_t d = (uint32_t)(i - initlen);
-            if (c.relax_tab && d <= (uint32_t)c.SimLen) {
-              e = ((const double *)c.relax_tab)[d];
-            } else {
-              const double den = (double)(4.f * 3600.f);
-              e = rs_exp(mt, rs_div(-((c.DTSecs * i) - (c.DTSecs * initlen)), den));
-            }
-            tair = tair - relax_dt * e;
-            vz = vz - relax_dv * e;
-            rhz = rhz - relax_dr * e;
-            if (rhz > R4(100.)) rhz = R4(100.0);
-          }
+          if (i > initlen) relax_apply(relax_factor(c, mt, i, initlen), relax_dt, relax_dv, relax_dr, tair, vz, rhz);
         }
       }
     } else {
       /* lastValues, src/InputOutput.f90:169-198: no checks, no obs forcing, no
        * relaxation; the pre-step surface temperature uses depth(SimLen) only */
       if (FULL) s.tsurf = surface_temperature(c, T, tbot, f.depth);
-      /* coupling%inCouplingPhase and SW/LWRadCof keep their last values: those of index SimLen-1 */
-      if (CPL && cpl_on) {
-        const int32_t j = c.SimLen - 1;
-        cp.in_phase = (j >= cpl_cs && j <= cpl_ce);
-        if (j > cpl_ce) {
-          const double e = cpl_decay(c, mt, j, cpl_ce);
-          cp.sw_cof = R4(1.0) + cpl_swcorr * e;
-          cp.lw_cof = R4(1.0) + cpl_lwcorr * e;
-        } else if (j >= cpl_cs) { /* the window reaches the end of the series: as the last pass left them */
-          cp.sw_cof = ka->state[(int64_t)RS_ST_CPL_SWCOF * ka->np_pad + row0 + lane];
-          cp.lw_cof = ka->state[(int64_t)RS_ST_CPL_LWCOF * ka->np_pad + row0 + lane];
-        }
-      }
+      if (CPL && cpl_on) cpl_last_values(c, mt, cw, cpl_swcorr, cpl_lwcorr, ka->state, ka->np_pad, row0 + lane, cp);
     }
     if (CPL) cp.last_tsurf_obs = cpl_lastobs;
     double sw_in = f.sw, lw_in = f.lw;
     if (SKY && sky_on) {
       /* the reference runs this between PrecipitationToStorage and BalanceModelOneStep
        * (Simulation.f90:151-162); the two do not share data, so the order is free */
-      if (!sky_view_radiation(ka->f.sun + (int64_t)k * RS_SUN_COLS, sinlat, coslat, lonrad, coslon, sinlon, skyv,
-                              ka->pp.albedo_surroundings,
-                              ka->pp.horizons ? ka->pp.horizons + (ka->pp.horizons_by_point ? (int64_t)hcol * 360 : (int64_t)hcol) : nullptr,
-                              ka->pp.horizons_by_point ? (int64_t)1 : ka->np_pad,
-                              sw_in, sw_dir, lw_in, lw_net))
+      int64_t hstride;
+      const double *hrow = horizon_row(ka, sky.hcol, hstride);
+      if (!sky_view_radiation(ka->f.sun + (int64_t)k * RS_SUN_COLS, sky.sinlat, sky.coslat, sky.lonrad, sky.coslon,
+                              sky.sinlon, sky.skyv, ka->pp.albedo_surroundings, hrow, hstride, sw_in, sw_dir, lw_in, lw_net))
         fail_at(i); /* the reference would `stop` the process here */
     }
-    if (SKY && ka->wb.sw_dir) {
-      /* the caller's arrays as the reference leaves them: SW_dir clamped by CheckValues
-       * (src/InputOutput.f90:75-77), SW / SW_dir / LW edited by ModRadiationBySurroundings
-       * (src/ModRadiation.f90:57-71) */
-      const int64_t wrow = (int64_t)k * ka->wb.t_stride + row0;
-      (ka->wb.sw_dir + wrow)[lane] = sw_dir;
-      if (sky_on) {
-        (ka->wb.sw + wrow)[lane] = sw_in;
-        (ka->wb.lw + wrow)[lane] = lw_in;
-      }
-    }
+    if (SKY) sky_write_back(ka, k, row0, sky_on, sw_dir, sw_in, lw_in, [&](double *base, double v) { base[lane] = v; });
     if (DIAG) /* (instances of their own, step_kernel_lds<., true> and step_kernel_sky<true>: see bl_diagnose) */
       bl_diagnose(&c, mt.expT, mt.logT, mt.K, s.tsurf, tair, vz, rhz, f.hour, i, ka->diag, ka->np_pad, row0 + lane);
     const Fluxes fx =
@@ -677,29 +577,8 @@ __device__ __forceinline__ void time_loop(const MathTab &mt, Prof &T, Scalars &s
     }
     if (owrite) store_outputs<CPL, A32>(ka, orow, row0, lane, s, true);
     if (!CPL && s.failed) blank_rows(i + 1); /* failed at this index: its own row is saved, the rest is not */
-    if (CPL && cpl_on && i < c.SimLen && i == cpl_ce) {
-      /* CheckEndCoupling + CouplingOperations2, src/Coupling.f90:98-141 (Coupling_failed is
-       * .false. before the first decision) */
-      double *st = ka->state;
-      const int64_t np = ka->np_pad, p = row0 + lane;
-      Coupling q;
-      load_coupling(st, np, p, q);
-      q.cs = cpl_cs; q.ce = cpl_ce; q.on = true;
-      if (!q.failed) {
-        if (q.iter == 0) q.tend1 = s.tsurf;
-        coupling_control(q, s.tsurf);
-        q.iter = q.iter + 1;
-        /* a point that failed CheckValues at this very index still ran Coupling_control
-         * (CheckEndCoupling does not look at simulation_failed), but its loop exits before any rewind:
-         * it must not park - the rows behind its window stay -9999.0 - and must not be listed */
-        if (s.failed) q.again = false;
-        store_coupling(st, np, p, q);
-        cpl_swcorr = q.swcorr;
-        cpl_lwcorr = q.lwcorr;
-        cpl_lastobs = q.lastobs; /* went to Kelvin and back in Coupling_control */
-        parked = q.again; /* replays its window in the rounds; RS_ST_CPL_RESUME = i + 1 */
-      }
-    }
+    if (CPL && cpl_on && i < c.SimLen && i == cpl_ce)
+      cpl_window_end(ka->state, ka->np_pad, row0 + lane, cw, s, cpl_swcorr, cpl_lwcorr, cpl_lastobs, parked);
   }
   if (CPL) ka->state[(int64_t)RS_ST_CPL_RESUME * ka->np_pad + row0 + lane] = (double)next_i;
 }
@@ -955,37 +834,22 @@ __device__ __forceinline__ void duo_surface(const MathTab &mt, DuoMailT<FULL ? P
     T.set(1, all.get(1));
     T.set(2, all.get(2));
   }
-  double skyv = R4(1.0), sinlat = 0, coslat = 0, lonrad = 0, coslon = 1.0, sinlon = 0;
-  bool sky_on = false;
-  uint32_t hcol = 0;
-  if (SKY && live) { /* as time_loop<SKY> */
-    skyv = ka->pp.sky_view[p];
-    sky_on = (skyv < R4(1.0) && skyv > R4(-0.01));
-    if (sky_on) {
-      sinlat = ka->pp.sin_lat[p];
-      coslat = ka->pp.cos_lat[p];
-      lonrad = ka->pp.lon_rad[p];
-      coslon = ::cos(lonrad);
-      sinlon = ::sin(lonrad);
-    }
-    hcol = ka->pp.horizon_index ? (uint32_t)ka->pp.horizon_index[p] : (uint32_t)p;
-  }
+  SkyPoint sky;
+  if (SKY && live) sky = sky_point(ka, p);
+  const bool sky_on = sky.on;
   const int32_t nsteps = ka->nsteps, t0 = ka->t0;
-  /* coupling, lock-step part (time_loop<CPL>): what a lane needs every step in registers, the rest of
-   * CouplingVariables in the state block, touched at the two events only */
-  bool cpl_on = false, parked = false;
-  int32_t cpl_cs = -99, cpl_ce = -99, next_i = t0;
+  /* coupling, lock-step part: what a lane needs every step in registers, the rest of CouplingVariables in the
+   * state block, touched at the two events only */
+  CplWindow cw;
+  if (CPL && live) cpl_window(ka, consts_of(ka), p, 0u, cw);
+  const bool cpl_on = cw.on;
+  const int32_t cpl_cs = cw.cs, cpl_ce = cw.ce;
+  bool parked = false;
+  int32_t next_i = t0;
   double cpl_lastobs = 0.0, cpl_swcorr = 0.0, cpl_lwcorr = 0.0;
   if (CPL && live) {
     const double *st = a.state;
     const int64_t np = a.np_pad;
-    const int32_t cidx = ka->pp.coupling_index ? ka->pp.coupling_index[p] : 0;
-    /* setInputParam + initCouplingTimes, src/InputOutput.f90:30-36, src/Coupling.f90:486-534 */
-    cpl_on = consts_of(ka).use_coupling && ka->pp.coupling_index && !(ka->pp.coupling_tsurf[p] < -100 || cidx < 1);
-    if (cpl_on) {
-      cpl_ce = cidx;
-      cpl_cs = ((double)cidx <= consts_of(ka).cplLenR) ? 1 : cidx - consts_of(ka).cplLenI;
-    }
     cpl_lastobs = st[(int64_t)RS_ST_CPL_LASTOBS * np + p];
     cpl_swcorr = st[(int64_t)RS_ST_CPL_SWCORR * np + p];
     cpl_lwcorr = st[(int64_t)RS_ST_CPL_LWCORR * np + p];
@@ -1002,7 +866,13 @@ __device__ __forceinline__ void duo_surface(const MathTab &mt, DuoMailT<FULL ? P
   /* arrives failed (or a dead lane): frozen from the first index; CPL: or not due for it */
   mail.failed[ml] = (s.failed || (CPL && (parked || t0 != next_i))) ? 1u : 0u;
   duo_meet();
-  auto blank_rows = [&](int32_t i_from) { /* as in time_loop */
+  /* the index still steps (the ground wave is in it already); the next does not */
+  auto fail_at = [&](int32_t idx) {
+    s.failed = true;
+    ka->state[(int64_t)RS_ST_FAILED * ka->np_pad + row0 + lane] = (double)idx;
+    mail.failed[ml] = 1u;
+  };
+  auto blank_rows = [&](int32_t i_from) {
     for (int32_t ii = i_from; ii < t0 + nsteps; ++ii) {
       int64_t r;
       if (output_row<false>(ka, ii, r)) {
@@ -1054,95 +924,47 @@ __device__ __forceinline__ void duo_surface(const MathTab &mt, DuoMailT<FULL ? P
         /* REPLAY, at the rewind: the index CheckValues has just seen is the one behind the window end - with
          * the surface temperature of the end of the window */
         const bool rewind = REPLAY && i == cpl_cs;
-        if ((rewind ? q.bad_rw : q.bad) | check_values_tsurf(c, s.tsurf)) {
-          s.failed = true;
-          ka->state[(int64_t)RS_ST_FAILED * ka->np_pad + row0 + lane] = (double)(rewind ? cpl_ce + 1 : i);
-          mail.failed[ml] = 1u; /* this index still steps (the ground wave is in it already); the next does not */
-        }
+        if ((rewind ? q.bad_rw : q.bad) | check_values_tsurf(c, s.tsurf)) fail_at(rewind ? cpl_ce + 1 : i);
       }
-      if (SKYG && q.stop) { /* as duo_surface<SKY> flags it: at any index */
-        s.failed = true;
-        ka->state[(int64_t)RS_ST_FAILED * ka->np_pad + row0 + lane] = (double)i;
-        mail.failed[ml] = 1u;
-      }
+      if (SKYG && q.stop) fail_at(i); /* the sky wave's sky_view_radiation: at any index */
       s.tnw1 = T.get(1);
       s.tnw2 = T.get(2);
       CouplingInputs cp;
-      if (CPL && cpl_on) { /* CouplingOperations1, src/Coupling.f90:10-96, first pass of the window: time_loop<CPL> */
+      if (CPL && cpl_on) { /* CouplingOperations1, src/Coupling.f90:10-96, first pass of the window */
         if (i < c.SimLen) {
           cp.in_phase = (i >= cpl_cs && i <= cpl_ce);
           if (REPLAY && i == cpl_cs) {
             /* inCouplingPhase is set from the loop index BEFORE a rewind takes it back (:22-27 against :61-66):
-             * the step at the window start of a replay runs outside the coupling phase.  uploadDataForCoupling
-             * :213-255: SrfIcemms, Q2Melt, T4Melt and TmpNw are NOT restored - s.tnw1/2 above hold the
-             * end-of-window values CalcHCapHCond sees in this step (the ground wave does the same for 3..N) */
+             * the step at the window start of a replay runs outside the coupling phase.  TmpNw is not restored:
+             * s.tnw1/2 above hold the end-of-window values CalcHCapHCond sees in this step (the ground wave does
+             * the same for 3..N) */
             cp.in_phase = false;
             double *st = ka->state;
             const int64_t np = ka->np_pad, pp_ = row0 + lane;
-            s.tsurf = st[(int64_t)RS_ST_CPL_SAVE_TSURF * np + pp_];
-            s.wat = st[(int64_t)RS_ST_CPL_SAVE_WAT * np + pp_];
-            s.ice2 = st[(int64_t)RS_ST_CPL_SAVE_ICE2 * np + pp_];
-            s.dep = st[(int64_t)RS_ST_CPL_SAVE_DEP * np + pp_];
-            s.snow = st[(int64_t)RS_ST_CPL_SAVE_SNOW * np + pp_];
-            s.albedo = st[(int64_t)RS_ST_CPL_SAVE_ALBEDO * np + pp_];
-            const int32_t fl = (int32_t)st[(int64_t)RS_ST_CPL_FLAGS * np + pp_];
-            s.verycold = (fl & 4) != 0;
-            st[(int64_t)RS_ST_CPL_FLAGS * np + pp_] = (double)(fl & ~1); /* start_coupling_again = .false. */
+            cpl_restore_surface<true>(st, np, pp_, s);
             T.set(1, st[(int64_t)(RS_ST_CPL_SAVE_TMP0 + 0) * np + pp_]);
             T.set(2, st[(int64_t)(RS_ST_CPL_SAVE_TMP0 + 1) * np + pp_]);
             t3 = st[(int64_t)(RS_ST_CPL_SAVE_TMP0 + 2) * np + pp_]; /* layer 2's lower boundary: the restored Tmp(3) */
-            /* short-wave scaling by day, long-wave by night (:68-76; no sky view in this instance) */
-            const double radcoeff = st[(int64_t)RS_ST_CPL_RADCOEFF * np + pp_];
-            if (q.sw > q.lw) {
-              r_swcof = radcoeff;
-              r_lwcof = R4(1.0);
-            } else {
-              r_swcof = R4(1.0);
-              r_lwcof = radcoeff;
-            }
+            /* (no sky view in this instance) */
+            cpl_rewind_coefs(st[(int64_t)RS_ST_CPL_RADCOEFF * np + pp_], q.sw, q.lw, false, r_swcof, r_lwcof);
             st[(int64_t)RS_ST_CPL_SWCOF * np + pp_] = r_swcof; /* Coupling_control reads them at the end */
             st[(int64_t)RS_ST_CPL_LWCOF * np + pp_] = r_lwcof;
           }
-          if (!REPLAY && i == cpl_cs) { /* saveDataForCoupling :172-210 - this wave's share (the ground wave saves layers 3..N) */
+          if (!REPLAY && i == cpl_cs) { /* this wave's share (the ground wave saves layers 3..N) */
             double *st = ka->state;
             const int64_t np = ka->np_pad, pp_ = row0 + lane;
-            st[(int64_t)RS_ST_CPL_SAVE_TSURF * np + pp_] = s.tsurf;
-            st[(int64_t)RS_ST_CPL_SAVE_WAT * np + pp_] = s.wat;
-            st[(int64_t)RS_ST_CPL_SAVE_ICE2 * np + pp_] = s.ice2;
-            st[(int64_t)RS_ST_CPL_SAVE_DEP * np + pp_] = s.dep;
-            st[(int64_t)RS_ST_CPL_SAVE_SNOW * np + pp_] = s.snow;
-            st[(int64_t)RS_ST_CPL_SAVE_ALBEDO * np + pp_] = s.albedo;
-            const int32_t fl = ((int32_t)st[(int64_t)RS_ST_CPL_FLAGS * np + pp_]) & (3 | RS_CPL_MSG_SMALL | RS_CPL_MSG_BIG);
-            st[(int64_t)RS_ST_CPL_FLAGS * np + pp_] = (double)(fl | (s.verycold ? 4 : 0));
+            cpl_save_surface(st, np, pp_, s);
             st[(int64_t)(RS_ST_CPL_SAVE_TMP0 + 0) * np + pp_] = T.get(1);
             st[(int64_t)(RS_ST_CPL_SAVE_TMP0 + 1) * np + pp_] = T.get(2);
           }
-          if (i > cpl_ce) {
-            const double e = cpl_decay(c, mt, i, cpl_ce);
-            cp.sw_cof = R4(1.0) + cpl_swcorr * e;
-            cp.lw_cof = R4(1.0) + cpl_lwcorr * e;
-          }
+          if (i > cpl_ce) cpl_decayed_coefs(c, mt, i, cpl_ce, cpl_swcorr, cpl_lwcorr, cp.sw_cof, cp.lw_cof);
           if (REPLAY && i >= cpl_cs && i <= cpl_ce) {
             cp.sw_cof = r_swcof;
             cp.lw_cof = r_lwcof;
           }
-          if (cp.in_phase) { /* snowIceCheck :259-289 */
-            if (cpl_lastobs > c.TLimMeltSnow && s.snow > R4(0.00)) { s.wat = s.wat + s.snow; s.snow = R4(0.00); }
-            if (cpl_lastobs > c.TLimMeltIce && s.ice > R4(0.00)) { s.wat = s.wat + s.ice; s.ice = R4(0.00); }
-            if (cpl_lastobs > c.TLimMeltIce && s.ice2 > R4(0.00)) s.ice2 = R4(0.00);
-            if (cpl_lastobs > c.TLimMeltDep && s.dep > R4(0.00)) { s.wat = s.wat + s.dep; s.dep = R4(0.00); }
-          }
-        } else { /* lastValues: inCouplingPhase and the coefficients keep the values of index SimLen - 1 */
-          const int32_t j = c.SimLen - 1;
-          cp.in_phase = (j >= cpl_cs && j <= cpl_ce);
-          if (j > cpl_ce) {
-            const double e = cpl_decay(c, mt, j, cpl_ce);
-            cp.sw_cof = R4(1.0) + cpl_swcorr * e;
-            cp.lw_cof = R4(1.0) + cpl_lwcorr * e;
-          } else if (j >= cpl_cs) {
-            cp.sw_cof = ka->state[(int64_t)RS_ST_CPL_SWCOF * ka->np_pad + row0 + lane];
-            cp.lw_cof = ka->state[(int64_t)RS_ST_CPL_LWCOF * ka->np_pad + row0 + lane];
-          }
+          if (cp.in_phase) snow_ice_check(c, cpl_lastobs, s);
+        } else {
+          cpl_last_values(c, mt, cw, cpl_swcorr, cpl_lwcorr, ka->state, ka->np_pad, row0 + lane, cp);
         }
       }
       if (CPL) cp.last_tsurf_obs = cpl_lastobs;
@@ -1168,31 +990,18 @@ __device__ __forceinline__ void duo_surface(const MathTab &mt, DuoMailT<FULL ? P
         const LaneOff L(lane);
         double sw_dir = L.ld(ka->f.sw_dir + row), lw_net = L.ld(ka->f.lw_net + row);
         if (i < c.SimLen) {
-          if (sky_on && (sw_dir < R4(-0.1) || sw_dir > R4(4000.0) || lw_net < R4(-1000.0) || lw_net > R4(1000.0))) {
-            s.failed = true; /* src/InputOutput.f90:68-74 */
-            ka->state[(int64_t)RS_ST_FAILED * ka->np_pad + row0 + lane] = (double)i;
-            mail.failed[ml] = 1u;
-          }
-          if (sw_dir > q.sw) sw_dir = q.sw; /* :75-77 */
+          if (sky_on && sky_limits_bad(sw_dir, lw_net)) fail_at(i);
+          sw_dir = sky_clamp_direct(sw_dir, q.sw);
         }
         if (sky_on) {
-          if (!sky_view_radiation(ka->f.sun + (int64_t)k * RS_SUN_COLS, sinlat, coslat, lonrad, coslon, sinlon, skyv,
-                                  ka->pp.albedo_surroundings,
-                                  ka->pp.horizons ? ka->pp.horizons + (ka->pp.horizons_by_point ? (int64_t)hcol * 360 : (int64_t)hcol) : nullptr,
-                                  ka->pp.horizons_by_point ? (int64_t)1 : ka->np_pad, qs.sw, sw_dir, qs.lw, lw_net)) {
-            s.failed = true; /* the reference would `stop` the process here */
-            ka->state[(int64_t)RS_ST_FAILED * ka->np_pad + row0 + lane] = (double)i;
-            mail.failed[ml] = 1u;
-          }
+          int64_t hstride;
+          const double *hrow = horizon_row(ka, sky.hcol, hstride);
+          if (!sky_view_radiation(ka->f.sun + (int64_t)k * RS_SUN_COLS, sky.sinlat, sky.coslat, sky.lonrad, sky.coslon,
+                                  sky.sinlon, sky.skyv, ka->pp.albedo_surroundings, hrow, hstride, qs.sw, sw_dir, qs.lw,
+                                  lw_net))
+            fail_at(i); /* the reference would `stop` the process here */
         }
-        if (ka->wb.sw_dir) { /* the caller's arrays as the reference leaves them (time_loop<SKY>) */
-          const int64_t wrow = (int64_t)k * ka->wb.t_stride + row0;
-          L.st(ka->wb.sw_dir + wrow, sw_dir);
-          if (sky_on) {
-            L.st(ka->wb.sw + wrow, qs.sw);
-            L.st(ka->wb.lw + wrow, qs.lw);
-          }
-        }
+        sky_write_back(ka, k, row0, sky_on, sw_dir, qs.sw, qs.lw, [&](double *base, double v) { L.st(base, v); });
       }
       const Fluxes fx = model_step_fluxes_prepped<SCORE ? 1 : 2>(c, mt, s, qs, cp);
       if (SCORE) {
@@ -1210,25 +1019,8 @@ __device__ __forceinline__ void duo_surface(const MathTab &mt, DuoMailT<FULL ? P
       /* (REPLAY: a point that fails in the middle of a replay keeps, up to its window end, what the earlier
        * passes saved there: src/InputOutput.f90:151-165 only ever overwrites) */
       if (s.failed) blank_rows(REPLAY && cpl_ce + 1 > i + 1 ? cpl_ce + 1 : i + 1);
-      if (CPL && cpl_on && i < c.SimLen && i == cpl_ce) {
-        /* CheckEndCoupling + CouplingOperations2, src/Coupling.f90:98-141: as time_loop<CPL> */
-        double *st = ka->state;
-        const int64_t np = ka->np_pad, pp_ = row0 + lane;
-        Coupling cq;
-        load_coupling(st, np, pp_, cq);
-        cq.cs = cpl_cs; cq.ce = cpl_ce; cq.on = true;
-        if (!cq.failed) {
-          if (cq.iter == 0) cq.tend1 = s.tsurf;
-          coupling_control(cq, s.tsurf);
-          cq.iter = cq.iter + 1;
-          if (s.failed) cq.again = false; /* its loop exits before any rewind: not parked, not listed */
-          store_coupling(st, np, pp_, cq);
-          cpl_swcorr = cq.swcorr;
-          cpl_lwcorr = cq.lwcorr;
-          cpl_lastobs = cq.lastobs;
-          parked = cq.again;
-        }
-      }
+      if (CPL && cpl_on && i < c.SimLen && i == cpl_ce)
+        cpl_window_end(ka->state, ka->np_pad, row0 + lane, cw, s, cpl_swcorr, cpl_lwcorr, cpl_lastobs, parked);
     }
     /* CPL: frozen at the NEXT index? (failed, parked, or not due for it) */
     if (CPL) mail.failed[ml] = (s.failed || parked || (i + 1) != next_i) ? 1u : 0u;
@@ -1831,21 +1623,9 @@ __device__ __forceinline__ void duo_sky(DuoMailT<PR_FULL> &mail, uint32_t *skyfl
   const int64_t row0 = a.wave_start ? (int64_t)a.wave_start[blockIdx.x] : (int64_t)blockIdx.x * 64;
   const int64_t p = row0 + lane;
   const bool live = a.wave_start ? (int32_t)lane < a.wave_cnt[blockIdx.x] : p < a.npoints;
-  double skyv = R4(1.0), sinlat = 0, coslat = 0, lonrad = 0, coslon = 1.0, sinlon = 0;
-  bool sky_on = false;
-  uint32_t hcol = 0;
-  if (live) { /* as time_loop<SKY> sets the point up */
-    skyv = ka->pp.sky_view[p];
-    sky_on = (skyv < R4(1.0) && skyv > R4(-0.01));
-    if (sky_on) {
-      sinlat = ka->pp.sin_lat[p];
-      coslat = ka->pp.cos_lat[p];
-      lonrad = ka->pp.lon_rad[p];
-      coslon = ::cos(lonrad);
-      sinlon = ::sin(lonrad);
-    }
-    hcol = ka->pp.horizon_index ? (uint32_t)ka->pp.horizon_index[p] : (uint32_t)p;
-  }
+  SkyPoint sky;
+  if (live) sky = sky_point(ka, p);
+  const bool sky_on = sky.on;
   const int64_t rcol = live ? (ka->raw.col ? (int64_t)ka->raw.col[p] : p) : 0;
   RawLerp<4> R;
   R.seg = ka->raw.seg0;
@@ -1860,15 +1640,15 @@ __device__ __forceinline__ void duo_sky(DuoMailT<PR_FULL> &mail, uint32_t *skyfl
     if (in < c.SimLen) {
       /* check_values_forcing's tests of SW and LW (the ground wave runs the others with 0 in their place) */
       bad = (sw < c.chk[1]) | (lw < c.chk[1]) | (sw > c.chk[5]) | (lw > c.chk[6]);
-      if (sky_on && (sw_dir < R4(-0.1) || sw_dir > R4(4000.0) || lw_net < R4(-1000.0) || lw_net > R4(1000.0)))
-        bad = true; /* src/InputOutput.f90:68-74 */
-      if (sw_dir > sw) sw_dir = sw; /* :75-77 */
+      if (sky_on && sky_limits_bad(sw_dir, lw_net)) bad = true;
+      sw_dir = sky_clamp_direct(sw_dir, sw);
     }
     if (sky_on) {
       const double *sunrow = ka->f.sun + (int64_t)(in - t0) * RS_SUN_COLS;
-      if (!sky_view_radiation(sunrow, sinlat, coslat, lonrad, coslon, sinlon, skyv, ka->pp.albedo_surroundings,
-                              ka->pp.horizons ? ka->pp.horizons + (ka->pp.horizons_by_point ? (int64_t)hcol * 360 : (int64_t)hcol) : nullptr,
-                              ka->pp.horizons_by_point ? (int64_t)1 : ka->np_pad, sw, sw_dir, lw, lw_net))
+      int64_t hstride;
+      const double *hrow = horizon_row(ka, sky.hcol, hstride);
+      if (!sky_view_radiation(sunrow, sky.sinlat, sky.coslat, sky.lonrad, sky.coslon, sky.sinlon, sky.skyv,
+                              ka->pp.albedo_surroundings, hrow, hstride, sw, sw_dir, lw, lw_net))
         stop = true; /* the reference would `stop` the process here: the point is failed at this index, checked or not */
     }
     mail.prep[buf][PR_SW][lane] = sw;
@@ -2219,6 +1999,7 @@ __global__ void __launch_bounds__(kBlock) cpl_window_bounds_kernel(const StepArg
   if (p >= a.npoints) return;
   const ConstsAS &c = consts_of(&a);
   if ((((int32_t)a.state[(int64_t)RS_ST_CPL_FLAGS * a.np_pad + p]) & 1) == 0) return;
+  /* (cpl_window's rule, kept in this form: see there) */
   const int32_t cidx = a.pp.coupling_index[p];
   if (a.pp.coupling_tsurf[p] < -100 || cidx < 1) return;
   const int32_t cs = ((double)cidx <= c.cplLenR) ? 1 : cidx - c.cplLenI;

@@ -66,6 +66,7 @@
 #define RS_PROFILE_PIN 0                 /* RegProfile::pin is empty */
 #define RS_CPL_SLOTS(c) ((c).use_coupling) /* the coupling slots of the state block exist for a coupled plan only */
 #define RS_CPL_DECAY_TABLE 0             /* the coupling decay by the hardware exponential, no table */
+#define RS_RELAX_TABLE 0
 #define RS_GEN_PREFETCH 0                /* the general loop loads an index's forcing where it uses it */
 #define RS_GEN_FP64_FEATURES 0           /* no diagnostics, write-back or cpl_stop park: refused on an fp32 plan */
 #define RS_INIT_KERNEL init_kernel_f32   /* the name of the kernel that makes the initial state */
@@ -699,7 +700,7 @@ __device__ __forceinline__ void x2d_ground(X2Mail &mail, const rs::StepArgs &a) 
     kk_c = __builtin_amdgcn_readfirstlane((t0 - 1) / kspk);
     kr_c = (t0 - 1) - kk_c * kspk;
   }
-  /* FULL: as the fp64 flavours set a point up (time_loop, duo_ground) */
+  /* FULL: relax_targets / relax_valid and the differences target - anchor, in f2 form (rs_general_body.inc) */
   i2 initlen = i2{0, 0};
   b2 relax = b2{false, false};
   f2 relax_dt = S2(0.f), relax_dv = S2(0.f), relax_dr = S2(0.f), tairR = S2(0.f), vzR = S2(0.f), rhR = S2(0.f);
@@ -720,7 +721,7 @@ __device__ __forceinline__ void x2d_ground(X2Mail &mail, const rs::StepArgs &a) 
       relax_dr = rhR - *reinterpret_cast<const f2 *>(st + (int64_t)RS_ST_RH_END * np + p);
     }
   }
-  /* SKY: as the fp64 flavours set a point up (rs_kernels.hip time_loop<SKY>) */
+  /* SKY: sky_point's set-up for the two components (spelled out here: rs_general_body.inc says why) */
   double skyv[2] = {1.0, 1.0}, sinlat[2] = {0, 0}, coslat[2] = {0, 0}, lonrad[2] = {0, 0}, coslon[2] = {1.0, 1.0}, sinlon[2] = {0, 0};
   bool sky_on[2] = {false, false};
   int64_t hcol[2] = {p, p + 1};

@@ -42,6 +42,7 @@
 #define RS_PROFILE_PIN 1                /* RegProfile::pin holds the new profile in place (see there) */
 #define RS_CPL_SLOTS(c) true            /* the coupling slots of the state block are written and read by every plan */
 #define RS_CPL_DECAY_TABLE 1            /* the coupling decay from the plan's table (RsConstantsDev::cpl_tab) */
+#define RS_RELAX_TABLE 1                /* the relaxation factor likewise (RsConstantsDev::relax_tab) */
 #define RS_GEN_PREFETCH 1               /* the general loop fetches the next index's forcing half a step early */
 #define RS_GEN_FP64_FEATURES 1          /* diagnostics, write-back of the in-place input edits, the cpl_stop park */
 #define RS_INIT_KERNEL init_kernel      /* the name of the kernel that makes the initial state */

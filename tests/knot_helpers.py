@@ -184,6 +184,42 @@ def run_knots(K: dict, settings, params, locals_, *, precision: int = 64, chunks
     return res
 
 
+# ---- the flavours a hand-made knot block is sent through ------------------------------------------------------
+# (entry, ...): "knots" / "window" - run_knots with that source, natural order; "points" - device.run_points with
+# (variant, lean_if_possible, chunked).  Launches of FLAVOUR_CHUNK indices where chunked.  Which step-kernel
+# instance each of them takes at 15 layers is pinned by tests/test_step_selection.py; the module docstring of
+# tests/test_hip_storage_waves.py names them.
+FLAVOUR_CHUNK = 60
+FLAVOURS = [("knots",), ("window",)] + [("points", v, lean, chunked) for v in (1, 2, 3, 4) for lean in (True, False)
+                                        for chunked in (False, True)]
+FLAVOURS_F32 = [("knots",), ("window",), ("points", 0, True, True), ("points", 0, False, True)]
+
+
+def flavour_id(fl) -> str:
+    if fl[0] != "points":
+        return fl[0]
+    return f"variant{fl[1]}_{'lean' if fl[2] else 'full'}_{'chunks' if fl[3] else 'whole'}"
+
+
+def run_flavour(fl, K: dict, f: dict, settings, params, locals_, *, start_hour: int, precision: int = 64):
+    """The knot block K (and its numpy expansion f, for the entries that take a forcing window from the host) through
+    one flavour: (outputs [n][SimLen], first failed index [n] - the plan's own for run_knots, read from the blank
+    rows for run_points, whose count of failed points must agree with them)."""
+    if fl[0] in ("knots", "window"):
+        res = run_knots(K, settings, params, locals_, precision=precision, chunks=FLAVOUR_CHUNK, order="natural",
+                        start_hour=start_hour, source=fl[0])
+        assert res["moved"] == 0
+        return res["out"], np.asarray(res["first_failed"], np.int32)
+    from roadsurf_amd import device
+    _, variant, lean, chunked = fl
+    got, nfail = device.run_points(f, settings, params, locals_, chunk=FLAVOUR_CHUNK if chunked else 0,
+                                   variant=variant, lean_if_possible=lean, precision=precision, device=0)
+    got = {k: got[k] for k in OUT}
+    failed = first_blank(got)
+    assert nfail == int((failed > 0).sum()), (nfail, failed.nonzero())
+    return got, failed
+
+
 # ---- host restatements (tests/test_knot_reference.py, the fp32 expansion reference) ---------------------------
 
 def rn(x: Fraction) -> float:

@@ -141,6 +141,22 @@ def test_one_point_per_lane_kernel_equals_the_oracle(references, case):
     _compare(case, got, ora, "one point per lane")
 
 
+OTHER_FLAVOURS = [fl for fl in kh.FLAVOURS if fl not in (("knots",), ("points", 1, True, True))]  # (the two above)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("fl", OTHER_FLAVOURS, ids=kh.flavour_id)
+def test_every_other_flavour_equals_the_oracle(references, fl):
+    """The same cases through the flavours of knot_helpers.FLAVOURS that the two tests above do not reach: the
+    window-reading two-wavefront launch, and run_points with every variant, LEAN and FULL, whole and in launches."""
+    for case in CASES:
+        K, f, ora, failed = references[case]
+        got, first_failed = kh.run_flavour(fl, K, f, abi.default_settings(L), params_of(case), _local(),
+                                           start_hour=start_hour_of(case))
+        assert np.array_equal(first_failed, failed), (case, first_failed.nonzero(), failed.nonzero())
+        _compare(case, got, ora, kh.flavour_id(fl))
+
+
 # ---- what the cases contain: the loop restated in numpy (no GPU) --------------------------------------------------
 
 def stab_safe(p):

@@ -123,6 +123,21 @@ def test_one_point_per_lane_kernel_equals_the_oracle(references, case):
     _compare(case, got, ora, "one point per lane")
 
 
+OTHER_FLAVOURS = [fl for fl in kh.FLAVOURS if fl not in (("knots",), ("points", 1, True, True))]  # (the two above)
+
+
+@pytest.mark.parametrize("fl", OTHER_FLAVOURS, ids=kh.flavour_id)
+def test_every_other_flavour_equals_the_oracle(references, fl):
+    """The same cases through the flavours of knot_helpers.FLAVOURS that the two tests above do not reach: the
+    window-reading two-wavefront launch, and run_points with every variant, LEAN and FULL, whole and in launches."""
+    for case in CASES:
+        K, f, ora, failed = references[case]
+        got, first_failed = kh.run_flavour(fl, K, f, abi.default_settings(L), abi.default_parameters(), _local(),
+                                           start_hour=9)
+        assert np.array_equal(first_failed, failed), (case, first_failed.nonzero(), failed.nonzero())
+        _compare(case, got, ora, kh.flavour_id(fl))
+
+
 def test_the_cases_are_what_they_claim(references):
     """What the oracle's own outputs say about the cases: dry roads stay dry, the condensing one gathers deposit,
     the wet lane alone differs from its dry twin, the margin case has wavefronts on both sides of the margin."""

@@ -924,6 +924,76 @@ int rs_hip_outputs_episodes(RsPlan *plan, const RsOutputs *src, const void *defi
                             double *acc_device, void *stream);
 int rs_hip_episodes_finish(RsPlan *plan, const RsEpisodeSpec *spec, double *acc_device, void *stream);
 
+/* Per-station probabilities of a road condition over the ensemble members, reduced from the member rows on the device
+ * (the ABI number stays: every name here is new, a binding detects them with rs_hip_prob_cols).  The number an ensemble
+ * is run for is the share of a station's members on which a condition holds - "Tsurf below 0 and water on the road",
+ * "ice present", "dew-point deficit below 0" - now, and by now: the monotone curve "probability of ice by 06:00".  A
+ * CONDITION is the condition of the episodes above, a conjunction of strict bounds on the RS_EPI_VARS variables Tsurf,
+ * Snow, Water, Ice, Deposit, Ice2 and the dew-point deficit:
+ *   use               bit k set: variable k is tested, and passes iff above[k] < x and x < below[k] - both strict,
+ *                     -inf / +inf make a bound one-sided, a NaN compares false; every bound is compared in fp64
+ * and a row of a member HOLDS under it by the episodes' rule: its Tsurf is not exactly -9999.0, every used variable
+ * passes and - if the deficit is used - the deficit is not exactly -9999.0.  A spec holds nconds in 1..RS_PROB_MAX_CONDS
+ * conditions; it is refused if ngroups < 1, max_members is outside 1..RS_ENS_MAX_MEMBERS, or a condition's use is 0 or
+ * has a bit at RS_EPI_VARS or above, or a bound is NaN.  The members of a station are given by the table of
+ * rs_ens_member_table for the same ngroups and max_members (an RsEnsSpec without quantiles): the same table serves
+ * both reducers.  rs_hip_outputs_prob reads the first `nrows` rows of a window `src` ([row][slot], of any launch and
+ * any flavour; float arrays on an fp32 plan, widened exactly) and WRITES
+ *     acc_device[((acc_row0 + r) * ngroups + g) * cols + col],   double,   cols = rs_hip_prob_cols = 1 + 2 * nconds
+ *   0                the number of VALID members of g at row r (Tsurf not exactly -9999.0)
+ *   1 + c            NOW: the number of members whose row r holds under condition c
+ *   1 + nconds + c   BY_NOW: the number of members that are valid at r and for which condition c has held at r or at
+ *                    any row fed earlier since the carry was reset - so every count is at or below column 0, and a
+ *                    member that failed after the condition held leaves numerator and denominator together
+ * Every cell is a count, exact in fp64; the probabilities are the counts over column 0, one division of the consumer's.
+ * The carry is ever_device[npoints_padded], int32 in POINT order (re-sorts between the calls do not matter): bit c set
+ * means that condition c has held at a fed row of the point; an invalid row sets nothing.  rs_hip_prob_reset writes
+ * zero into all npoints_padded entries; rs_hip_outputs_prob reads and updates the entries of the points [0, npoints)
+ * only.  Columns 0 and NOW do not depend on the order of feeding; BY_NOW does: the calls of a pass feed consecutive
+ * rows in time order - cut anywhere, the result is that of one call - and rows fed out of order give the curve of the
+ * order fed (documented, not detected).  A cell is complete in one call, as for rs_hip_outputs_ens: every station's
+ * cell of every fed row is written, the empty one (all zeros) included, rows outside [acc_row0, acc_row0 + nrows) are
+ * not touched, and a station whose members are spread over several plans is not supported.  The definition, in numpy:
+ * roadsurf_amd/ensprob.py (reduce_members_prob); the tests hold the device to it exactly.
+ * `deficit_device` holds the deficit of the same rows in the layout and type of the window, [row][slot] with
+ * src->t_stride; it is required iff rs_hip_prob_needs_deficit, and the call is refused without it then.
+ * `order_device` and `stream` as for rs_hip_outputs_summary: NULL = the plan's current order, on the plan's stream; a
+ * stream of the caller's only with a kept order row.  `work_device`: int32[work_ints] of the caller's, at least
+ * rs_hip_prob_work_ints(plan, nrows) = npoints_padded * (1 + nrows); the call fills it on the same stream - the inverse
+ * of the order row it resolved, then one word per row and slot - and leaves its contents unspecified.  No state is
+ * hidden in the plan, so calls on different streams (with scratch each) cannot race.  Refused, with nothing launched:
+ * null arguments or nrows < 1; a bad spec; rows outside acc_rows; a missing deficit; missing or short scratch; a missing
+ * stream of the six; t_stride below the plan's points; a stream of the caller's without a kept order row.  A table
+ * that rs_ens_member_table did not make, or an order row that is no permutation, may give unspecified cells and carry
+ * for the stations and points it touches, never an access outside the table, the window, the carry, the scratch or the
+ * accumulator: the kernels read the table's ngroups + 1 + npoints ints and the window's columns [0, npoints) only, clamp
+ * a segment to max_members and to the table, and an entry or an inverse outside [0, npoints) contributes nothing.
+ * Two kernels, no atomics: BY_NOW is sequential per member, so one lane owns a slot and walks the call's rows in time
+ * order (whole lines, several rows in flight, as the episodes' feed), writing per row one word - bits 0..7 holds now,
+ * bits 8..15 counted by now, bit 16 valid - and the carry once; then a workgroup takes 64 consecutive stations,
+ * resolves their members to slots once as rs_hip_outputs_ens does, and lane g counts the bits of station g's words.
+ * It reads 48 B per member and row (56 B with the deficit, half of that from an fp32 window) and writes and reads 4 B;
+ * tools/bench_ensemble_prob.py measures the cost (its output is kept as profiles/ensemble_prob.txt). */
+#define RS_PROB_MAX_CONDS 8
+typedef struct RsProbCond {
+  int32_t use, reserved;      /* bit k: variable k is tested (Tsurf, Snow, Water, Ice, Deposit, Ice2, deficit) */
+  double above[RS_EPI_VARS];  /* variable k passes iff above[k] < x ... */
+  double below[RS_EPI_VARS];  /* ... and x < below[k] */
+} RsProbCond;
+typedef struct RsProbSpec {
+  int32_t ngroups, max_members, nconds, reserved;
+  RsProbCond cond[RS_PROB_MAX_CONDS];
+} RsProbSpec;
+int32_t rs_hip_prob_cols(const RsProbSpec *spec);          /* 1 + 2 * nconds; <0: bad spec (host only) */
+int32_t rs_hip_prob_needs_deficit(const RsProbSpec *spec); /* 1 iff some condition uses bit 6; <0: bad spec */
+int64_t rs_hip_prob_spec_bytes(void);                      /* sizeof(RsProbSpec): the binding's size check */
+int64_t rs_hip_prob_work_ints(const RsPlan *plan, int32_t nrows); /* int32s of scratch one call over nrows rows needs; <0: no plan or nrows < 1 */
+int rs_hip_prob_reset(RsPlan *plan, int32_t *ever_device, void *stream); /* zero into all npoints_padded entries */
+int rs_hip_outputs_prob(RsPlan *plan, const RsOutputs *src, const void *deficit_device, int32_t nrows,
+                        const int32_t *table_device, const int32_t *order_device, const RsProbSpec *spec,
+                        int32_t *ever_device, double *acc_device, int64_t acc_rows, int64_t acc_row0,
+                        int32_t *work_device, int64_t work_ints, void *stream);
+
 /* Gridded fields gathered to points on the device (the ABI number stays: every name here is new, a binding detects
  * them with rs_hip_grid_max_stencil).  A weather model delivers fields [time][node]; every kernel here reads series
  * [time][point].  Each point has a stencil of `stencil` nodes, node_device[point * stencil + k] (int32) with weights

@@ -652,6 +652,51 @@ int rs_hip_episodes_finish(RsPlan *pl, const RsEpisodeSpec *spec, double *acc, v
   return 0;
 }
 
+int32_t rs_hip_prob_cols(const RsProbSpec *spec) { return rs_cluster_prob_cols(spec); }
+int32_t rs_hip_prob_needs_deficit(const RsProbSpec *spec) { return rs_cluster_prob_needs_deficit(spec); }
+int64_t rs_hip_prob_spec_bytes(void) { return (int64_t)sizeof(RsProbSpec); }
+
+/* the inverse of the order row [npoints_padded], then one word per row and slot [nrows][npoints_padded] */
+int64_t rs_hip_prob_work_ints(const RsPlan *pl, int32_t nrows) {
+  if (!pl || nrows < 1) return -1;
+  return pl->np_pad * ((int64_t)1 + nrows);
+}
+
+int rs_hip_prob_reset(RsPlan *pl, int32_t *ever, void *stream) {
+  if (!pl || !ever) return set_err("rs_hip_prob_reset: bad arguments");
+  HIP_OK(hipSetDevice(pl->device));
+  HIP_OK(hipMemsetAsync(ever, 0, (size_t)pl->np_pad * sizeof(int32_t), stream_of(pl, stream)));
+  return 0;
+}
+
+int rs_hip_outputs_prob(RsPlan *pl, const RsOutputs *src, const void *deficit, int32_t nrows, const int32_t *table,
+                        const int32_t *order, const RsProbSpec *spec, int32_t *ever, double *acc, int64_t acc_rows,
+                        int64_t acc_row0, int32_t *work, int64_t work_ints, void *stream) {
+  if (!pl || !src || !table || !spec || !ever || !acc || nrows < 1)
+    return set_err("rs_hip_outputs_prob: bad arguments (nrows >= 1 rows, a member table, a spec, a carry and an accumulator)");
+  const int32_t cols = rs_cluster_prob_cols(spec);
+  if (cols < 0)
+    return set_err("rs_hip_outputs_prob: bad spec (ngroups >= 1, 1 <= max_members <= RS_ENS_MAX_MEMBERS, 1 .. "
+                   "RS_PROB_MAX_CONDS conditions; use: bits 0..6, at least one; no NaN bound)");
+  if (acc_row0 < 0 || acc_rows < 1 || acc_row0 > acc_rows - nrows)
+    return set_err("rs_hip_outputs_prob: rows [acc_row0, acc_row0 + nrows) outside the accumulator's acc_rows");
+  if (!deficit && rs_cluster_prob_needs_deficit(spec) == 1)
+    return set_err("rs_hip_outputs_prob: this spec uses the deficit (bit 6): deficit_device is required");
+  if (!work) return set_err("rs_hip_outputs_prob: work_device is required (int32[rs_hip_prob_work_ints] of the caller's)");
+  if (work_ints < rs_hip_prob_work_ints(pl, nrows))
+    return set_err("rs_hip_outputs_prob: work_ints = %lld is below rs_hip_prob_work_ints = %lld", (long long)work_ints,
+                   (long long)rs_hip_prob_work_ints(pl, nrows));
+  RowsOn on;
+  if (rows_prologue(pl, src, order, stream, "rs_hip_outputs_prob", on)) return -1;
+  /* where every point sits in the order row the window was stepped in; a point the row does not name has no slot */
+  HIP_OK(hipMemsetAsync(work, 0xff, (size_t)pl->npoints * sizeof(int32_t), on.stream));
+  HIP_OK(rs_cluster_inverse(on.order, pl->npoints, work, on.stream));
+  HIP_OK(rs_cluster_outputs_prob(on.in, deficit, pl->f32, on.order, table, work, pl->npoints, src->t_stride, nrows, *spec,
+                                 ever, reinterpret_cast<uint32_t *>(work + pl->np_pad), pl->np_pad,
+                                 acc + acc_row0 * spec->ngroups * cols, on.stream));
+  return 0;
+}
+
 int32_t rs_hip_grid_max_stencil(void) { return RS_GRID_MAX_STENCIL; }
 
 int rs_hip_gather_nodes(RsPlan *pl, const double *src, int32_t nrows, int64_t n_nodes, int64_t src_stride,

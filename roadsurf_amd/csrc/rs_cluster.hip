@@ -966,6 +966,234 @@ hipError_t rs_cluster_outputs_ens(const void *const src[6], bool f32, const int3
   return hipGetLastError();
 }
 
+/* Per-station probabilities of conditions over the members (include/roadsurf.h, rs_hip_outputs_prob; the definition is
+ * roadsurf_amd/ensprob.py, reduce_members_prob): the fourth reducer over the slots of a row, and the first that is also
+ * sequential over the rows - "has held by now" is a member's history, a station's cell runs over its members.  Two
+ * kernels therefore.  prob_bits_kernel is the episodes' feed with a smaller automaton: one lane owns a slot, reads the
+ * carry of its point once, walks the call's rows in time order with PROB_ROWS rows of all streams in flight (every row
+ * load a coalesced 512 B per wavefront and stream, 256 B of an fp32 window), stores per row one word at [row][slot] -
+ * bits 0..7 holds now per condition, bits 8..15 valid and held by now, bit 16 valid - and the carry once.  The
+ * conditions are kernel arguments, tested in loops that unroll over constants under wave-uniform branches: no bound is
+ * indexed per lane.  prob_count_kernel takes 64 consecutive stations per workgroup, resolves their segment of the member
+ * list ONCE to slots in LDS exactly as ens_stats_kernel does (clamped counts, their scan, -1 for an entry or an inverse
+ * outside [0, npoints)), and then lane g walks station g's words of a row - each wavefront rows of its own - and counts
+ * their bits into registers.  The words are 4 B against the 48 B the first kernel read for them, and the members of a
+ * station sit in a few lines that stay in the caches from one member position to the next, so the walk is not staged
+ * through LDS as the statistics' doubles are.  No atomics; every offset is 64 bits. */
+int32_t rs_cluster_prob_cols(const RsProbSpec *sp) {
+  if (!sp || sp->ngroups < 1 || sp->max_members < 1 || sp->max_members > RS_ENS_MAX_MEMBERS || sp->nconds < 1 ||
+      sp->nconds > RS_PROB_MAX_CONDS)
+    return -1;
+  for (int32_t c = 0; c < sp->nconds; ++c) {
+    const RsProbCond &k = sp->cond[c];
+    if (k.use <= 0 || (k.use >> RS_EPI_VARS) != 0) return -1;
+    for (int v = 0; v < RS_EPI_VARS; ++v)
+      if (k.above[v] != k.above[v] || k.below[v] != k.below[v]) return -1;
+  }
+  return 1 + 2 * sp->nconds;
+}
+
+int32_t rs_cluster_prob_needs_deficit(const RsProbSpec *sp) {
+  if (rs_cluster_prob_cols(sp) < 0) return -1;
+  for (int32_t c = 0; c < sp->nconds; ++c)
+    if ((sp->cond[c].use >> 6) & 1) return 1;
+  return 0;
+}
+
+namespace {
+constexpr int PROB_ROWS = 4;  /* rows of all streams a lane of prob_bits_kernel has in flight */
+constexpr int PROB_WAVES = 4; /* wavefronts of prob_count_kernel's workgroup: rows in flight */
+constexpr int PROB_WORDS = 4; /* words a lane of prob_count_kernel has in flight */
+
+struct ProbBitsArgs {
+  const void *src[RS_EPI_VARS]; /* T[nrows][stride] each: Tsurf, Snow, Water, Ice, Deposit, Ice2, deficit (or NULL) */
+  const int32_t *order;         /* column s is point order[s] */
+  int32_t *ever;                /* [np_pad], point order: bit c = condition c has held */
+  uint32_t *words;              /* [nrows][wstride] */
+  int64_t npoints, stride, wstride;
+  int32_t nrows, nconds;
+  RsProbCond cond[RS_PROB_MAX_CONDS];
+};
+
+template <typename T>
+__global__ void __launch_bounds__(RS_BLOCK) prob_bits_kernel(const ProbBitsArgs a) {
+  const int64_t s = (int64_t)blockIdx.x * RS_BLOCK + threadIdx.x;
+  if (s >= a.npoints) return;
+  const int64_t p = a.order ? (int64_t)a.order[s] : s;
+  const bool own = p >= 0 && p < a.npoints; /* not an order row of this plan: no carry is read or written */
+  uint32_t ever = own ? (uint32_t)a.ever[p] : 0u;
+  const bool with_deficit = a.src[6] != nullptr;
+#pragma unroll 1
+  for (int32_t r0 = 0; r0 < a.nrows; r0 += PROB_ROWS) {
+    T x[PROB_ROWS][RS_EPI_VARS];
+#pragma unroll
+    for (int q = 0; q < PROB_ROWS; ++q) {
+      const int32_t r = r0 + q < a.nrows ? r0 + q : a.nrows - 1; /* behind the range: its last row again, not taken */
+#pragma unroll
+      for (int f = 0; f < 6; ++f) x[q][f] = static_cast<const T *>(a.src[f])[(int64_t)r * a.stride + s];
+      x[q][6] = with_deficit ? static_cast<const T *>(a.src[6])[(int64_t)r * a.stride + s] : (T)0;
+    }
+#pragma unroll
+    for (int q = 0; q < PROB_ROWS; ++q) {
+      if (r0 + q >= a.nrows) break;
+      const double v[RS_EPI_VARS] = {(double)x[q][0], (double)x[q][1], (double)x[q][2], (double)x[q][3],
+                                     (double)x[q][4], (double)x[q][5], (double)x[q][6]};
+      const bool valid = v[0] != -9999.0; /* never saved: behind the last index of a failed point, or a rejected point */
+      uint32_t now = 0;
+#pragma unroll
+      for (int c = 0; c < RS_PROB_MAX_CONDS; ++c) {
+        if (c >= a.nconds) break;
+        const int32_t use = a.cond[c].use;
+        bool ok = valid;
+#pragma unroll
+        for (int k = 0; k < RS_EPI_VARS; ++k)
+          if ((use >> k) & 1) ok = ok && a.cond[c].above[k] < v[k] && v[k] < a.cond[c].below[k];
+        if ((use >> 6) & 1) ok = ok && v[6] != -9999.0; /* no deficit there (roadsurf_amd/kept.py) */
+        now |= (ok ? 1u : 0u) << c;
+      }
+      ever |= now;
+      a.words[(int64_t)(r0 + q) * a.wstride + s] = valid ? (now | ((ever & 0xffu) << 8) | (1u << 16)) : 0u;
+    }
+  }
+  if (own) a.ever[p] = (int32_t)ever;
+}
+
+struct ProbCountArgs {
+  const uint32_t *words; /* [nrows][wstride] */
+  const int32_t *table;  /* [ngroups + 1] starts, [npoints] entries (rs_ens_table.hpp) */
+  const int32_t *inv;    /* [npoints]: the slot of a point */
+  double *acc;           /* [nrows][ngroups][cols]: row acc_row0 of the caller's accumulator */
+  int64_t npoints, wstride;
+  int32_t nrows, ngroups, max_members, nconds, cols, rows_per_block;
+};
+
+__global__ void __launch_bounds__(64 * PROB_WAVES) prob_count_kernel(const ProbCountArgs a) {
+  extern __shared__ int32_t prob_slot[]; /* [64 * max_members]: the slot of every entry of the workgroup's segment */
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t g = (int64_t)blockIdx.x * 64 + lane;
+  const bool live = g < a.ngroups;
+  /* the station's segment of the member list, clamped to max_members and to the list */
+  int32_t first = 0, cnt = 0;
+  if (live) {
+    const int64_t s0 = a.table[g], s1 = a.table[g + 1];
+    if (s0 >= 0 && s0 < a.npoints && s1 > s0) {
+      int64_t c = s1 - s0;
+      if (c > a.max_members) c = a.max_members;
+      if (c > a.npoints - s0) c = a.npoints - s0;
+      first = (int32_t)s0;
+      cnt = (int32_t)c;
+    }
+  }
+  /* where the station's entries begin in the workgroup's segment: the scan of the clamped counts */
+  int32_t incl = cnt;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int32_t u = __shfl_up(incl, d, 64);
+    if (lane >= d) incl += u;
+  }
+  const int32_t off = incl - cnt; /* off + cnt <= 64 * max_members */
+  /* entries to slots, once: wavefront w resolves the member positions w, w + PROB_WAVES, ... of every station */
+  const int32_t *entry = a.table + ((int64_t)a.ngroups + 1);
+  for (int32_t j = wave; j < cnt; j += PROB_WAVES) {
+    const int64_t p = entry[(int64_t)first + j];
+    int32_t s = -1;
+    if (p >= 0 && p < a.npoints) {
+      const int64_t q = a.inv[p];
+      if (q >= 0 && q < a.npoints) s = (int32_t)q;
+    }
+    prob_slot[off + j] = s;
+  }
+  __syncthreads();
+
+  const int32_t r_lo = (int32_t)blockIdx.y * a.rows_per_block,
+                r_hi = a.nrows - r_lo < a.rows_per_block ? a.nrows : r_lo + a.rows_per_block;
+  const int32_t *mine = prob_slot + off;
+#pragma unroll 1
+  for (int32_t r = r_lo + wave; r < r_hi; r += PROB_WAVES) {
+    const uint32_t *w = a.words + (int64_t)r * a.wstride;
+    int32_t nvalid = 0, now[RS_PROB_MAX_CONDS], by[RS_PROB_MAX_CONDS];
+#pragma unroll
+    for (int c = 0; c < RS_PROB_MAX_CONDS; ++c) now[c] = by[c] = 0;
+    for (int32_t j0 = 0; j0 < cnt; j0 += PROB_WORDS) {
+      uint32_t x[PROB_WORDS];
+#pragma unroll
+      for (int q = 0; q < PROB_WORDS; ++q) {
+        const int32_t s = j0 + q < cnt ? mine[j0 + q] : -1;
+        x[q] = s >= 0 ? w[s] : 0u; /* no such member: invalid, and under no condition */
+      }
+#pragma unroll
+      for (int q = 0; q < PROB_WORDS; ++q) {
+        nvalid += (int32_t)((x[q] >> 16) & 1u);
+#pragma unroll
+        for (int c = 0; c < RS_PROB_MAX_CONDS; ++c) {
+          if (c >= a.nconds) break;
+          now[c] += (int32_t)((x[q] >> c) & 1u);
+          by[c] += (int32_t)((x[q] >> (8 + c)) & 1u);
+        }
+      }
+    }
+    if (live) {
+      double *cell = a.acc + ((int64_t)r * a.ngroups + g) * a.cols;
+      cell[0] = (double)nvalid;
+#pragma unroll
+      for (int c = 0; c < RS_PROB_MAX_CONDS; ++c) {
+        if (c >= a.nconds) break;
+        cell[1 + c] = (double)now[c];
+        cell[1 + a.nconds + c] = (double)by[c];
+      }
+    }
+  }
+}
+}  // namespace
+
+hipError_t rs_cluster_outputs_prob(const void *const src[6], const void *deficit, bool f32, const int32_t *order,
+                                   const int32_t *table, const int32_t *inv, int64_t npoints, int64_t src_stride,
+                                   int32_t nrows, const RsProbSpec &spec, int32_t *ever, uint32_t *words,
+                                   int64_t wstride, double *acc_row0, hipStream_t stream) {
+  const int32_t cols = rs_cluster_prob_cols(&spec);
+  if (cols < 0 || nrows < 1 || npoints < 1 || wstride < npoints) return hipErrorInvalidValue;
+  ProbBitsArgs b;
+  for (int f = 0; f < 6; ++f) b.src[f] = src[f];
+  b.src[6] = rs_cluster_prob_needs_deficit(&spec) == 1 ? deficit : nullptr;
+  b.order = order;
+  b.ever = ever;
+  b.words = words;
+  b.npoints = npoints;
+  b.stride = src_stride;
+  b.wstride = wstride;
+  b.nrows = nrows;
+  b.nconds = spec.nconds;
+  for (int c = 0; c < RS_PROB_MAX_CONDS; ++c) b.cond[c] = spec.cond[c < spec.nconds ? c : 0];
+  if (f32)
+    hipLaunchKernelGGL(prob_bits_kernel<float>, grid1(npoints), dim3(RS_BLOCK), 0, stream, b);
+  else
+    hipLaunchKernelGGL(prob_bits_kernel<double>, grid1(npoints), dim3(RS_BLOCK), 0, stream, b);
+  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  ProbCountArgs a;
+  a.words = words;
+  a.table = table;
+  a.inv = inv;
+  a.acc = acc_row0;
+  a.npoints = npoints;
+  a.wstride = wstride;
+  a.nrows = nrows;
+  a.ngroups = spec.ngroups;
+  a.max_members = spec.max_members;
+  a.nconds = spec.nconds;
+  a.cols = cols;
+  /* the grid of the ensemble statistics: the stations give x, blocks of rows y, several rounds of what the chip holds
+   * at once, each workgroup with a whole number of rows per wavefront */
+  const int64_t station_blocks = ((int64_t)spec.ngroups + 63) / 64;
+  const int64_t want_row_blocks = std::max<int64_t>(1, 6144 / station_blocks);
+  const int64_t rows_each = std::max<int64_t>(1, ((int64_t)nrows + want_row_blocks - 1) / want_row_blocks);
+  a.rows_per_block = (int32_t)std::min<int64_t>(INT32_MAX / 2, (rows_each + PROB_WAVES - 1) / PROB_WAVES * PROB_WAVES);
+  const int64_t row_blocks = ((int64_t)nrows + a.rows_per_block - 1) / a.rows_per_block;
+  const dim3 grid((unsigned)station_blocks, (unsigned)row_blocks);
+  const size_t lds = (size_t)64 * spec.max_members * sizeof(int32_t);
+  hipLaunchKernelGGL(prob_count_kernel, grid, dim3(64 * PROB_WAVES), lds, stream, a);
+  return hipGetLastError();
+}
+
 hipError_t rs_cluster_identity(int32_t *order, int64_t np_pad, hipStream_t stream) {
   hipLaunchKernelGGL(iota_kernel, grid1(np_pad), dim3(RS_BLOCK), 0, stream, order, np_pad);
   return hipGetLastError();

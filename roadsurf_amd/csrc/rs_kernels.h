@@ -207,6 +207,16 @@ hipError_t rs_cluster_outputs_episodes(const void *const src[6], const void *def
                                        hipStream_t stream);
 hipError_t rs_cluster_episodes_finish(double *acc, int64_t npoints, int64_t np_pad, const RsEpisodeSpec &spec,
                                       hipStream_t stream);
+/* per-station probabilities of conditions over the members (rs_hip_outputs_prob): acc_row0[nrows][ngroups][cols] is
+ * WRITTEN; src, deficit and order as for the episodes, table and inv as for the ensemble statistics; ever[np_pad] the
+ * carry in point order; words[nrows][wstride >= npoints]: one word per row and slot, filled by the first kernel and read
+ * by the second.  rs_cluster_prob_cols checks the spec (<0: bad), rs_cluster_prob_needs_deficit: 1 iff bit 6 is used */
+int32_t rs_cluster_prob_cols(const RsProbSpec *spec);
+int32_t rs_cluster_prob_needs_deficit(const RsProbSpec *spec);
+hipError_t rs_cluster_outputs_prob(const void *const src[6], const void *deficit, bool f32, const int32_t *order,
+                                   const int32_t *table, const int32_t *inv, int64_t npoints, int64_t src_stride,
+                                   int32_t nrows, const RsProbSpec &spec, int32_t *ever, uint32_t *words,
+                                   int64_t wstride, double *acc_row0, hipStream_t stream);
 /* gridded fields gathered to points (rs_grid.hip, rs_hip_gather_nodes): dst[r][slot] for r < nrows, slot < npoints;
  * node / weight [point][stencil]; order NULL = column s is point s */
 hipError_t rs_grid_gather(const double *src, int32_t nrows, int64_t n_nodes, int64_t src_stride, const int32_t *node,

@@ -452,7 +452,9 @@ class Plan:
         """The member table of ``group`` - int32 [npoints] on the HOST (numpy or a CPU tensor), every point's station
         in POINT order - built by the library (rs_ens_member_table; roadsurf_amd/ensstats.py, member_table, defines
         it) and uploaded: int32 [ngroups + 1 + npoints] on this device, what ``outputs_ens`` reads.  A station with
-        more than ``spec.max_members`` members is refused.  Also makes the plan's work row for ``outputs_ens``."""
+        more than ``spec.max_members`` members is refused.  Also makes the plan's work row for ``outputs_ens``.
+        ``spec``: an ensstats.EnsSpec, or an ensprob.ProbSpec - ``ngroups`` and ``max_members`` alone make the table,
+        which serves ``outputs_prob`` too."""
         import numpy as np
         sp, _ = self._ens_spec(spec)
         if torch.is_tensor(group):
@@ -499,6 +501,77 @@ class Plan:
             raise RuntimeError("this libroadsurf_hip.so has no ensemble statistics (rs_hip_ens_cols)")
         a = acc.cpu().numpy()
         assert spec is None or a.shape[1:] == (int(spec.ngroups), lib.ens_cols(spec))
+        return a
+
+    def _prob_spec(self, spec):
+        if not hasattr(self.L, "rs_hip_prob_cols"):
+            raise RuntimeError("this libroadsurf_hip.so has no probabilities over the members (rs_hip_prob_cols)")
+        sp = lib.prob_spec(spec)
+        return sp, lib.prob_cols(sp)
+
+    def prob_work_ints(self, nrows: int) -> int:
+        """int32s of scratch one ``outputs_prob`` over ``nrows`` rows needs (rs_hip_prob_work_ints)."""
+        if not hasattr(self.L, "rs_hip_prob_cols"):
+            raise RuntimeError("this libroadsurf_hip.so has no probabilities over the members (rs_hip_prob_cols)")
+        n = int(self.L.rs_hip_prob_work_ints(self._h, int(nrows)))
+        if n < 0:
+            raise ValueError("prob_work_ints: nrows >= 1")
+        return n
+
+    def prob_reset(self, ever: torch.Tensor | None = None, stream: torch.cuda.Stream | None = None) -> torch.Tensor:
+        """Zero into every entry of the carry ``ever``, int32 [np_pad] on this device in POINT order (made here if
+        None) - what ``outputs_prob`` reads and updates (rs_hip_prob_reset): no condition has held yet."""
+        if not hasattr(self.L, "rs_hip_prob_cols"):
+            raise RuntimeError("this libroadsurf_hip.so has no probabilities over the members (rs_hip_prob_cols)")
+        if ever is None:
+            ever = torch.empty((self.np_pad,), dtype=torch.int32, device=self.device)
+        assert ever.dtype == torch.int32 and ever.shape == (self.np_pad,) and ever.is_contiguous()
+        lib.check(self.L.rs_hip_prob_reset(self._h, C.c_void_p(ever.data_ptr()), _stream_ptr(stream)),
+                  "rs_hip_prob_reset")
+        return ever
+
+    def outputs_prob(self, out: "OutputWindow", nrows: int, table: torch.Tensor, spec, ever: torch.Tensor,
+                     acc: torch.Tensor, acc_row0: int, deficit: torch.Tensor | None = None, order=None,
+                     stream: torch.cuda.Stream | None = None, row: int = 0, work: torch.Tensor | None = None) -> None:
+        """Rows ``row .. row + nrows - 1`` of the output window, [row][slot], fed IN ORDER: per station the members
+        under each condition now and by now, WRITTEN to rows ``acc_row0 ..`` of ``acc`` [rows, ngroups, cols], and the
+        carry ``ever`` [np_pad] updated (rs_hip_outputs_prob; roadsurf_amd/ensprob.py defines the cells).  ``table``:
+        what ``ens_table`` returned for the same stations; ``spec``: ensprob.ProbSpec; ``deficit`` as for
+        ``outputs_episodes``, required iff a condition tests it; ``order`` and ``stream`` as for
+        ``outputs_by_point``.  ``work``: int32 scratch on this device of at least ``prob_work_ints(nrows)`` entries,
+        default the plan's own, grown as needed - a call on a stream of the caller's needs its own."""
+        sp, cols = self._prob_spec(spec)
+        assert acc.dtype == torch.float64 and acc.dim() == 3 and acc.is_contiguous()
+        assert acc.shape[1:] == (int(sp.ngroups), cols)
+        assert table.dtype == torch.int32 and table.is_contiguous()
+        assert table.numel() >= int(sp.ngroups) + 1 + self.npoints
+        assert ever.dtype == torch.int32 and ever.numel() >= self.np_pad and ever.is_contiguous()
+        if work is None:
+            if stream is not None:
+                raise ValueError("outputs_prob: a call on a stream of the caller's needs a work of the caller's")
+            need = self.prob_work_ints(nrows)
+            if getattr(self, "_prob_work", None) is None or self._prob_work.numel() < need:
+                self._prob_work = torch.empty((need,), dtype=torch.int32, device=self.device)
+            work = self._prob_work
+        assert work.dtype == torch.int32 and work.dim() == 1 and work.is_contiguous()
+        o = out.struct_from(row)
+        d = None
+        if deficit is not None:
+            assert deficit.dtype == out.tensors["tsurf"].dtype and deficit.dim() == 2 and deficit.stride(1) == 1
+            assert deficit.stride(0) == out.t_stride and deficit.shape[0] >= row + nrows
+            d = C.c_void_p(deficit[row].data_ptr())
+        lib.check(self.L.rs_hip_outputs_prob(self._h, C.byref(o), d, int(nrows), C.c_void_p(table.data_ptr()),
+                                             _ptr(order), C.byref(sp), C.c_void_p(ever.data_ptr()),
+                                             C.c_void_p(acc.data_ptr()), int(acc.shape[0]), int(acc_row0),
+                                             C.c_void_p(work.data_ptr()), int(work.numel()), _stream_ptr(stream)),
+                  "rs_hip_outputs_prob")
+
+    def prob(self, acc: torch.Tensor, spec=None):
+        """``acc`` as the numpy array [rows, ngroups, cols] that ensprob.reduce_members_prob returns (synchronises)."""
+        if not hasattr(self.L, "rs_hip_prob_cols"):
+            raise RuntimeError("this libroadsurf_hip.so has no probabilities over the members (rs_hip_prob_cols)")
+        a = acc.cpu().numpy()
+        assert spec is None or a.shape[1:] == (int(spec.ngroups), lib.prob_cols(spec))
         return a
 
     def gather_nodes(self, src: torch.Tensor, node: torch.Tensor, weight: torch.Tensor, dst: torch.Tensor,
@@ -587,7 +660,7 @@ class Plan:
 def run_points(forcing: dict, settings: abi.InputSettings, params: abi.InputParameters,
                local, chunk: int = 0, variant: int = 0, device: int = 0,
                lean_if_possible: bool = True, year_month_day=None, history_score: bool | None = None,
-               precision: int = 64, horizon_index=None, summary=None, groups=None, episodes=None):
+               precision: int = 64, horizon_index=None, summary=None, groups=None, episodes=None, probs=None):
     """Run host arrays ``forcing[name][n, SimLen]`` (numpy, reference layout) through the
     device-resident API and return outputs ``[n, SimLen]`` as numpy.  Test/bench helper:
     transposes with torch on the device, windows of ``chunk`` steps (0 = whole series).
@@ -598,8 +671,10 @@ def run_points(forcing: dict, settings: abi.InputSettings, params: abi.InputPara
     has ``groups`` [SimLen, ngroups, cols], row r being time index r + 1; not with coupling either.
     ``episodes``: an episodes.EpisodeSpec that does not need the deficit - every launch's rows are also fed to the
     per-point episodes (``Plan.outputs_episodes``) and the result has ``episodes`` [n, cols], finished; not with
-    coupling either."""
-    from . import legs  # (legs imports this module when a Leg is made)
+    coupling either.  ``probs``: (ensprob.ProbSpec that does not need the deficit, stations int32 [n]) - every
+    launch's rows are also counted per station and condition (``Plan.outputs_prob``) and the result has ``probs``
+    [SimLen, ngroups, cols], row r being time index r + 1; not with coupling either."""
+    from . import ensprob, legs  # (legs imports this module when a Leg is made)
 
     require_gpu()
     n, L = forcing["tair"].shape
@@ -607,15 +682,17 @@ def run_points(forcing: dict, settings: abi.InputSettings, params: abi.InputPara
     if isinstance(local, abi.LocalParameters):
         local = [local] * n
     coupled = settings.use_coupling == 1
-    for name, spec in (("summary", summary), ("groups", groups), ("episodes", episodes)):
+    for name, spec in (("summary", summary), ("groups", groups), ("episodes", episodes), ("probs", probs)):
         if spec is not None and coupled:  # (the reducers are for the launches of an uncoupled run)
             raise ValueError(f"run_points: no {name} with coupling")
+    if probs is not None and ensprob.needs_deficit(probs[0]):
+        raise ValueError("run_points: probs: a condition uses the deficit, and the runner has no deficit rows")
     if year_month_day is None:
         year_month_day = (int(forcing["year"][0]), int(forcing["month"][0]), int(forcing["day"][0]))
     need_full, sky_on = legs.feature_set(settings, local, [forcing], lean_if_possible)
     leg = legs.Leg(forcing, settings, params, local, need_full=need_full, sky_on=sky_on, tbottom_date=year_month_day,
                    precision=precision, variant=variant, history_score=history_score, horizon_index=horizon_index,
-                   device=device, summary=summary, groups=groups, episodes=episodes)
+                   device=device, summary=summary, groups=groups, episodes=episodes, probs=probs)
     leg.init()
     leg.run(legs.coupling_stages(settings, local, L, chunked=bool(chunk)), chunk)
     res = leg.results()

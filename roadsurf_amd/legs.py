@@ -84,11 +84,12 @@ class Leg:
     ``recluster``: ``Plan.recluster()`` behind every launch.  ``horizon_index``: point i reads column
     ``horizon_index[i]`` of ``local_horizons`` (not with ``recluster``, which derives its own from the plan order).
     The reducers run behind every launch but a replay: ``summary`` (a SummarySpec) and ``episodes`` (an EpisodeSpec)
-    by absolute time index, ``groups`` (GroupSpec, ids [n]) and ``stats`` (EnsSpec, stations [n]) by row."""
+    by absolute time index, ``groups`` (GroupSpec, ids [n]) and ``stats`` (EnsSpec, stations [n]) by row, and
+    ``probs`` (ProbSpec without the deficit, stations [n]) by row and in row order, its carry reset once."""
 
     def __init__(self, forcing, settings, params, local, *, need_full, tbottom_date, sky_on=False, first=1,
                  precision=64, variant=0, history_score=None, recluster=False, horizon_index=None, device=0,
-                 summary=None, groups=None, episodes=None, stats=None):
+                 summary=None, groups=None, episodes=None, stats=None, probs=None):
         import torch
         from . import device as dv
         assert not (recluster and horizon_index is not None)
@@ -180,6 +181,13 @@ class Leg:
             tacc = torch.empty((nrows, int(tspec.ngroups), lib.ens_cols(tspec)), dtype=torch.float64, device=dev)
             self.reducers.append(("stats", lambda out, ns, t0, row: plan.outputs_ens(
                 out, ns, table, tspec, tacc, t0 - first, row=row), lambda: plan.ens(tacc, tspec)))
+        if probs is not None:  # (cells are written, so no reset of them; the carry is reset once, here)
+            pspec = probs[0]
+            ptable = plan.ens_table(np.ascontiguousarray(probs[1], dtype=np.int32), pspec)
+            pever = plan.prob_reset()
+            pacc = torch.empty((nrows, int(pspec.ngroups), lib.prob_cols(pspec)), dtype=torch.float64, device=dev)
+            self.reducers.append(("probs", lambda out, ns, t0, row: plan.outputs_prob(
+                out, ns, ptable, pspec, pever, pacc, t0 - first, row=row), lambda: plan.prob(pacc, pspec)))
 
     def _window(self, tens, hour, sun, nrows):
         tens = dict(tens, hour=hour)

@@ -123,6 +123,19 @@ class RsEpisodeSpec(C.Structure):
                 ("above", C.c_double * RS_EPI_VARS), ("below", C.c_double * RS_EPI_VARS)]
 
 
+RS_PROB_MAX_CONDS = 8
+
+
+class RsProbCond(C.Structure):
+    _fields_ = [("use", C.c_int32), ("reserved", C.c_int32),
+                ("above", C.c_double * RS_EPI_VARS), ("below", C.c_double * RS_EPI_VARS)]
+
+
+class RsProbSpec(C.Structure):
+    _fields_ = [("ngroups", C.c_int32), ("max_members", C.c_int32), ("nconds", C.c_int32), ("reserved", C.c_int32),
+                ("cond", RsProbCond * RS_PROB_MAX_CONDS)]
+
+
 class RsSynthSpec(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("point_offset", C.c_int64),
                 ("steps_per_knot", C.c_int32), ("start_hour", C.c_int32), ("order", C.c_void_p)]
@@ -137,7 +150,7 @@ EXPORTS = (
     "rs_hip_plan_npoints", "rs_hip_plan_npoints_padded", "rs_hip_plan_state_bytes",
     "rs_hip_init_state", "rs_hip_step", "rs_hip_step_cpl", "rs_hip_cpl_replay", "rs_hip_set_output_by_point", "rs_hip_state_download", "rs_hip_state_upload", "rs_hip_state_fanout",
     "rs_hip_failed_count", "rs_hip_clock_probe", "rs_hip_first_failed_index", "rs_hip_set_diagnostics", "rs_hip_diagnostics", "rs_hip_sync", "rs_hip_synth_knots", "rs_hip_expand_forcing", "rs_hip_expand_forcing_ordered", "rs_hip_step_knots", "rs_hip_expand_forcing_on",
-    "rs_hip_plan_order", "rs_hip_recluster", "rs_hip_recluster_forecast", "rs_hip_set_history_score", "rs_hip_coupling_windows_closed", "rs_hip_set_writeback", "rs_hip_plan_order_copy", "rs_hip_outputs_by_point", "rs_hip_summary_cols", "rs_hip_summary_reset", "rs_hip_outputs_summary", "rs_hip_group_cols", "rs_hip_group_path", "rs_hip_group_reset", "rs_hip_outputs_groups", "rs_hip_ens_cols", "rs_ens_table_ints", "rs_ens_member_table", "rs_hip_outputs_ens", "rs_hip_episode_cols", "rs_hip_episodes_reset", "rs_hip_outputs_episodes", "rs_hip_episodes_finish", "rs_hip_grid_max_stencil", "rs_hip_gather_nodes", "rs_hip_plan_reset_order", "rs_hip_set_variant", "rs_hip_set_precision", "rs_hip_test_math", "rs_hip_division_mode", "rs_hip_div_mismatch_count", "rs_hip_div_special_count", "rs_hip_div_samples", "rs_hip_timing_reset", "rs_hip_timing_step_ms", "rs_hip_timing_intervals",
+    "rs_hip_plan_order", "rs_hip_recluster", "rs_hip_recluster_forecast", "rs_hip_set_history_score", "rs_hip_coupling_windows_closed", "rs_hip_set_writeback", "rs_hip_plan_order_copy", "rs_hip_outputs_by_point", "rs_hip_summary_cols", "rs_hip_summary_reset", "rs_hip_outputs_summary", "rs_hip_group_cols", "rs_hip_group_path", "rs_hip_group_reset", "rs_hip_outputs_groups", "rs_hip_ens_cols", "rs_ens_table_ints", "rs_ens_member_table", "rs_hip_outputs_ens", "rs_hip_episode_cols", "rs_hip_episodes_reset", "rs_hip_outputs_episodes", "rs_hip_episodes_finish", "rs_hip_prob_cols", "rs_hip_prob_needs_deficit", "rs_hip_prob_spec_bytes", "rs_hip_prob_work_ints", "rs_hip_prob_reset", "rs_hip_outputs_prob", "rs_hip_grid_max_stencil", "rs_hip_gather_nodes", "rs_hip_plan_reset_order", "rs_hip_set_variant", "rs_hip_set_precision", "rs_hip_test_math", "rs_hip_division_mode", "rs_hip_div_mismatch_count", "rs_hip_div_special_count", "rs_hip_div_samples", "rs_hip_timing_reset", "rs_hip_timing_step_ms", "rs_hip_timing_intervals",
     "rs_host_run_batch", "rs_last_fanout", "rs_driver_run_request", "rs_driver_run", "rs_driver_run_summary", "rs_driver_run_groups", "rs_driver_run_grid", "rs_driver_expand_grid", "rs_driver_run_kept", "rs_driver_kept_fields", "rs_driver_run_episodes", "rs_driver_last_tiles", "rs_driver_last_raw_launches", "rs_hip_bl_stats", "rs_compat_begin", "rs_compat_step", "rs_compat_replay", "rs_compat_failed_index", "rs_compat_last_state", "rs_compat_outputs", "rs_compat_end", "rs_driver_expand", "rs_driver_release_cache", "rs_abi_version", "rs_abi_sizeof", "rs_fortran_sizeof",
 )
 
@@ -262,6 +275,22 @@ def load() -> C.CDLL:
         L.rs_hip_outputs_episodes.argtypes = [C.c_void_p, P(RsOutputs), C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                               C.c_void_p, P(RsEpisodeSpec), C.c_void_p, C.c_void_p]
         L.rs_hip_episodes_finish.argtypes = [C.c_void_p, P(RsEpisodeSpec), C.c_void_p, C.c_void_p]
+    if hasattr(L, "rs_hip_prob_cols"):  # ... nor for the probabilities of conditions over the members
+        L.rs_hip_prob_cols.restype = C.c_int32
+        L.rs_hip_prob_cols.argtypes = [P(RsProbSpec)]
+        L.rs_hip_prob_needs_deficit.restype = C.c_int32
+        L.rs_hip_prob_needs_deficit.argtypes = [P(RsProbSpec)]
+        L.rs_hip_prob_spec_bytes.restype = C.c_int64
+        L.rs_hip_prob_spec_bytes.argtypes = []
+        if L.rs_hip_prob_spec_bytes() != C.sizeof(RsProbSpec):
+            raise RuntimeError(f"{LIB_PATH}: RsProbSpec has {L.rs_hip_prob_spec_bytes()} bytes, this binding assumes "
+                               f"{C.sizeof(RsProbSpec)}")
+        L.rs_hip_prob_work_ints.restype = C.c_int64
+        L.rs_hip_prob_work_ints.argtypes = [C.c_void_p, C.c_int32]
+        L.rs_hip_prob_reset.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rs_hip_outputs_prob.argtypes = [C.c_void_p, P(RsOutputs), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                          P(RsProbSpec), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                          C.c_int64, C.c_void_p]
     if hasattr(L, "rs_hip_state_fanout"):  # ... nor for the fan-out of the carried state
         L.rs_hip_state_fanout.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.rs_hip_plan_reset_order.argtypes = [C.c_void_p]
@@ -339,7 +368,7 @@ def ens_spec(spec) -> RsEnsSpec:
     than the struct holds are cut to that many and their number kept: the library refuses the spec."""
     if isinstance(spec, RsEnsSpec):
         return spec
-    quant = [float(x) for x in spec.quantiles]
+    quant = [float(x) for x in getattr(spec, "quantiles", ())]  # (none: the table of an ensprob.ProbSpec)
     e = RsEnsSpec()
     e.ngroups = int(spec.ngroups)
     e.max_members = int(spec.max_members)
@@ -383,6 +412,38 @@ def episode_cols(spec) -> int:
     if n < 0:
         raise RuntimeError("rs_hip_episode_cols: bad spec (use: bits 0..6, at least one; no NaN bound; peak 0..6; "
                            "min_rows >= 1; max_episodes 1..RS_EPI_MAX)")
+    return n
+
+
+def prob_spec(spec) -> RsProbSpec:
+    """RsProbSpec of anything with ``ngroups``, ``max_members`` and ``conditions``, each with ``use``, ``above[7]`` and
+    ``below[7]`` (ensprob.ProbSpec).  More conditions than the struct holds are cut to that many and their number
+    kept; nothing else is judged here: the library refuses a bad spec."""
+    if isinstance(spec, RsProbSpec):
+        return spec
+    s = RsProbSpec()
+    s.ngroups = int(spec.ngroups)
+    s.max_members = int(spec.max_members)
+    s.nconds = len(spec.conditions)
+    for i, c in enumerate(list(spec.conditions)[:RS_PROB_MAX_CONDS]):
+        above, below = [float(x) for x in c.above], [float(x) for x in c.below]
+        if len(above) != RS_EPI_VARS or len(below) != RS_EPI_VARS:
+            raise ValueError("above, below: seven bounds (tsurf, snow, water, ice, deposit, ice2, deficit)")
+        s.cond[i].use = int(c.use)
+        for k in range(RS_EPI_VARS):
+            s.cond[i].above[k], s.cond[i].below[k] = above[k], below[k]
+    return s
+
+
+def prob_cols(spec) -> int:
+    """Numbers per cell of this spec as the library counts them (rs_hip_prob_cols); raises on a spec it refuses."""
+    L = load()
+    if not hasattr(L, "rs_hip_prob_cols"):
+        raise RuntimeError("this libroadsurf_hip.so has no probabilities over the members (rs_hip_prob_cols)")
+    n = L.rs_hip_prob_cols(C.byref(prob_spec(spec)))
+    if n < 0:
+        raise RuntimeError("rs_hip_prob_cols: bad spec (ngroups >= 1, 1 <= max_members <= RS_ENS_MAX_MEMBERS, 1 .. "
+                           "RS_PROB_MAX_CONDS conditions; use: bits 0..6, at least one; no NaN bound)")
     return n
 
 

@@ -1258,15 +1258,22 @@ __global__ void __launch_bounds__(256) cs_hist_kernel(const uint32_t *__restrict
                                                       int nbins, int ntiles, uint32_t *__restrict__ H) {
   __builtin_amdgcn_s_setprio(3); /* a link of the chain between two step launches of a plan: little work, all of it waited for */
   extern __shared__ uint32_t cs_h[];
+  /* (the two loops over the bins stay rolled and the tile's keys are addressed by a 32-bit offset from the tile's
+   * uniform base: the kernel has to fit in the 32 registers per lane that five step wavefronts leave on a SIMD) */
+#pragma unroll 1
   for (int b = threadIdx.x; b < nbins; b += 256) cs_h[b] = 0u;
   __syncthreads();
   const int64_t base = (int64_t)blockIdx.x * CS_TILE;
-  for (int i = threadIdx.x; i < CS_TILE; i += 256) {
-    const int64_t idx = base + i;
-    if (idx < n) atomicAdd(&cs_h[(keys[via ? (int64_t)via[idx] : idx] >> shift) & (uint32_t)(nbins - 1)], 1u);
-  }
+  const int64_t left = n - base;
+  const uint32_t cnt = left < CS_TILE ? (uint32_t)left : (uint32_t)CS_TILE; /* (a tile is never empty) */
+  const uint32_t *vt = via ? via + base : nullptr;
+#pragma unroll
+  for (uint32_t i = threadIdx.x; i < (uint32_t)CS_TILE; i += 256)
+    if (i < cnt) atomicAdd(&cs_h[(keys[vt ? (int64_t)vt[i] : base + i] >> shift) & (uint32_t)(nbins - 1)], 1u);
   __syncthreads();
-  for (int b = threadIdx.x; b < nbins; b += 256) H[(int64_t)blockIdx.x * nbins + b] = cs_h[b];
+  uint32_t *Ht = H + (int64_t)blockIdx.x * nbins;
+#pragma unroll 1
+  for (int b = threadIdx.x; b < nbins; b += 256) Ht[b] = cs_h[b];
 }
 
 /* one lane per bin: walks the tiles in order (coalesced rows of H[tile][bin]), leaves the bin's
@@ -1314,7 +1321,7 @@ __global__ void __launch_bounds__(64) cs_scatter_kernel(const uint32_t *__restri
     /* the rows' loads are issued a batch at a time (round 3 issued them one row at a time, behind the
      * scan of the row before: 64 L2 round trips in a row, 80 of the kernel's 85 us on a 62 500-point
      * plan, where nothing else hides them) */
-    constexpr int ROWS = 16;
+    constexpr int ROWS = 8;
     uint32_t carry = 0u;
     for (int r0 = 0; r0 < nbins; r0 += 64 * ROWS) {
       uint32_t tv[ROWS], hv[ROWS];
@@ -1337,24 +1344,27 @@ __global__ void __launch_bounds__(64) cs_scatter_kernel(const uint32_t *__restri
   /* the keys of CS_BATCH rounds are fetched together (a load per round would put 64 memory round trips
    * behind one another), but no more: the kernel has to fit beside the step kernels' wavefronts, which
    * leave few vector registers free on a SIMD (64 keys in registers: 193 VGPRs, 0.5 ms per sort) */
-  constexpr int CS_BATCH = 8;
+  constexpr int CS_BATCH = 4;
+  /* (a key's place in the tile as a 32-bit offset beside the tile's uniform base: `cnt` keys, never none) */
+  const int64_t left = n - base;
+  const uint32_t cnt = left < CS_TILE ? (uint32_t)left : (uint32_t)CS_TILE;
+  const uint32_t *vt = via ? via + base : nullptr;
   for (int r0 = 0; r0 < CS_TILE / 64; r0 += CS_BATCH) {
-    if (base + (int64_t)r0 * 64 >= n) break; /* uniform: behind the last key */
+    if ((uint32_t)r0 * 64u >= cnt) break; /* uniform: behind the last key */
     uint32_t kreg[CS_BATCH], sreg[CS_BATCH];
 #pragma unroll
     for (int q = 0; q < CS_BATCH; ++q) {
-      const int64_t idx = base + (int64_t)(r0 + q) * 64 + lane;
-      sreg[q] = (idx < n && via) ? via[idx] : (uint32_t)idx;
+      const uint32_t off = (uint32_t)(r0 + q) * 64u + lane;
+      sreg[q] = (off < cnt && vt) ? vt[off] : (uint32_t)base + off;
     }
 #pragma unroll
     for (int q = 0; q < CS_BATCH; ++q) {
-      const int64_t idx = base + (int64_t)(r0 + q) * 64 + lane;
-      kreg[q] = idx < n ? ((keys[sreg[q]] >> shift) & (uint32_t)(nbins - 1)) : 0u;
+      const uint32_t off = (uint32_t)(r0 + q) * 64u + lane;
+      kreg[q] = off < cnt ? ((keys[sreg[q]] >> shift) & (uint32_t)(nbins - 1)) : 0u;
     }
 #pragma unroll
   for (int q = 0; q < CS_BATCH; ++q) {
-    const int64_t idx = base + (int64_t)(r0 + q) * 64 + lane;
-    const bool valid = idx < n;
+    const bool valid = (uint32_t)(r0 + q) * 64u + lane < cnt;
     const uint32_t key = kreg[q];
     unsigned long long same = __ballot(valid);
     for (int bit = 0; bit < nbits; ++bit) {

@@ -98,6 +98,11 @@ struct ForecastArgs {
   int32_t extra_log; /* field 0 of the mode: 0 = the previews' extra passes summed, saturating at 7; 1 = the
                         LONGEST loop expected in the window (previews, the last index stepped, a passage through
                         the loop's slow band) in classes 5, 6, 7, 8, 9-12, 13-20, 21-30, 31+ */
+  /* filled by rs_launch_forecast_keys from pv.mode, so that no thread divides by ten: the mode's decimal digits
+   * (its shorthands 0..3 spelled out), four bits each, the most significant in the highest nibble used; how many;
+   * whether one of them is the ground digit 9 */
+  uint64_t mode_digits;
+  int32_t mode_ndigits, mode_ground;
 };
 
 struct KnotArgs {

@@ -709,8 +709,13 @@ enum { PR_TAIR = 0, PR_VZ, PR_RHZ, PR_RAIN, PR_SNOW, PR_AVC, PR_EAIR, PR_SW, PR_
 template <int NPREP>
 struct DuoMailT {
   double v[2][2][64]; /* [buffer][0: Tmp(2) from the surface wave, 1: Tmp(3) from the ground wave][lane] */
-  uint32_t failed[64]; /* sticky, set by the surface wave: the point's loop has exited (the ground wave
-                          then leaves Tmp(3..N) alone, as the one-point-per-lane flavours do) */
+  /* [buffer = index parity][lane], written by the surface wave during the index BEFORE: the point's loop has
+   * exited (the ground wave then leaves Tmp(3..N) alone, as the one-point-per-lane flavours do).  Double-buffered
+   * like everything else in the mailbox: as one word per lane, set in the failing index itself, it held only as
+   * long as the ground wave read it before the surface wave got that far - a ground wave that waits for a global
+   * load first (the LEAN instances' bottom temperature behind a window's forcing loads) skipped the failing index's
+   * own step (tests/test_hip_parity.py: the state of failed points). */
+  uint32_t failed[2][64];
   /* round 4: what a step needs of its forcing alone (ForcingPrep, rs_physics_body.inc), worked out by
    * the ground wave one index ahead: [buffer = index parity][value][lane].  The traffic friction is the same for
    * every point of an index (one bit per buffer), VK x VZ and the products with the air's volumetric heat capacity
@@ -719,7 +724,7 @@ struct DuoMailT {
    * constant is three operations on the air temperature the surface wave has anyway: nine values instead of eleven
    * (+ 1.2 % at 1 M points).  The air's vapour pressure left too (RS_EAIR_SURFACE, rs_physics.hpp): a Magnus
    * quotient and an exp that the surface wave runs on the mailed tair and rhz, and only in a wavefront whose dry
-   * tail does not skip them - eight values, 15 168 B per workgroup of the LEAN instances (see RS_DUO_LEAN_WAVES). */
+   * tail does not skip them - eight values, 15 424 B per workgroup of the LEAN instances (see RS_DUO_LEAN_WAVES). */
   double prep[2][NPREP][64];
   /* bit 0: CheckValues' verdict on the forcing; bit 1: the index falls in the night of
    * SetDayDependendVariables (src/BalanceModel.f90:354-387) - per LANE: with RsForcing::hour_pstride = 1
@@ -743,19 +748,39 @@ __device__ __forceinline__ void duo_put_prep(Mail &mail, int buf, uint32_t lane,
   if (FULL) w[PR_OBS][lane] = q.tsurfobs;
   mail.prep_bad[buf][lane] = (q.bad ? 1u : 0u) | (q.night ? 2u : 0u) | (q.bad_rw ? 8u : 0u);
 }
-template <bool FULL, bool SKYG = false, class C, class Mail>
-__device__ __forceinline__ ForcingPrep duo_get_prep(const C &c, const Mail &mail, int buf, uint32_t lane,
-                                                    const uint32_t *skyfl = nullptr) {
+/* LATE (the LEAN instances): the humidity, the short- and long-wave radiation and the wind speed of the guard's
+ * fallback are read from the mailbox where model_step_fluxes_prepped first uses them - behind the boundary-layer
+ * loop, or in a wavefront whose dry tail is alive - instead of being held in registers across the loop.  Buffer
+ * k & 1 stays as the ground wave left it until the barrier that ends index k: the ground wave writes the other one. */
+struct DuoLatePrep : ForcingPrep {
+  const double (*w)[64];
+  uint32_t lane;
+  __device__ __forceinline__ double rhz_late() const { return w[PR_RHZ][lane]; }
+  __device__ __forceinline__ double vz_late() const { return w[PR_VZ][lane]; }
+  __device__ __forceinline__ double sw_late() const { return w[PR_SW][lane]; }
+  __device__ __forceinline__ double lw_late() const { return w[PR_LW][lane]; }
+};
+template <bool FULL, bool SKYG = false, bool LATE = false, class C, class Mail>
+__device__ __forceinline__ auto duo_get_prep(const C &c, const Mail &mail, int buf, uint32_t lane,
+                                             const uint32_t *skyfl = nullptr) {
   const double (*w)[64] = mail.prep[buf];
-  ForcingPrep q;
-  q.tair = w[PR_TAIR][lane]; q.vz = w[PR_VZ][lane]; q.rhz = w[PR_RHZ][lane]; q.rain = w[PR_RAIN][lane];
+  typename std::conditional<LATE, DuoLatePrep, ForcingPrep>::type q;
+  if constexpr (LATE) {
+    q.w = w;
+    q.lane = lane;
+  }
+  q.tair = w[PR_TAIR][lane]; q.vz = w[PR_VZ][lane]; q.rain = w[PR_RAIN][lane];
+  if (!LATE) q.rhz = w[PR_RHZ][lane];
   q.snow = w[PR_SNOW][lane];
   const double AirVCap = w[PR_AVC][lane];
   q.AirVCap = AirVCap;
 #ifndef RS_EAIR_SURFACE
   q.EAir = w[PR_EAIR][lane];
 #endif
-  q.sw = w[PR_SW][lane]; q.lw = w[PR_LW][lane];
+  if (!LATE) {
+    q.sw = w[PR_SW][lane];
+    q.lw = w[PR_LW][lane];
+  }
   if (FULL) q.tsurfobs = w[PR_OBS][lane];
   uint32_t flags = mail.prep_bad[buf][lane];
   if (SKYG) flags |= skyfl[buf * 64 + lane]; /* the sky wave's share of CheckValues (bit 0) and its `stop` (bit 2) */
@@ -810,6 +835,7 @@ __device__ __forceinline__ void duo_surface(const MathTab &mt, DuoMailT<FULL ? P
   static_assert(!(SKY && SKYG), "the sky view is this wave's or the ground wave's");
   static_assert(FULL || !CPL, "coupling belongs to the FULL feature set");
   static_assert(CPL || !REPLAY, "replays belong to coupling");
+  constexpr bool LATE = !FULL; /* duo_get_prep: the LEAN instances read part of the mailbox where it is used */
   KernArgs ka = kernargs();
   const uint32_t ml = threadIdx.x & 63u;
   /* the workgroup's slots: 64 from 64 * blockIdx.x, or what the wave table says (rs_cluster_wave_table);
@@ -864,14 +890,13 @@ __device__ __forceinline__ void duo_surface(const MathTab &mt, DuoMailT<FULL ? P
   double r_swcof = R4(1.0), r_lwcof = R4(1.0);
   mail.v[0][0][ml] = T.get(2);
   /* arrives failed (or a dead lane): frozen from the first index; CPL: or not due for it */
-  mail.failed[ml] = (s.failed || (CPL && (parked || t0 != next_i))) ? 1u : 0u;
+  mail.failed[0][ml] = (s.failed || (CPL && (parked || t0 != next_i))) ? 1u : 0u;
   duo_meet();
   /* the index still steps (the ground wave is in it already); the next does not */
   auto fail_at = [&](int32_t idx) {
     s.failed = true;
     ka->state[(int64_t)RS_ST_FAILED * ka->np_pad + row0 + lane] = (double)idx;
-    mail.failed[ml] = 1u;
-  };
+  }; /* (the ground wave hears of it through the flag of the NEXT index, written before the meeting) */
   auto blank_rows = [&](int32_t i_from) {
     for (int32_t ii = i_from; ii < t0 + nsteps; ++ii) {
       int64_t r;
@@ -912,14 +937,16 @@ __device__ __forceinline__ void duo_surface(const MathTab &mt, DuoMailT<FULL ? P
     int64_t orow = orow_next;
     bool owrite = owait == 0;
     if (OUTIDX) owrite = output_row<true>(ka, i, orow);
-    double t3 = mail.v[k & 1][1][ml]; /* Tmp(3) as the last step left it */
+    /* Tmp(3) as the last step left it (LATE: read where layer 2 needs it, behind the boundary-layer loop - the
+     * ground wave writes the other buffer during this index) */
+    double t3 = LATE ? 0.0 : mail.v[k & 1][1][ml];
     bool go = true; /* CPL: the lane is due for this index (a failed lane keeps counting: its rows are blanked) */
     if (CPL) {
       go = !(parked || i != next_i);
       if (go) next_i = i + 1;
     }
     if (go && !s.failed) {
-      const ForcingPrep q = duo_get_prep<FULL, SKYG>(c, mail, k & 1, ml, skyfl);
+      const auto q = duo_get_prep<FULL, SKYG, LATE>(c, mail, k & 1, ml, skyfl);
       if (i < c.SimLen) { /* CheckValues: the forcing's verdict | the surface temperature's */
         /* REPLAY, at the rewind: the index CheckValues has just seen is the one behind the window end - with
          * the surface temperature of the end of the window */
@@ -984,7 +1011,7 @@ __device__ __forceinline__ void duo_surface(const MathTab &mt, DuoMailT<FULL ? P
         }
       }
       const double tair = q.tair;
-      ForcingPrep qs = q;
+      auto qs = q;
       if (SKY) {
         const int64_t row = (int64_t)k * ka->f.t_stride + row0;
         const LaneOff L(lane);
@@ -1011,6 +1038,7 @@ __device__ __forceinline__ void duo_surface(const MathTab &mt, DuoMailT<FULL ? P
         score = fx.trips; /* the launch's last index: what forecast_key_kernel takes as one more preview */
       }
       /* layers 1-2 with Tmp(3) where a two-layer column has its lower boundary */
+      if (LATE) t3 = mail.v[k & 1][1][ml];
       model_step_ground<RegProfile<2>, RegProfile<2>, false>(c, s, T, t3, tair, fx, R4(-9999.9), cp);
       if (owrite) {
         if (OUTIDX && ka->out_index) store_outputs<true, false>(ka, orow, row0, lane, s, true);
@@ -1022,8 +1050,8 @@ __device__ __forceinline__ void duo_surface(const MathTab &mt, DuoMailT<FULL ? P
       if (CPL && cpl_on && i < c.SimLen && i == cpl_ce)
         cpl_window_end(ka->state, ka->np_pad, row0 + lane, cw, s, cpl_swcorr, cpl_lwcorr, cpl_lastobs, parked);
     }
-    /* CPL: frozen at the NEXT index? (failed, parked, or not due for it) */
-    if (CPL) mail.failed[ml] = (s.failed || parked || (i + 1) != next_i) ? 1u : 0u;
+    /* frozen at the NEXT index?  failed; CPL: or parked, or not due for it */
+    mail.failed[(k & 1) ^ 1][ml] = (s.failed || (CPL && (parked || (i + 1) != next_i))) ? 1u : 0u;
     mail.v[(k & 1) ^ 1][0][ml] = T.get(2);
     if (!OUTIDX) {
       if (owrite) {
@@ -1039,6 +1067,11 @@ __device__ __forceinline__ void duo_surface(const MathTab &mt, DuoMailT<FULL ? P
   if (live) {
     double *st = a.state;
     const int64_t np = a.np_pad;
+    /* LATE: the point's row formed again from the lane, which the loop keeps anyway, instead of a 64-bit index
+     * held across the time loop for these stores alone */
+    uint32_t le = ml;
+    if (LATE) asm volatile("" : "+v"(le));
+    const int64_t p = LATE ? row0 + le : row0 + lane;
     st[(int64_t)(RS_ST_TMP0 + 0) * np + p] = T.get(1);
     st[(int64_t)(RS_ST_TMP0 + 1) * np + p] = T.get(2);
     st[(int64_t)RS_ST_TNW1 * np + p] = s.tnw1;
@@ -1068,7 +1101,7 @@ __device__ __forceinline__ void duo_surface(const MathTab &mt, DuoMailT<FULL ? P
 template <bool FULL>
 struct KnotLerp {
   double v0[FULL ? 7 : 6], dv[FULL ? 7 : 6]; /* tair, vz, rhz, prec, sw, lw [, tdew] */
-  int32_t ph0, ph1;
+  int32_t ph1; /* (PrecPhase of the earlier knot is used where it is loaded only: knot_forcing) */
   /* The time bookkeeping, launch-uniform and carried from index to index (knot_begin, knot_forcing): the knot
    * interval k and the position r in it of the index knot_forcing makes next - one division per launch, for its
    * first index; the span, its double and its reciprocal, read once per launch; the hour of the interval and
@@ -1099,6 +1132,9 @@ template <bool FULL>
 __device__ __forceinline__ Forcing knot_forcing(KernArgs ka, int64_t col, bool live, KnotLerp<FULL> &K,
                                                 int32_t &kcur, int32_t i) {
   const int32_t k = K.k, r = K.r;
+  /* PrecPhase of the earlier knot: the index on a knot (r == 0) is the first of its interval, or of the launch - the
+   * call that loads the interval's knots, and the only one to read it */
+  int32_t ph0 = 0;
   if (k != kcur) { /* uniform: a new knot interval */
     kcur = k;
     /* rs_sy_hour's expression on the interval, forcing_prep_tail's comparison on the hour: both change here only */
@@ -1117,8 +1153,8 @@ __device__ __forceinline__ Forcing knot_forcing(KernArgs ka, int64_t col, bool l
       const double v1 = (live && has_b) ? kb_[(int64_t)fld[q] * np] : K.v0[q];
       K.dv[q] = v1 - K.v0[q];
     }
-    K.ph0 = live ? (int32_t)ka_[8 * np] : 0;
-    K.ph1 = (live && has_b) ? (int32_t)kb_[8 * np] : K.ph0;
+    ph0 = live ? (int32_t)ka_[8 * np] : 0;
+    K.ph1 = (live && has_b) ? (int32_t)kb_[8 * np] : ph0;
   }
   /* FULL: beside seven knot pairs and thirteen layers the span, its double and its reciprocal cost the instance two
    * vector registers when they stay resident (120 -> 122): that feature set reads them again at every index */
@@ -1131,7 +1167,7 @@ __device__ __forceinline__ Forcing knot_forcing(KernArgs ka, int64_t col, bool l
   f.prec = K.v0[3] + rs_div_u(secs * K.dv[3], span, r_spk);
   f.sw = K.v0[4] + rs_div_u(secs * K.dv[4], span, r_spk);
   f.lw = K.v0[5] + rs_div_u(secs * K.dv[5], span, r_spk);
-  f.phase = (r == 0) ? K.ph0 : K.ph1;
+  f.phase = (r == 0) ? ph0 : K.ph1;
   f.hour = K.hour;
   f.tdew = 0.0;
   f.tsurfobs = R4(-9999.9);
@@ -1419,7 +1455,11 @@ __device__ __forceinline__ void duo_ground(const MathTab &mt, DuoMailT<FULL ? PR
   double Tg[NL - 2]; /* Tmp(3..NL) */
 #pragma unroll
   for (int j = 3; j <= NL; ++j) Tg[j - 3] = live ? a.state[(int64_t)(RS_ST_TMP0 + j - 1) * a.np_pad + p] : 0.0;
-  const double tbot = live ? ka->pp.tbottom[p] : 0.0;
+  /* LATE (the LEAN instances): what the time loop uses once per index or once per knot interval is not held across
+   * it - the bottom temperature is read again at every index (one coalesced load from the scalar base), the knot
+   * column is a 32-bit lane value beside a scalar base, the point's row is formed again for the final stores */
+  constexpr bool LATE = !FULL;
+  const double tbot = (live && !LATE) ? ka->pp.tbottom[p] : 0.0;
   mail.v[0][1][ml] = Tg[0];
   const int32_t nsteps = ka->nsteps, t0 = ka->t0;
   /* FULL: as time_loop sets them up */
@@ -1521,7 +1561,10 @@ __device__ __forceinline__ void duo_ground(const MathTab &mt, DuoMailT<FULL ? PR
    * reads nothing: the windows need only span npoints columns) */
   Forcing nxt = Forcing();
   int32_t kcur = -1;
-  const int64_t kcol = (KNOTS && live) ? (ka->knot_gather ? (int64_t)ka->knot_gather[p] : p) : 0;
+  /* (LATE: gathered, the 32-bit entry of the order row; else the lane beside the workgroup's first row) */
+  const int32_t kcol32 = (KNOTS && LATE && live) ? (ka->knot_gather ? ka->knot_gather[p] : (int32_t)lane) : 0;
+  const int64_t kcol0 = (KNOTS && LATE && !ka->knot_gather) ? row0 : 0;
+  const int64_t kcol = LATE ? 0 : (KNOTS && live) ? (ka->knot_gather ? (int64_t)ka->knot_gather[p] : p) : 0;
   /* RAW: the point's column of the raw series, read_input's verdict on it, the segment of the first index */
   constexpr int FSET = SKYG ? FSET_GROUND : FSET_ALL;
   RawLerp<raw_nfields(FSET)> rlerp;
@@ -1540,7 +1583,7 @@ __device__ __forceinline__ void duo_ground(const MathTab &mt, DuoMailT<FULL ? PR
     const ConstsAS &c0 = consts_of(ka);
     if (KNOTS) {
       knot_begin<FULL>(ka, klerp, t0);
-      nxt = knot_forcing<FULL>(ka, kcol, live, klerp, kcur, t0);
+      nxt = knot_forcing<FULL>(ka, LATE ? kcol0 + kcol32 : kcol, live, klerp, kcur, t0);
     } else if (RAW) nxt = raw_forcing<FSET>(ka, rcol, live, rejected, rlerp, t0, obs_wanted(c0, t0));
     else if (live) nxt = load_forcing<FULL, true>(ka, row0, lane, 0);
     duo_put_prep<FULL, SKYG>(mail, 0, ml, prep(c0, nxt, t0, obs_cur));
@@ -1553,9 +1596,10 @@ __device__ __forceinline__ void duo_ground(const MathTab &mt, DuoMailT<FULL ? PR
     /* next index's forcing: fetched here, used behind the layers */
     if (!KNOTS && !RAW && k + 1 < nsteps && live) nxt = load_forcing<FULL, true>(ka, row0, lane, k + 1);
     double t2 = mail.v[k & 1][0][ml]; /* Tmp(2) as the last step left it (melting included) */
+    const double tbot_k = !LATE ? tbot : live ? LaneOff(lane).ld(ka->pp.tbottom + row0) : 0.0;
     /* a failed point takes no further step in any flavour: its Tmp(3..N) stay as the failing index left
      * them (the flag was raised before the barrier that ended that index) */
-    if (REPLAY && !mail.failed[ml] && t0 + k == cpl_cs && t0 + k < c.SimLen && live) {
+    if (REPLAY && !mail.failed[k & 1][ml] && t0 + k == cpl_cs && t0 + k < c.SimLen && live) {
       /* the rewind (uploadDataForCoupling, src/Coupling.f90:245-247): Tmp is restored, TmpNw is not - this
        * step's heat capacities see the end-of-window profile (Tg as it stands), its fluxes the restored one */
       const double *sv = ka->state + (int64_t)RS_ST_CPL_SAVE_TMP0 * ka->np_pad + p;
@@ -1570,7 +1614,7 @@ __device__ __forceinline__ void duo_ground(const MathTab &mt, DuoMailT<FULL ? PR
         cur = tnext;
       }
     } else
-    if (!mail.failed[ml]) {
+    if (!mail.failed[k & 1][ml]) {
       if (CPL && !REPLAY && t0 + k == cpl_cs && t0 + k < c.SimLen && live) { /* saveDataForCoupling: layers 3..N as they stand */
 #pragma unroll
         for (int j = 3; j <= NL; ++j) ka->state[(int64_t)(RS_ST_CPL_SAVE_TMP0 + j - 1) * ka->np_pad + p] = Tg[j - 3];
@@ -1588,7 +1632,7 @@ __device__ __forceinline__ void duo_ground(const MathTab &mt, DuoMailT<FULL ? PR
 #pragma unroll
       for (int j = 3; j <= NL; ++j) {
         const double tj = Tg[j - 3];
-        const double tnext = (j == NL) ? tbot : Tg[j - 2];
+        const double tnext = (j == NL) ? tbot_k : Tg[j - 2];
         Tg[j - 3] = layer_step(c, j, tj, tj, tnext, Gprev, nullptr);
       }
     }
@@ -1596,15 +1640,18 @@ __device__ __forceinline__ void duo_ground(const MathTab &mt, DuoMailT<FULL ? PR
     mail.v[(k & 1) ^ 1][1][ml] = Tg[0];
     if (k + 1 < nsteps) {
       const int32_t in = t0 + k + 1;
-      if (KNOTS) nxt = knot_forcing<FULL>(ka, kcol, live, klerp, kcur, in);
+      if (KNOTS) nxt = knot_forcing<FULL>(ka, LATE ? kcol0 + kcol32 : kcol, live, klerp, kcur, in);
       if (RAW) nxt = raw_forcing<FSET>(ka, rcol, live, rejected, rlerp, in, obs_wanted(c, in));
       duo_put_prep<FULL, SKYG>(mail, (k & 1) ^ 1, ml, prep(c, nxt, in, obs_cur));
     }
     duo_meet();
   }
   if (live) {
+    uint32_t le = ml; /* (LATE: as in duo_surface) */
+    if (LATE) asm volatile("" : "+v"(le));
+    const int64_t pe = LATE ? row0 + le : p;
 #pragma unroll
-    for (int j = 3; j <= NL; ++j) a.state[(int64_t)(RS_ST_TMP0 + j - 1) * a.np_pad + p] = Tg[j - 3];
+    for (int j = 3; j <= NL; ++j) a.state[(int64_t)(RS_ST_TMP0 + j - 1) * a.np_pad + pe] = Tg[j - 3];
   }
 }
 
@@ -1670,11 +1717,17 @@ __device__ __forceinline__ void duo_sky(DuoMailT<PR_FULL> &mail, uint32_t *skyfl
 template <int NL, bool SCORE, int SRC = SRC_WINDOW, bool FULL = false, bool SKY = false, bool CPL = false,
           bool REPLAY = false>
 #ifndef RS_DUO_LEAN_WAVES
-/* The LEAN instances' LDS (15 168 B; 16 192 B when this was measured) would let ten workgroups onto a CU, and at five
- * wavefronts per SIMD they fit 96 registers with 9-14 spilled - measured (tools/experiments/r6_ab3.sh, profiles/r06_lean_waves_per_simd.txt): 1 M
- * points 2.513e10 at five against 2.560e10 at four (2.529e10 with round 5's mailbox of eleven values), level at
- * 250 000 and 125 000 points.  The pass is bound by what the wavefronts issue, not by how many of them wait. */
-#define RS_DUO_LEAN_WAVES 4
+/* Five wavefronts per SIMD for the LEAN instances: 96 registers without a spill (the mailbox values a step first needs
+ * behind the boundary-layer loop are read there, the ground wave keeps no per-point constant it uses once per index:
+ * LATE in duo_surface / duo_ground; tests/test_duo_lean_resources.py holds the figures), 15 424 B of LDS - ten
+ * workgroups to a CU.  Measured against four (profiles/r11_five_waves.txt): the step launches of a pass sum to 15 %
+ * less, and the headline gains - but only with EVERY kernel of the re-sort chain inside the 32 registers per lane
+ * that five step wavefronts leave on a SIMD (forecast_key_kernel, cs_hist, cs_binscan, cs_scatter, apply_kernel):
+ * with the forecast key at 46 registers it queued behind the step wavefronts for half a millisecond per launch and the
+ * headline LOST 6 %.  (Round 6 had forced five wavefronts on code that then spilled 9-14 registers into the time
+ * loop, - 1.7 %: profiles/r06_lean_waves_per_simd.txt.)  A new value held across the time loop, or a chain kernel that
+ * grows past 32 registers, undoes it. */
+#define RS_DUO_LEAN_WAVES 5
 #endif
 __global__ void __launch_bounds__((SKY && SRC == SRC_RAW) ? 192 : 128, REPLAY ? 3 : FULL ? 4 : RS_DUO_LEAN_WAVES) step_kernel_duo(const StepArgs a) {
   /* (REPLAY at three waves per SIMD: with the rewind's code the instance spilled 50 registers at four) */
@@ -2013,26 +2066,26 @@ __global__ void __launch_bounds__(kBlock) cpl_window_bounds_kernel(const StepArg
  * hardware reciprocal/sqrt/log - it only orders the slots, no model value depends on it. */
 __global__ void __launch_bounds__(kBlock) forecast_key_kernel(const ForecastArgs a) {
   __builtin_amdgcn_s_setprio(3); /* a link of the chain between two step launches of a plan: little work, all of it waited for */
-  const int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (s >= a.npoints) return;
+  /* (the slot and the preview column are 32-bit values - the slots are, rs_cluster.hip - and the carried surface
+   * temperature and the air temperature of `now` are read again at every preview instead of being held across the
+   * loops: registers, see the scheduling barrier below) */
+  const uint32_t s = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
+  if ((int64_t)s >= a.npoints) return;
   const ConstsAS &c = consts_of(&a);
   const int64_t np = a.np_pad;
-  auto st = [&](int row) -> double {
-    return a.f32 ? (double)((const float *)a.state)[(int64_t)row * np + s]
-                 : ((const double *)a.state)[(int64_t)row * np + s];
+  auto st_at = [&](int row, uint32_t slot) -> double {
+    return a.f32 ? (double)((const float *)a.state)[(int64_t)row * np + slot]
+                 : ((const double *)a.state)[(int64_t)row * np + slot];
   };
-  const double ts_now = st(RS_ST_TSURF);
-  const bool has_snow = st(RS_ST_SNOW) > 0.0, has_ice = st(RS_ST_ICE) > 0.0 || st(RS_ST_ICE2) > 0.0,
-             has_wet = st(RS_ST_WAT) > 0.0 || st(RS_ST_DEP) > 0.0;
-  const int32_t cover = (has_snow || has_ice || has_wet) ? 1 : 0;
-  /* which storage branches the point will take (src/Storage.f90): snow is the longest chain */
-  const int32_t sclass = has_snow ? 3 : has_ice ? 2 : has_wet ? 1 : 0;
-  const int64_t pq = a.pv.index ? (int64_t)a.pv.index[s] : s; /* preview rows in point order */
+  auto st = [&](int row) -> double { return st_at(row, s); };
+  const uint32_t pq = a.pv.index ? (uint32_t)a.pv.index[s] : s; /* preview rows in point order */
+  auto preview_at = [&](const double *const *row, const double *const *row_b, int q, uint32_t col) -> double {
+    const double v = row[q][col];
+    return row_b[q] ? v + a.pv.w[q] * (row_b[q][col] - v) : v; /* RsPreview::tair_b: between two rows */
+  };
   auto preview = [&](const double *const *row, const double *const *row_b, int q) -> double {
-    const double v = row[q][pq];
-    return row_b[q] ? v + a.pv.w[q] * (row_b[q][pq] - v) : v; /* RsPreview::tair_b: between two rows */
+    return preview_at(row, row_b, q, pq);
   };
-  const double ta_now = a.pv.tair_now ? a.pv.tair_now[pq] : preview(a.pv.tair, a.pv.tair_b, 0);
   const double stab_num = -c.VK_Const * c.ZRefT * c.Grav;
   int32_t unst = 0, farc = 0, extra = 0, maxtrip = 5;
   float stab_lo = 2.f, stab_hi = -2.f; /* the converged stability parameter of the previews, after its clamp */
@@ -2042,9 +2095,16 @@ __global__ void __launch_bounds__(kBlock) forecast_key_kernel(const ForecastArgs
     const double hour = (double)a.pv.hour[q];
     const double calm = (hour >= c.NightOn || hour <= c.NightOff) ? c.CalmLimNgt : c.CalmLimDay;
     if (vz < calm) vz = calm;
+    uint32_t sl = s, pl = pq; /* (opaque copies: the two loads stay inside the loop) */
+    asm volatile("" : "+v"(sl), "+v"(pl));
+    const double ts_now = st_at(RS_ST_TSURF, sl);
+    const double ta_now = a.pv.tair_now ? a.pv.tair_now[pl] : preview_at(a.pv.tair, a.pv.tair_b, 0, pl);
     const double ts = ts_now + a.pv.alpha * (ta - ta_now);
     const double TaK = ta + R4(273.15);
     const double dens = R4(100000.0) / (R4(287.05) * TaK);
+    /* (one IEEE division after the other: interleaved by the scheduler the two expansions held 40 registers, and
+     * the kernel has to fit in the 32 that five step wavefronts leave on a SIMD) */
+    __builtin_amdgcn_sched_barrier(0);
     const double hcap = R4(1005.0) + (TaK - R4(250.0)) * (TaK - R4(250.0)) / R4(3364.);
     const double avc = hcap * dens;
     /* the iteration itself in single precision with the hardware's reciprocal, square root and
@@ -2055,6 +2115,7 @@ __global__ void __launch_bounds__(kBlock) forecast_key_kernel(const ForecastArgs
                 lC = (float)c.logCond;
     float psim = 0.f, psih = 0.f, bl = 0.f, stab_last = 0.f;
     int32_t nnear = 0, nfar = 0, j = 1;
+#pragma nounroll /* (unrolled by two it carried six registers more) */
     for (; j <= RS_BL_MAXIT; ++j) {
       const float old = bl;
       const float us = vkvz * __builtin_amdgcn_rcpf(lU + psim);
@@ -2092,6 +2153,12 @@ __global__ void __launch_bounds__(kBlock) forecast_key_kernel(const ForecastArgs
    * parameter sits at its clamp (PSI = 4.7, two passes and it stands), on the other below: a point whose
    * previews lie on both sides passes through the band inside the window ... */
   if (a.extra_log && stab_hi >= 1.f && stab_lo < 1.f) maxtrip = 31;
+  /* (the storages are read here, behind the previews: nothing of them is held across the loops above) */
+  const bool has_snow = st(RS_ST_SNOW) > 0.0, has_ice = st(RS_ST_ICE) > 0.0 || st(RS_ST_ICE2) > 0.0,
+             has_wet = st(RS_ST_WAT) > 0.0 || st(RS_ST_DEP) > 0.0;
+  const int32_t cover = (has_snow || has_ice || has_wet) ? 1 : 0;
+  /* which storage branches the point will take (src/Storage.f90): snow is the longest chain */
+  const int32_t sclass = has_snow ? 3 : has_ice ? 2 : has_wet ? 1 : 0;
   if (a.extra_log) { /* ... and the pass count of the last index stepped is one more preview (the two-wavefront
                         flavour without the history score leaves it in the score's slot; other flavours leave 0
                         or a score there: ignored unless 5..RS_BL_MAXIT) */
@@ -2110,10 +2177,7 @@ __global__ void __launch_bounds__(kBlock) forecast_key_kernel(const ForecastArgs
    * classes of the boundary-layer fields stay as they are, their points line up by frost depth. */
   uint32_t ground = 0u;
   {
-    int32_t m9 = a.pv.mode;
-    bool want = false;
-    for (; m9 > 0; m9 /= 10) want |= (m9 % 10) == 9;
-    if (want) {
+    if (a.mode_ground) {
       const int NL = c.NLayers;
       int32_t deepest = 0, first = 0;
       for (int j = NL; j >= 1; --j)
@@ -2129,14 +2193,10 @@ __global__ void __launch_bounds__(kBlock) forecast_key_kernel(const ForecastArgs
   /* key fields, most significant first, named by the decimal digits of `mode`:
    * 1 unstable previews (4 bits), 2 of which on the table path of log (4 bits), 3 cover (1 bit),
    * 4 predicted extra passes (12 bits), 5 storage class snow > ice > wet > bare (2 bits).  Modes 0..3 are shorthands for 14, 124, 134, 1234. */
-  int32_t m = a.pv.mode;
-  m = (m == 0) ? 14 : (m == 1) ? 124 : (m == 2) ? 134 : (m == 3) ? 1234 : m;
-  int32_t div = 1;
-  while (m / div >= 10) div *= 10;
   uint32_t key = 0;
   int bits = 0;
-  for (; div >= 1; div /= 10) {
-    const int d = (m / div) % 10;
+  for (int t = a.mode_ndigits - 1; t >= 0; --t) { /* (the digits come from the host: ForecastArgs::mode_digits) */
+    const int d = (int)((a.mode_digits >> (4 * t)) & 15u);
     if (d == 1) { key = (key << 4) | (uint32_t)unst; bits += 4; }
     else if (d == 2) { key = (key << 4) | (uint32_t)farc; bits += 4; }
     else if (d == 3) { key = (key << 1) | (uint32_t)cover; bits += 1; }
@@ -2244,7 +2304,20 @@ int rs_forecast_key_bits(int32_t m) {
   return bits;
 }
 
-hipError_t rs_launch_forecast_keys(const rs::ForecastArgs &a, hipStream_t stream) {
+hipError_t rs_launch_forecast_keys(const rs::ForecastArgs &a_, hipStream_t stream) {
+  rs::ForecastArgs a = a_;
+  { /* the mode's digits, as forecast_key_kernel used to take them apart itself */
+    int32_t m = a.pv.mode;
+    a.mode_ground = 0;
+    for (int32_t m9 = m; m9 > 0; m9 /= 10) a.mode_ground |= (m9 % 10) == 9;
+    m = (m == 0) ? 14 : (m == 1) ? 124 : (m == 2) ? 134 : (m == 3) ? 1234 : m;
+    a.mode_digits = 0;
+    a.mode_ndigits = 0;
+    for (; m > 0; m /= 10) { /* (a negative mode has no digit that names a field: no field, as before) */
+      a.mode_digits |= (uint64_t)(m % 10) << (4 * a.mode_ndigits);
+      ++a.mode_ndigits;
+    }
+  }
   hipLaunchKernelGGL(rs::forecast_key_kernel, grid_for(a.npoints), dim3(RS_BLOCK), 0, stream, a);
   return hipGetLastError();
 }

@@ -840,6 +840,13 @@ struct ForcingPrep {
   bool bad_rw = false; /* coupling replays: CheckValues' verdict on the forcing of the index BEHIND the point's
                           coupling window, which the reference's loop has just seen when it rewinds (step_kernel_duo<REPLAY>) */
   RS_REAL tsurfobs = R4(-9999.9); /* FULL: the observation SetCurrentValues forces on Tmp(1:2) at this index, or missing */
+  /* What model_step_fluxes_prepped first reads behind the boundary-layer loop (or in a wavefront whose dry tail is
+   * alive), through accessors: a caller whose ForcingPrep lies in memory that stays put for the whole step hands
+   * over a type that fetches them THERE instead of holding them across the loop (rs_kernels.hip DuoLatePrep). */
+  __device__ __forceinline__ RS_REAL rhz_late() const { return rhz; }
+  __device__ __forceinline__ RS_REAL vz_late() const { return vz; }
+  __device__ __forceinline__ RS_REAL sw_late() const { return sw; }
+  __device__ __forceinline__ RS_REAL lw_late() const { return lw; }
 };
 
 __device__ __forceinline__ bool check_values_forcing(const RS_CONSTS &c, const Forcing &f) {
@@ -1028,12 +1035,13 @@ __device__ __forceinline__ void bl_stats_trips(const BlStatsStep &st, int j) {
 #ifdef RS_BL_LAST
 /* CalcLE's numerator AirVCap*(ESurf - EAir) (src/BoundaryLayer.f90:160-176); the product AirDens x AirHCap arrives
  * as AirVCap, EAir by the mailbox or from the mailed tair and rhz (EAIR ON DEMAND) */
-__device__ __forceinline__ RS_REAL le_numerator(const MathTab &mt, RS_REAL tsurf, const ForcingPrep &q) {
+template <class Q>
+__device__ __forceinline__ RS_REAL le_numerator(const MathTab &mt, RS_REAL tsurf, const Q &q) {
   const RS_REAL as = (tsurf < 0) ? R4(21.875) : R4(17.269);
   const RS_REAL bs = (tsurf < 0) ? R4(265.5) : R4(237.3);
   const RS_REAL ESurf = R4(0.61078) * rs_exp(mt, rs_dv<false>(as * tsurf, tsurf + bs));
 #ifdef RS_EAIR_SURFACE
-  const RS_REAL EAir = air_vapour_pressure(mt, q.tair, q.rhz);
+  const RS_REAL EAir = air_vapour_pressure(mt, q.tair, q.rhz_late());
 #else
   const RS_REAL EAir = q.EAir;
 #endif
@@ -1059,9 +1067,9 @@ __device__ __forceinline__ void bl_last_count(bool dead, bool skip, bool all_war
 #endif
 
 /* The flavour with THE LAST PASS (DRY TAIL): tests, loop on Stab, then the skip or the final correction and the tail */
-template <int TRIPS = 1>
+template <int TRIPS = 1, class Q = ForcingPrep>
 __device__ __forceinline__ Fluxes model_step_fluxes_prepped(const RS_CONSTS &c, const MathTab &mt,
-                                                            Scalars &s, const ForcingPrep &q,
+                                                            Scalars &s, const Q &q,
                                                             const CouplingInputs &cp = CouplingInputs()) {
   Fluxes fx;
   s.wat = s.wat + q.rain;
@@ -1150,19 +1158,19 @@ __device__ __forceinline__ Fluxes model_step_fluxes_prepped(const RS_CONSTS &c, 
   }
 #if RS_BL_GUARD && !defined(RS_IEEE_DIV) && !defined(RS_DIV_CHECK) && !defined(RS_NO_BL_GUARD) && !defined(RS_BL_FIXUP)
   if (!(rs_fabs(fx.blcond) < __builtin_inf()) || !(rs_fabs(fx.le) < __builtin_inf())) {
-    const BlOut o = boundary_layer_ieee(&c, mt.expT, mt.logT, mt.K, s.tsurf, q.tair, q.vz, q.rhz, s.wat);
+    const BlOut o = boundary_layer_ieee(&c, mt.expT, mt.logT, mt.K, s.tsurf, q.tair, q.vz_late(), q.rhz_late(), s.wat);
     fx.blcond = o.blcond;
     fx.le = o.le;
     fx.evap = o.evap;
   }
 #endif
-  fluxes_post(c, s, q.sw, q.lw, cp, fx);
+  fluxes_post(c, s, q.sw_late(), q.lw_late(), cp, fx);
   return fx;
 }
 #else
-template <int TRIPS = 1>
+template <int TRIPS = 1, class Q = ForcingPrep>
 __device__ __forceinline__ Fluxes model_step_fluxes_prepped(const RS_CONSTS &c, const MathTab &mt,
-                                                            Scalars &s, const ForcingPrep &q,
+                                                            Scalars &s, const Q &q,
                                                             const CouplingInputs &cp = CouplingInputs()) {
   Fluxes fx;
   s.wat = s.wat + q.rain;
@@ -1242,7 +1250,7 @@ __device__ __forceinline__ Fluxes model_step_fluxes_prepped(const RS_CONSTS &c, 
     const RS_REAL ESurf = R4(0.61078) * rs_exp(mt, rs_dv<false>(as * s.tsurf, s.tsurf + bs));
 #endif
 #ifdef RS_EAIR_SURFACE
-    const RS_REAL EAir = air_vapour_pressure(mt, q.tair, q.rhz);
+    const RS_REAL EAir = air_vapour_pressure(mt, q.tair, q.rhz_late());
 #else
     const RS_REAL EAir = q.EAir;
 #endif
@@ -1274,13 +1282,13 @@ __device__ __forceinline__ Fluxes model_step_fluxes_prepped(const RS_CONSTS &c, 
   } while (false);
 #if RS_BL_GUARD && !defined(RS_IEEE_DIV) && !defined(RS_DIV_CHECK) && !defined(RS_NO_BL_GUARD) && !defined(RS_BL_FIXUP)
   if (!(rs_fabs(fx.blcond) < __builtin_inf()) || !(rs_fabs(fx.le) < __builtin_inf())) {
-    const BlOut o = boundary_layer_ieee(&c, mt.expT, mt.logT, mt.K, s.tsurf, q.tair, q.vz, q.rhz, s.wat);
+    const BlOut o = boundary_layer_ieee(&c, mt.expT, mt.logT, mt.K, s.tsurf, q.tair, q.vz_late(), q.rhz_late(), s.wat);
     fx.blcond = o.blcond;
     fx.le = o.le;
     fx.evap = o.evap;
   }
 #endif
-  fluxes_post(c, s, q.sw, q.lw, cp, fx);
+  fluxes_post(c, s, q.sw_late(), q.lw_late(), cp, fx);
   return fx;
 }
 #endif /* RS_BL_LAST */

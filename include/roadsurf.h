@@ -994,6 +994,62 @@ int rs_hip_outputs_prob(RsPlan *plan, const RsOutputs *src, const void *deficit_
                         int32_t *ever_device, double *acc_device, int64_t acc_rows, int64_t acc_row0,
                         int32_t *work_device, int64_t work_ints, void *stream);
 
+/* Per-point aggregates over output periods, reduced from the output rows on the device (the ABI number stays: every
+ * name here is new, a binding detects them with rs_hip_period_cols).  The model steps every DTSecs and a consumer
+ * keeps far fewer rows: a kept row is a SAMPLE, and what it does not show - how cold the surface got within the hour,
+ * whether there was ice at any time in it - is what a regular coarse series is wanted for.  A spec cuts the time axis
+ * into `nperiods` periods of `length` indices: period w holds the absolute 1-based time indices
+ *     first_index + w*length .. first_index + (w+1)*length - 1,   0 <= w < nperiods,
+ * and a row outside [first_index, first_index + length*nperiods) belongs to no period and is ignored.  (With
+ * first_index = 2 and length = the driver's decimation step, period w ends at the driver's kept row w + 1.)
+ * rs_hip_outputs_periods reads the first `nrows` rows of a window `src` ([row][slot], of any launch and any flavour;
+ * on an fp32 plan the members of `src` are float arrays, widened exactly), row r being the time index
+ * index0 + r*index_step (computed in 64 bits: any index0 is taken, a row before first_index is simply no period's),
+ * and continues the accumulator of the caller,
+ *     acc_device[(w * RS_PER_COLS + col) * npoints_padded + point],   point = order[slot],   double:
+ *   0       number of valid rows of the period - VALID iff Tsurf is not exactly -9999.0, as for the summaries; only
+ *           valid rows count below
+ *   1, 2    min Tsurf, max Tsurf (+inf / -inf when there is none; a NaN never wins)
+ *   3       the sum of Tsurf over the valid rows in ascending time index, ((x0 + x1) + x2) + ..., every addition
+ *           rounded on its own (0.0 when there is none); the mean is the consumer's one division by column 0
+ *   4       number of rows with Tsurf < spec.th.tsurf_below
+ *   5, 6    Tsurf of the valid row with the largest time index, and that index (-9999.0 and 0 when there is none):
+ *           the sample, which beside min and max shows what sampling missed
+ *   7..11   max of Snow, Water, Ice, Deposit, Ice2 (-inf when there is none; a NaN never wins)
+ *   12..16  number of rows with that storage > spec.th.storage_above[k]
+ * Every comparison is strict; NaN compares false everywhere and still counts as a valid row - column 3 is NaN from
+ * such a row on, column 5 may be one.  rs_hip_periods_reset writes the cell of no rows into all npoints_padded columns
+ * of all periods.  THE FEED CONTRACT: every column but 3 is independent of the order in which rows are fed (column 6
+ * decides column 5); column 3 equals the definition when the rows of each period are fed in ascending time order, each
+ * once, cut into calls anywhere - a call continues the cells it finds.  Rows fed out of order give the sum of the
+ * order fed, a row fed twice counts twice: documented, not detected (as BY_NOW of rs_hip_outputs_prob).  The
+ * accumulator is in POINT order, so re-sorts between the calls do not matter.  The definition, in numpy:
+ * roadsurf_amd/periods.py (reduce_series); the tests hold the device to it bit for bit.
+ * `order_device` and `stream` as for rs_hip_outputs_summary: NULL = the plan's current order, on the plan's stream; a
+ * stream of the caller's only with a kept order row.  An order entry outside [0, npoints) writes nothing; columns at
+ * or beyond npoints are never touched by the feed; the window is read at columns [0, npoints) and rows [0, nrows)
+ * only, and a cell only for 0 <= w < nperiods: the accumulator is nperiods * RS_PER_COLS * npoints_padded doubles.
+ * Refused, with nothing launched and the argument named in rs_last_error: a NULL plan, src, spec or acc_device;
+ * nrows < 1; index_step < 1; a bad spec (first_index < 1, length < 1, nperiods < 1, length * nperiods > 2^31 - 1,
+ * reserved != 0, a threshold that is not finite - rs_hip_period_check says which, on the host alone); a missing
+ * stream of the six; t_stride below the plan's points; a stream of the caller's without a kept order row.
+ * One lane owns a slot and carries the open period's cell in registers over that period's rows in time order, several
+ * rows of all six streams in flight, every row load a whole line per wavefront; a period is never split, and the
+ * periods of a call that spans several go to different wavefronts.  No atomics.  It reads 48 B per point and row (24 B
+ * of an fp32 window) and reads and writes 272 B (2 * RS_PER_COLS * 8) per point and period the call touches;
+ * tools/bench_period_outputs.py measures the cost (its output is kept as profiles/period_outputs.txt). */
+#define RS_PER_COLS 17
+typedef struct RsPeriodSpec {
+  int32_t first_index, length, nperiods, reserved /* 0 */;
+  RsSummarySpec th; /* Tsurf strictly below, storages strictly above: what columns 4 and 12..16 count */
+} RsPeriodSpec;
+int32_t rs_hip_period_cols(void);                      /* RS_PER_COLS of the library */
+int64_t rs_hip_period_spec_bytes(void);                /* sizeof(RsPeriodSpec): the binding's size check */
+int rs_hip_period_check(const RsPeriodSpec *spec);     /* host only; 0, or <0 with rs_last_error naming the member */
+int rs_hip_periods_reset(RsPlan *plan, const RsPeriodSpec *spec, double *acc_device, void *stream);
+int rs_hip_outputs_periods(RsPlan *plan, const RsOutputs *src, int32_t nrows, int32_t index0, int32_t index_step,
+                           const int32_t *order_device, const RsPeriodSpec *spec, double *acc_device, void *stream);
+
 /* Gridded fields gathered to points on the device (the ABI number stays: every name here is new, a binding detects
  * them with rs_hip_grid_max_stencil).  A weather model delivers fields [time][node]; every kernel here reads series
  * [time][point].  Each point has a stencil of `stencil` nodes, node_device[point * stencil + k] (int32) with weights

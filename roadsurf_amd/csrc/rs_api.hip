@@ -20,6 +20,7 @@
 #include "../../include/roadsurf.h"
 #include "rs_kernels.h"
 #include "rs_ens_table.hpp"
+#include "rs_period_rule.hpp"
 #include "rs_devutil.hpp"
 #include <cstdint>
 #include <algorithm>
@@ -554,6 +555,42 @@ int rs_hip_outputs_summary(RsPlan *pl, const RsOutputs *src, int32_t nrows, int3
   if (rows_prologue(pl, src, order, stream, "rs_hip_outputs_summary", on)) return -1;
   HIP_OK(rs_cluster_outputs_summary(on.in, pl->f32, on.order, pl->npoints, src->t_stride, nrows, index0, index_step, *spec,
                                     acc, pl->np_pad, on.stream));
+  return 0;
+}
+
+int32_t rs_hip_period_cols(void) { return RS_PER_COLS; }
+int64_t rs_hip_period_spec_bytes(void) { return (int64_t)sizeof(RsPeriodSpec); }
+
+/* the spec's own limits (rs_period_rule.hpp), the refusal named after the entry point */
+static int period_spec_ok(const RsPeriodSpec *spec, const char *who) {
+  const int code = rs_per::check(spec);
+  return code ? set_err("%s: %s", who, rs_per::check_message(code)) : 0;
+}
+
+int rs_hip_period_check(const RsPeriodSpec *spec) { return period_spec_ok(spec, "rs_hip_period_check"); }
+
+int rs_hip_periods_reset(RsPlan *pl, const RsPeriodSpec *spec, double *acc, void *stream) {
+  if (!pl) return set_err("rs_hip_periods_reset: plan is NULL");
+  if (period_spec_ok(spec, "rs_hip_periods_reset")) return -1;
+  if (!acc) return set_err("rs_hip_periods_reset: acc_device is NULL");
+  HIP_OK(hipSetDevice(pl->device));
+  HIP_OK(rs_cluster_periods_reset(acc, pl->np_pad, *spec, stream_of(pl, stream)));
+  return 0;
+}
+
+int rs_hip_outputs_periods(RsPlan *pl, const RsOutputs *src, int32_t nrows, int32_t index0, int32_t index_step,
+                           const int32_t *order, const RsPeriodSpec *spec, double *acc, void *stream) {
+  const char *who = "rs_hip_outputs_periods";
+  if (!pl) return set_err("%s: plan is NULL", who);
+  if (!src) return set_err("%s: src is NULL", who);
+  if (period_spec_ok(spec, who)) return -1;
+  if (!acc) return set_err("%s: acc_device is NULL", who);
+  if (nrows < 1) return set_err("%s: nrows = %d < 1", who, (int)nrows);
+  if (index_step < 1) return set_err("%s: index_step = %d < 1 (row r is the time index index0 + r*index_step)", who, (int)index_step);
+  RowsOn on;
+  if (rows_prologue(pl, src, order, stream, who, on)) return -1;
+  HIP_OK(rs_cluster_outputs_periods(on.in, pl->f32, on.order, pl->npoints, src->t_stride, nrows, index0, index_step,
+                                    *spec, acc, pl->np_pad, on.stream));
   return 0;
 }
 

@@ -11,6 +11,7 @@
 #include "rs_ens_table.hpp"
 #include "rs_group_rule.hpp"
 #include "rs_kernels.h"
+#include "rs_period_rule.hpp"
 #include "rs_state.h"
 
 namespace {
@@ -330,6 +331,162 @@ hipError_t rs_cluster_outputs_summary(const void *const src[6], bool f32, const 
     hipLaunchKernelGGL(outputs_summary_kernel<float>, grid, block, 0, stream, a);
   else
     hipLaunchKernelGGL(outputs_summary_kernel<double>, grid, block, 0, stream, a);
+  return hipGetLastError();
+}
+
+/* Per-point aggregates over output periods (include/roadsurf.h, rs_hip_outputs_periods; the definition is
+ * roadsurf_amd/periods.py, reduce_series; which rows a period has: rs_period_rule.hpp): the summaries' sibling with
+ * one cell per point AND period, and with a column - the sum of Tsurf - that depends on the order of the additions.
+ * So the summary kernel's split of a call's rows over four wavefronts does not carry over: the rows of one period are
+ * walked by ONE lane in time order.  What is spread instead is the periods, which are independent: a wavefront is 64
+ * slots (blockIdx.x) and every gridDim.y-th period the call touches (blockIdx.y; every gridDim.y-th row where
+ * index_step is above the length, when each row is a period of its own) - the headline's launches of 60
+ * indices touch one or two hourly periods and fill the device with slots alone, a batch of a few hundred points run
+ * in one launch has its hundreds of periods to spread.  The time index is wave-uniform, so a period's rows [lo, hi) of
+ * the call are scalars and leaving a period is a uniform branch: a lane reads its point's cell (17 doubles, computed
+ * address in POINT order) when the call first touches the period, carries it in registers over the period's rows with
+ * PER_ROWS rows of all six streams in flight - every row load a coalesced 512 B per wavefront and stream, 256 B of an
+ * fp32 window - and writes it once on leaving.  A point sits in one slot and a (point, period) cell belongs to one
+ * lane of one wavefront: plain loads and stores, no atomics; all offsets are 64-bit.  Nothing is indexed by a number
+ * of the caller's unchecked: slots and order entries are compared with npoints, rows come from rs_per::rows_of_period
+ * (inside [0, nrows)), periods from rs_per::periods_of_call (inside [0, nperiods)). */
+namespace {
+constexpr int PER_ROWS = 4;
+
+struct Per {
+  double v[RS_PER_COLS]; /* the columns of include/roadsurf.h: everything fp64, indices and counts are exact there */
+  __device__ void load(const double *p, int64_t stride) {
+#pragma unroll
+    for (int c = 0; c < RS_PER_COLS; ++c) v[c] = p[c * stride];
+  }
+  __device__ void store(double *p, int64_t stride) const {
+#pragma unroll
+    for (int c = 0; c < RS_PER_COLS; ++c) p[c * stride] = v[c];
+  }
+  /* one row of the point, the next in time of its period: its time index, Tsurf and the five storages */
+  __device__ void row(double i, double t, const double s[5], const RsSummarySpec &th) {
+    if (t == -9999.0) return; /* never saved: behind the last index of a failed point, or a rejected point */
+    /* ((x0 + x1) + x2) + ...: the first valid row is the sum, not 0.0 + it; every addition rounded on its own */
+    v[3] = v[0] == 0.0 ? t : __dadd_rn(v[3], t);
+    v[0] += 1.0;
+    if (t < v[1]) v[1] = t; /* a NaN never wins: every comparison with it is false */
+    if (t > v[2]) v[2] = t;
+    if (t < th.tsurf_below) v[4] += 1.0;
+    if (i > v[6]) { v[5] = t; v[6] = i; } /* the sample: column 6 decides, whatever the order of feeding */
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+      if (s[k] > v[7 + k]) v[7 + k] = s[k];
+      if (s[k] > th.storage_above[k]) v[12 + k] += 1.0;
+    }
+  }
+};
+
+struct PeriodArgs {
+  const void *src[6];   /* T[nrows][stride] each: Tsurf, Snow, Water, Ice, Deposit, Ice2 */
+  const int32_t *order; /* column s is point order[s]; NULL: point s */
+  double *acc;          /* [nperiods][RS_PER_COLS][np_pad], point order */
+  int64_t npoints, stride, np_pad;
+  int64_t w_lo, w_hi;   /* the periods the call can touch (rs_per::periods_of_call), w_lo <= w_hi */
+  int32_t nrows, index0, index_step;
+  RsPeriodSpec spec;
+};
+
+template <typename T>
+__global__ void __launch_bounds__(64) outputs_periods_kernel(const PeriodArgs a) {
+  const int64_t s = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (s >= a.npoints) return;
+  const int64_t p = a.order ? (int64_t)a.order[s] : s;
+  if (p < 0 || p >= a.npoints) return; /* not an order row of this plan: nothing is written */
+  /* a unit is a period of [w_lo, w_hi] - or, where index_step is above length and so no two rows share a period, a
+   * row: such a call may span far more periods than it has rows */
+  const bool by_row = a.index_step > a.spec.length;
+  const int64_t units = by_row ? (int64_t)a.nrows : a.w_hi - a.w_lo + 1;
+#pragma unroll 1
+  for (int64_t u = blockIdx.y; u < units; u += (int64_t)gridDim.y) {
+    int64_t w;
+    rs_per::Rows rows;
+    if (by_row) {
+      w = rs_per::period_of_row(a.spec, a.index0, a.index_step, u);
+      rows.lo = u;
+      rows.hi = w < 0 ? u : u + 1;
+    } else {
+      w = a.w_lo + u;
+      rows = rs_per::rows_of_period(a.spec, a.index0, a.index_step, a.nrows, w);
+    }
+    if (rows.lo >= rows.hi) continue; /* a row of no period */
+    double *cell = a.acc + w * (int64_t)RS_PER_COLS * a.np_pad + p;
+    Per c;
+    c.load(cell, a.np_pad);
+#pragma unroll 1
+    for (int64_t r0 = rows.lo; r0 < rows.hi; r0 += PER_ROWS) {
+      T x[PER_ROWS][6];
+#pragma unroll
+      for (int q = 0; q < PER_ROWS; ++q) {
+        const int64_t r = r0 + q < rows.hi ? r0 + q : rows.hi - 1; /* behind the range: its last row again, not taken */
+#pragma unroll
+        for (int f = 0; f < 6; ++f) x[q][f] = static_cast<const T *>(a.src[f])[r * a.stride + s];
+      }
+#pragma unroll
+      for (int q = 0; q < PER_ROWS; ++q) {
+        if (r0 + q >= rows.hi) break;
+        const double st[5] = {(double)x[q][1], (double)x[q][2], (double)x[q][3], (double)x[q][4], (double)x[q][5]};
+        c.row((double)rs_per::index_of_row(a.index0, a.index_step, r0 + q), (double)x[q][0], st, a.spec.th);
+      }
+    }
+    c.store(cell, a.np_pad);
+  }
+}
+
+/* the cell of no rows into all np_pad columns of every gridDim.y-th period */
+__global__ void __launch_bounds__(RS_BLOCK) periods_reset_kernel(double *acc, int64_t np_pad, int64_t nperiods) {
+  const int64_t p = (int64_t)blockIdx.x * RS_BLOCK + threadIdx.x;
+  if (p >= np_pad) return;
+  for (int64_t w = blockIdx.y; w < nperiods; w += (int64_t)gridDim.y) {
+    double *cell = acc + w * (int64_t)RS_PER_COLS * np_pad + p;
+#pragma unroll
+    for (int c = 0; c < RS_PER_COLS; ++c) cell[c * np_pad] = rs_per::empty(c);
+  }
+}
+
+/* blocks along y: enough wavefronts for the device where the x blocks alone are few, never more than there are
+ * periods, never above the grid's limit */
+inline unsigned periods_grid_y(int64_t blocks_x, int64_t periods) {
+  const int64_t want = (8192 + blocks_x - 1) / blocks_x;
+  return (unsigned)std::max<int64_t>(1, std::min<int64_t>({want, periods, 65535}));
+}
+}  // namespace
+
+hipError_t rs_cluster_periods_reset(double *acc, int64_t np_pad, const RsPeriodSpec &spec, hipStream_t stream) {
+  const dim3 grid = dim3(grid1(np_pad).x, periods_grid_y((np_pad + RS_BLOCK - 1) / RS_BLOCK, spec.nperiods));
+  hipLaunchKernelGGL(periods_reset_kernel, grid, dim3(RS_BLOCK), 0, stream, acc, np_pad, (int64_t)spec.nperiods);
+  return hipGetLastError();
+}
+
+hipError_t rs_cluster_outputs_periods(const void *const src[6], bool f32, const int32_t *order, int64_t npoints,
+                                      int64_t src_stride, int32_t nrows, int32_t index0, int32_t index_step,
+                                      const RsPeriodSpec &spec, double *acc, int64_t np_pad, hipStream_t stream) {
+  const rs_per::Span span = rs_per::periods_of_call(spec, index0, index_step, nrows);
+  if (span.lo > span.hi || npoints < 1) return hipSuccess; /* every row lies before the first period or behind the last */
+  PeriodArgs a;
+  for (int f = 0; f < 6; ++f) a.src[f] = src[f];
+  a.order = order;
+  a.acc = acc;
+  a.npoints = npoints;
+  a.stride = src_stride;
+  a.np_pad = np_pad;
+  a.w_lo = span.lo;
+  a.w_hi = span.hi;
+  a.nrows = nrows;
+  a.index0 = index0;
+  a.index_step = index_step;
+  a.spec = spec;
+  const int64_t blocks_x = (npoints + 63) / 64;
+  const int64_t units = index_step > spec.length ? (int64_t)nrows : span.hi - span.lo + 1; /* (the kernel's units) */
+  const dim3 grid((unsigned)blocks_x, periods_grid_y(blocks_x, units)), block(64);
+  if (f32)
+    hipLaunchKernelGGL(outputs_periods_kernel<float>, grid, block, 0, stream, a);
+  else
+    hipLaunchKernelGGL(outputs_periods_kernel<double>, grid, block, 0, stream, a);
   return hipGetLastError();
 }
 

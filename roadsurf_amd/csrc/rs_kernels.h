@@ -183,6 +183,12 @@ hipError_t rs_cluster_summary_reset(double *acc, int64_t np_pad, hipStream_t str
 hipError_t rs_cluster_outputs_summary(const void *const src[6], bool f32, const int32_t *order, int64_t npoints,
                                       int64_t src_stride, int32_t nrows, int32_t index0, int32_t index_step,
                                       const RsSummarySpec &spec, double *acc, int64_t np_pad, hipStream_t stream);
+/* per-point aggregates over output periods (rs_hip_outputs_periods): acc[nperiods][RS_PER_COLS][np_pad] in point
+ * order; src and order as above; the spec was checked by the caller (rs_period_rule.hpp, rs_per::check) */
+hipError_t rs_cluster_periods_reset(double *acc, int64_t np_pad, const RsPeriodSpec &spec, hipStream_t stream);
+hipError_t rs_cluster_outputs_periods(const void *const src[6], bool f32, const int32_t *order, int64_t npoints,
+                                      int64_t src_stride, int32_t nrows, int32_t index0, int32_t index_step,
+                                      const RsPeriodSpec &spec, double *acc, int64_t np_pad, hipStream_t stream);
 /* per-group series of output rows (rs_hip_outputs_groups): acc_row0[nrows][ngroups][cols] is the caller's accumulator
  * from its row acc_row0 on; group[npoints] in point order; src and order as above.  rs_cluster_group_cols checks the
  * spec (<0: bad), rs_cluster_group_path chooses the kernel (1: cells in LDS, 2: global cells directly) */

@@ -360,6 +360,45 @@ class Plan:
         """``acc`` as the numpy array [npoints, RS_SUM_COLS] that summary.reduce_series returns (synchronises)."""
         return acc[:, :self.npoints].T.contiguous().cpu().numpy()
 
+    def _period_acc(self, spec, acc):
+        sp, cols = lib.period_spec(spec), lib.period_cols()
+        lib.check(self.L.rs_hip_period_check(C.byref(sp)), "rs_hip_period_check")  # (the spec sizes the accumulator)
+        shape = (int(sp.nperiods), cols, self.np_pad)
+        if acc is None:
+            acc = torch.empty(shape, dtype=torch.float64, device=self.device)
+        assert acc.dtype == torch.float64 and acc.shape == shape and acc.is_contiguous()
+        return sp, acc
+
+    def periods_reset(self, spec, acc: torch.Tensor | None = None,
+                      stream: torch.cuda.Stream | None = None) -> torch.Tensor:
+        """The cell of no rows into every column of every period of ``acc``, float64 [nperiods, RS_PER_COLS, np_pad]
+        on this device (made here if None) - what ``outputs_periods`` continues (rs_hip_periods_reset); ``spec``:
+        periods.PeriodSpec."""
+        sp, acc = self._period_acc(spec, acc)
+        lib.check(self.L.rs_hip_periods_reset(self._h, C.byref(sp), C.c_void_p(acc.data_ptr()), _stream_ptr(stream)),
+                  "rs_hip_periods_reset")
+        return acc
+
+    def outputs_periods(self, out: "OutputWindow", nrows: int, index0: int, index_step: int, spec, acc: torch.Tensor,
+                        order=None, stream: torch.cuda.Stream | None = None, row: int = 0) -> None:
+        """Rows ``row .. row + nrows - 1`` of the output window, [row][slot], fed IN TIME ORDER into the per-point
+        cells of the output periods ``acc`` [nperiods, RS_PER_COLS, np_pad] in POINT order (rs_hip_outputs_periods;
+        roadsurf_amd/periods.py defines the columns and the feed contract).  The first of these rows is the absolute
+        1-based time index ``index0``, the next ``index0 + index_step``; rows outside the spec's periods are ignored;
+        ``spec``: periods.PeriodSpec; ``order`` and ``stream`` as for ``outputs_by_point``."""
+        sp, acc = self._period_acc(spec, acc)
+        o = out.struct_from(row)
+        lib.check(self.L.rs_hip_outputs_periods(self._h, C.byref(o), int(nrows), int(index0), int(index_step), _ptr(order),
+                                                C.byref(sp), C.c_void_p(acc.data_ptr()), _stream_ptr(stream)),
+                  "rs_hip_outputs_periods")
+
+    def periods(self, acc: torch.Tensor, spec=None):
+        """``acc`` as the numpy array [npoints, nperiods, RS_PER_COLS] that periods.reduce_series returns
+        (synchronises)."""
+        a = acc[:, :, :self.npoints].permute(2, 0, 1).contiguous().cpu().numpy()
+        assert spec is None or a.shape[1:] == (int(spec.nperiods), lib.period_cols())
+        return a
+
     def _episode_acc(self, spec, acc):
         if not hasattr(self.L, "rs_hip_episode_cols"):
             raise RuntimeError("this libroadsurf_hip.so has no threshold episodes (rs_hip_episode_cols)")
@@ -660,7 +699,8 @@ class Plan:
 def run_points(forcing: dict, settings: abi.InputSettings, params: abi.InputParameters,
                local, chunk: int = 0, variant: int = 0, device: int = 0,
                lean_if_possible: bool = True, year_month_day=None, history_score: bool | None = None,
-               precision: int = 64, horizon_index=None, summary=None, groups=None, episodes=None, probs=None):
+               precision: int = 64, horizon_index=None, summary=None, groups=None, episodes=None, probs=None,
+               periods=None):
     """Run host arrays ``forcing[name][n, SimLen]`` (numpy, reference layout) through the
     device-resident API and return outputs ``[n, SimLen]`` as numpy.  Test/bench helper:
     transposes with torch on the device, windows of ``chunk`` steps (0 = whole series).
@@ -673,8 +713,12 @@ def run_points(forcing: dict, settings: abi.InputSettings, params: abi.InputPara
     per-point episodes (``Plan.outputs_episodes``) and the result has ``episodes`` [n, cols], finished; not with
     coupling either.  ``probs``: (ensprob.ProbSpec that does not need the deficit, stations int32 [n]) - every
     launch's rows are also counted per station and condition (``Plan.outputs_prob``) and the result has ``probs``
-    [SimLen, ngroups, cols], row r being time index r + 1; not with coupling either."""
+    [SimLen, ngroups, cols], row r being time index r + 1; not with coupling either.  ``periods``: a
+    periods.PeriodSpec - every launch's rows are also fed, by absolute time index and in time order, to the per-point
+    aggregates over output periods (``Plan.outputs_periods``) and the result has ``periods`` [n, nperiods,
+    RS_PER_COLS]; not with coupling either."""
     from . import ensprob, legs  # (legs imports this module when a Leg is made)
+    from . import periods as periods_
 
     require_gpu()
     n, L = forcing["tair"].shape
@@ -682,17 +726,21 @@ def run_points(forcing: dict, settings: abi.InputSettings, params: abi.InputPara
     if isinstance(local, abi.LocalParameters):
         local = [local] * n
     coupled = settings.use_coupling == 1
-    for name, spec in (("summary", summary), ("groups", groups), ("episodes", episodes), ("probs", probs)):
+    for name, spec in (("summary", summary), ("groups", groups), ("episodes", episodes), ("probs", probs),
+                       ("periods", periods)):
         if spec is not None and coupled:  # (the reducers are for the launches of an uncoupled run)
             raise ValueError(f"run_points: no {name} with coupling")
     if probs is not None and ensprob.needs_deficit(probs[0]):
         raise ValueError("run_points: probs: a condition uses the deficit, and the runner has no deficit rows")
+    if periods is not None:
+        periods_.check_spec(periods)
     if year_month_day is None:
         year_month_day = (int(forcing["year"][0]), int(forcing["month"][0]), int(forcing["day"][0]))
     need_full, sky_on = legs.feature_set(settings, local, [forcing], lean_if_possible)
     leg = legs.Leg(forcing, settings, params, local, need_full=need_full, sky_on=sky_on, tbottom_date=year_month_day,
                    precision=precision, variant=variant, history_score=history_score, horizon_index=horizon_index,
-                   device=device, summary=summary, groups=groups, episodes=episodes, probs=probs)
+                   device=device, summary=summary, groups=groups, episodes=episodes, probs=probs,
+                   periods=periods)
     leg.init()
     leg.run(legs.coupling_stages(settings, local, L, chunked=bool(chunk)), chunk)
     res = leg.results()

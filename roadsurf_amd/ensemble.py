@@ -80,7 +80,7 @@ def member_locals(station_local, member_local, parent):
 
 
 def check(S, L, B, settings, station_local, member_local, parent, precision=64, recluster=False, stats=None,
-          probs=None) -> None:
+          probs=None, periods=None) -> None:
     """The refusals of ``run_ensemble`` (ValueError), all of them before any device work."""
     if not 1 <= B <= L - 1:
         raise ValueError(f"run_ensemble: B = {B} outside [1, L - 1 = {L - 1}]: both the analysis and the members "
@@ -115,6 +115,12 @@ def check(S, L, B, settings, station_local, member_local, parent, precision=64, 
         if ensprob.needs_deficit(probs):
             raise ValueError("run_ensemble: probs: a condition uses the deficit, and the runner has no deficit rows "
                              "(such conditions belong to the device API, whose caller supplies them)")
+    if periods is not None:
+        from . import periods as periods_
+        try:
+            periods_.check_spec(periods)
+        except ValueError as e:
+            raise ValueError(f"run_ensemble: periods: {e}") from None
     coupled = settings.use_coupling == 1
     if coupled and precision == 32:
         raise ValueError("run_ensemble: coupling is fp64 only (the time-chunked coupling calls need the fp64 flavour)")
@@ -140,7 +146,7 @@ def check(S, L, B, settings, station_local, member_local, parent, precision=64, 
 def run_ensemble(station_forcing: dict, member_tail: dict, B: int, settings: abi.InputSettings,
                  params: abi.InputParameters, station_local, member_local=None, parent=None, chunk: int = 0,
                  variant: int = 0, precision: int = 64, recluster: bool = False, groups=None, device: int = 0,
-                 timing: dict | None = None, stats=None, probs=None):
+                 timing: dict | None = None, stats=None, probs=None, periods=None):
     """Step ``S`` stations over ``[1, B]``, fan their carried state out to ``len(parent)`` members on the device and
     step those over ``[B + 1, L]``: what ``device.run_points(replicate(...))`` returns for the members, bit for bit,
     without stepping any station's analysis more than once.
@@ -154,12 +160,15 @@ def run_ensemble(station_forcing: dict, member_tail: dict, B: int, settings: abi
     ``stats``: an ``ensstats.EnsSpec`` with ``ngroups = S`` - the members' rows are also reduced per STATION on the
     device (group = parent), behind every launch: mean, spread and quantiles of Tsurf, mean storages; ``probs``: an
     ``ensprob.ProbSpec`` with ``ngroups = S`` whose conditions do not use the deficit - the members under each
-    condition are also counted per STATION on the device, now and by now, behind every launch in row order.
+    condition are also counted per STATION on the device, now and by now, behind every launch in row order;
+    ``periods``: a ``periods.PeriodSpec`` in absolute time indices (``first_index = B + 1``: the first period starts
+    with the members' first index) - the members' rows are also fed to the per-point aggregates over output periods.
 
     Returns a dict: ``stations[name][S][B]``, ``members[name][len(parent)][L - B]`` (row r is time index
     ``B + 1 + r``), ``failed`` = (stations, members) counts, with ``groups`` the series ``[L - B, ngroups, cols]`` and
     with ``stats`` the cells ``stats[L - B, S, cols]`` of ``ensstats.reduce_members`` and with ``probs`` the cells
-    ``probs[L - B, S, cols]`` of ``ensprob.reduce_members_prob`` (row r is time index ``B + 1 + r``).
+    ``probs[L - B, S, cols]`` of ``ensprob.reduce_members_prob`` (row r is time index ``B + 1 + r``) and with
+    ``periods`` the cells ``periods[len(parent), nperiods, RS_PER_COLS]`` of ``periods.reduce_series``.
     Raises ValueError - before any device work - where the analysis would not be shared (``check``)."""
     S = station_forcing["tair"].shape[0]
     nmem, tail_len = member_tail["tair"].shape
@@ -179,7 +188,7 @@ def run_ensemble(station_forcing: dict, member_tail: dict, B: int, settings: abi
     sl = _locals(station_local, S)
     if len(sl) != S:
         raise ValueError("run_ensemble: one LocalParameters, or one per station")
-    check(S, L, B, settings, sl, member_local, parent, precision, recluster, stats, probs)
+    check(S, L, B, settings, sl, member_local, parent, precision, recluster, stats, probs, periods)
     if station_forcing["tair"].shape[1] < B:
         raise ValueError(f"run_ensemble: the stations' forcing is shorter than B = {B}")
     ml = member_locals(sl, member_local, parent)
@@ -198,7 +207,7 @@ def run_ensemble(station_forcing: dict, member_tail: dict, B: int, settings: abi
     st = Leg(head, settings, params, sl, first=1, **common)
     mem = Leg(tail, settings, params, ml, first=B + 1, groups=groups,
               stats=None if stats is None else (stats, parent),
-              probs=None if probs is None else (probs, parent), **common)
+              probs=None if probs is None else (probs, parent), periods=periods, **common)
     st.init()
     st.run(coupling_stages(settings, sl, B, chunked=True), chunk)
     if coupled:  # every window is closed, and the members go on in lock step from where every point resumes, B + 1

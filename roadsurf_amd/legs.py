@@ -85,11 +85,12 @@ class Leg:
     ``horizon_index[i]`` of ``local_horizons`` (not with ``recluster``, which derives its own from the plan order).
     The reducers run behind every launch but a replay: ``summary`` (a SummarySpec) and ``episodes`` (an EpisodeSpec)
     by absolute time index, ``groups`` (GroupSpec, ids [n]) and ``stats`` (EnsSpec, stations [n]) by row, and
-    ``probs`` (ProbSpec without the deficit, stations [n]) by row and in row order, its carry reset once."""
+    ``probs`` (ProbSpec without the deficit, stations [n]) by row and in row order, its carry reset once, and
+    ``periods`` (a PeriodSpec) by absolute time index and in time order, its cells reset once."""
 
     def __init__(self, forcing, settings, params, local, *, need_full, tbottom_date, sky_on=False, first=1,
                  precision=64, variant=0, history_score=None, recluster=False, horizon_index=None, device=0,
-                 summary=None, groups=None, episodes=None, stats=None, probs=None):
+                 summary=None, groups=None, episodes=None, stats=None, probs=None, periods=None):
         import torch
         from . import device as dv
         assert not (recluster and horizon_index is not None)
@@ -188,6 +189,10 @@ class Leg:
             pacc = torch.empty((nrows, int(pspec.ngroups), lib.prob_cols(pspec)), dtype=torch.float64, device=dev)
             self.reducers.append(("probs", lambda out, ns, t0, row: plan.outputs_prob(
                 out, ns, ptable, pspec, pever, pacc, t0 - first, row=row), lambda: plan.prob(pacc, pspec)))
+        if periods is not None:  # (the launches of a leg come in time order: what the sum of a period needs)
+            wacc = plan.periods_reset(periods)
+            self.reducers.append(("periods", lambda out, ns, t0, row: plan.outputs_periods(
+                out, ns, t0, 1, periods, wacc, row=row), lambda: plan.periods(wacc, periods)))
 
     def _window(self, tens, hour, sun, nrows):
         tens = dict(tens, hour=hour)

@@ -136,6 +136,14 @@ class RsProbSpec(C.Structure):
                 ("cond", RsProbCond * RS_PROB_MAX_CONDS)]
 
 
+RS_PER_COLS = 17
+
+
+class RsPeriodSpec(C.Structure):
+    _fields_ = [("first_index", C.c_int32), ("length", C.c_int32), ("nperiods", C.c_int32), ("reserved", C.c_int32),
+                ("th", RsSummarySpec)]
+
+
 class RsSynthSpec(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("point_offset", C.c_int64),
                 ("steps_per_knot", C.c_int32), ("start_hour", C.c_int32), ("order", C.c_void_p)]
@@ -150,7 +158,7 @@ EXPORTS = (
     "rs_hip_plan_npoints", "rs_hip_plan_npoints_padded", "rs_hip_plan_state_bytes",
     "rs_hip_init_state", "rs_hip_step", "rs_hip_step_cpl", "rs_hip_cpl_replay", "rs_hip_set_output_by_point", "rs_hip_state_download", "rs_hip_state_upload", "rs_hip_state_fanout",
     "rs_hip_failed_count", "rs_hip_clock_probe", "rs_hip_first_failed_index", "rs_hip_set_diagnostics", "rs_hip_diagnostics", "rs_hip_sync", "rs_hip_synth_knots", "rs_hip_expand_forcing", "rs_hip_expand_forcing_ordered", "rs_hip_step_knots", "rs_hip_expand_forcing_on",
-    "rs_hip_plan_order", "rs_hip_recluster", "rs_hip_recluster_forecast", "rs_hip_set_history_score", "rs_hip_coupling_windows_closed", "rs_hip_set_writeback", "rs_hip_plan_order_copy", "rs_hip_outputs_by_point", "rs_hip_summary_cols", "rs_hip_summary_reset", "rs_hip_outputs_summary", "rs_hip_group_cols", "rs_hip_group_path", "rs_hip_group_reset", "rs_hip_outputs_groups", "rs_hip_ens_cols", "rs_ens_table_ints", "rs_ens_member_table", "rs_hip_outputs_ens", "rs_hip_episode_cols", "rs_hip_episodes_reset", "rs_hip_outputs_episodes", "rs_hip_episodes_finish", "rs_hip_prob_cols", "rs_hip_prob_needs_deficit", "rs_hip_prob_spec_bytes", "rs_hip_prob_work_ints", "rs_hip_prob_reset", "rs_hip_outputs_prob", "rs_hip_grid_max_stencil", "rs_hip_gather_nodes", "rs_hip_plan_reset_order", "rs_hip_set_variant", "rs_hip_set_precision", "rs_hip_test_math", "rs_hip_division_mode", "rs_hip_div_mismatch_count", "rs_hip_div_special_count", "rs_hip_div_samples", "rs_hip_timing_reset", "rs_hip_timing_step_ms", "rs_hip_timing_intervals",
+    "rs_hip_plan_order", "rs_hip_recluster", "rs_hip_recluster_forecast", "rs_hip_set_history_score", "rs_hip_coupling_windows_closed", "rs_hip_set_writeback", "rs_hip_plan_order_copy", "rs_hip_outputs_by_point", "rs_hip_summary_cols", "rs_hip_summary_reset", "rs_hip_outputs_summary", "rs_hip_group_cols", "rs_hip_group_path", "rs_hip_group_reset", "rs_hip_outputs_groups", "rs_hip_ens_cols", "rs_ens_table_ints", "rs_ens_member_table", "rs_hip_outputs_ens", "rs_hip_episode_cols", "rs_hip_episodes_reset", "rs_hip_outputs_episodes", "rs_hip_episodes_finish", "rs_hip_prob_cols", "rs_hip_prob_needs_deficit", "rs_hip_prob_spec_bytes", "rs_hip_prob_work_ints", "rs_hip_prob_reset", "rs_hip_outputs_prob", "rs_hip_period_cols", "rs_hip_period_spec_bytes", "rs_hip_period_check", "rs_hip_periods_reset", "rs_hip_outputs_periods", "rs_hip_grid_max_stencil", "rs_hip_gather_nodes", "rs_hip_plan_reset_order", "rs_hip_set_variant", "rs_hip_set_precision", "rs_hip_test_math", "rs_hip_division_mode", "rs_hip_div_mismatch_count", "rs_hip_div_special_count", "rs_hip_div_samples", "rs_hip_timing_reset", "rs_hip_timing_step_ms", "rs_hip_timing_intervals",
     "rs_host_run_batch", "rs_last_fanout", "rs_driver_run_request", "rs_driver_run", "rs_driver_run_summary", "rs_driver_run_groups", "rs_driver_run_grid", "rs_driver_expand_grid", "rs_driver_run_kept", "rs_driver_kept_fields", "rs_driver_run_episodes", "rs_driver_last_tiles", "rs_driver_last_raw_launches", "rs_hip_bl_stats", "rs_compat_begin", "rs_compat_step", "rs_compat_replay", "rs_compat_failed_index", "rs_compat_last_state", "rs_compat_outputs", "rs_compat_end", "rs_driver_expand", "rs_driver_release_cache", "rs_abi_version", "rs_abi_sizeof", "rs_fortran_sizeof",
 )
 
@@ -291,6 +299,18 @@ def load() -> C.CDLL:
         L.rs_hip_outputs_prob.argtypes = [C.c_void_p, P(RsOutputs), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                           P(RsProbSpec), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
                                           C.c_int64, C.c_void_p]
+    if hasattr(L, "rs_hip_period_cols"):  # ... nor for the aggregates over output periods
+        L.rs_hip_period_cols.restype = C.c_int32
+        L.rs_hip_period_cols.argtypes = []
+        L.rs_hip_period_spec_bytes.restype = C.c_int64
+        L.rs_hip_period_spec_bytes.argtypes = []
+        if L.rs_hip_period_spec_bytes() != C.sizeof(RsPeriodSpec):
+            raise RuntimeError(f"{LIB_PATH}: RsPeriodSpec has {L.rs_hip_period_spec_bytes()} bytes, this binding "
+                               f"assumes {C.sizeof(RsPeriodSpec)}")
+        L.rs_hip_period_check.argtypes = [P(RsPeriodSpec)]
+        L.rs_hip_periods_reset.argtypes = [C.c_void_p, P(RsPeriodSpec), C.c_void_p, C.c_void_p]
+        L.rs_hip_outputs_periods.argtypes = [C.c_void_p, P(RsOutputs), C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                             P(RsPeriodSpec), C.c_void_p, C.c_void_p]
     if hasattr(L, "rs_hip_state_fanout"):  # ... nor for the fan-out of the carried state
         L.rs_hip_state_fanout.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.rs_hip_plan_reset_order.argtypes = [C.c_void_p]
@@ -445,6 +465,26 @@ def prob_cols(spec) -> int:
         raise RuntimeError("rs_hip_prob_cols: bad spec (ngroups >= 1, 1 <= max_members <= RS_ENS_MAX_MEMBERS, 1 .. "
                            "RS_PROB_MAX_CONDS conditions; use: bits 0..6, at least one; no NaN bound)")
     return n
+
+
+def period_spec(spec) -> RsPeriodSpec:
+    """RsPeriodSpec of anything with ``first_index``, ``length``, ``nperiods``, ``tsurf_below`` and
+    ``storage_above[5]`` (periods.PeriodSpec).  An integer that does not fit the struct's int32 is a ValueError (ctypes
+    would wrap it); nothing else is judged here: the library refuses a bad spec."""
+    if isinstance(spec, RsPeriodSpec):
+        return spec
+    ints = [int(x) for x in (spec.first_index, spec.length, spec.nperiods)]
+    if any(not -2**31 <= x < 2**31 for x in ints):
+        raise ValueError("first_index, length, nperiods: int32")
+    return RsPeriodSpec(*ints, 0, summary_spec(spec))
+
+
+def period_cols() -> int:
+    """Numbers per point and period as the library counts them (rs_hip_period_cols)."""
+    L = load()
+    if not hasattr(L, "rs_hip_period_cols"):
+        raise RuntimeError("this libroadsurf_hip.so has no aggregates over output periods (rs_hip_period_cols)")
+    return int(L.rs_hip_period_cols())
 
 
 def last_error() -> str:

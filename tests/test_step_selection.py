@@ -232,6 +232,34 @@ ROWS = [
     (row(f32=1, sky=1, nl=8), ("rs32::step_kernel_f32_coupled", g(M), 256, L32(8))),
     (row(f32=1, full=1, cpl=CHUNK), ("NONE", 0, 256, 0)),
     (row(f32=1, src=RAW, full=1), ("NONE", 0, 256, 0)),
+    # the dressed wavefronts of tests/test_hip_sky_cpl_waves.py: 1 280 points with sky view, with coupling (1 120 of
+    # them with coupling on: what a replay round lists at most), with both, at 15 and 12 layers, through the driver
+    (row(full=1, sky=1, npoints=1280), (duo(1, 0, 1, sky=1), 20, 128, 0)),
+    (row(full=1, sky=1, npoints=1280, score=0), (duo(0, 0, 1, sky=1), 20, 128, 0)),
+    (row(full=1, sky=1, npoints=1280, a32=0), ("rs::step_kernel_sky_h<4>", 5, 256, 0)),
+    (row(full=1, sky=1, npoints=1280, nl=12), ("rs::step_kernel_sky<false>", 5, 256, L64(12))),
+    (row(src=RAW, full=1, sky=1, npoints=1280), (duo(1, 2, 1, sky=1), 20, 192, 0)),
+    (row(full=1, cpl=GENERAL, npoints=1280), ("rs::step_kernel_coupled<false>", 5, 256, L64(15))),
+    (row(full=1, cpl=CHUNK, npoints=1280), ("rs::step_kernel_cpl_h<3, false>", 5, 256, 0)),
+    (row(full=1, cpl=REPLAY, npoints=1280, list=1, nlist=1120), ("rs::step_kernel_cpl_replay_h<3, false>", 5, 256, 0)),
+    (row(full=1, cpl=GENERAL, npoints=1280, list=1, nlist=1120), ("rs::step_kernel_coupled<false>", 5, 256, L64(15))),
+    (row(full=1, cpl=CHUNK, npoints=1280, nl=12), ("rs::step_kernel_cpl<false>", 5, 256, L64(12))),
+    (row(full=1, cpl=REPLAY, npoints=1280, nl=12, list=1, nlist=1120),
+     ("rs::step_kernel_cpl_replay<false>", 5, 256, L64(12))),
+    (row(full=1, cpl=GENERAL, npoints=1280, nl=12, list=1, nlist=1120),
+     ("rs::step_kernel_coupled<false>", 5, 256, L64(12))),
+    (row(full=1, cpl=CHUNK, sky=1, npoints=1280), ("rs::step_kernel_cpl_h<3, true>", 5, 256, 0)),
+    (row(full=1, cpl=REPLAY, sky=1, npoints=1280, list=1, nlist=1120),
+     ("rs::step_kernel_cpl_replay_h<3, true>", 5, 256, 0)),
+    (row(full=1, cpl=CHUNK, sky=1, npoints=1280, nl=12), ("rs::step_kernel_cpl<true>", 5, 256, L64(12))),
+    (row(full=1, cpl=REPLAY, sky=1, npoints=1280, nl=12, list=1, nlist=1120),
+     ("rs::step_kernel_cpl_replay<true>", 5, 256, L64(12))),
+    (row(src=RAW, full=1, cpl=CHUNK, npoints=1280), (duo(1, 2, 1, cpl=1), 20, 128, 0)),
+    (row(src=RAW, full=1, cpl=REPLAY, npoints=1280, list=1, nlist=1280), (duo(1, 2, 1, cpl=1, replay=1), 20, 128, 0)),
+    (row(src=RAW, full=1, cpl=CHUNK, sky=1, npoints=1280), (duo(1, 2, 1, sky=1, cpl=1), 20, 192, 0)),
+    (row(f32=1, full=1, sky=1, npoints=1280), ("rs32::step_kernel_f32duo<0, true, true, true>", 10, 128, 0)),
+    (row(f32=1, full=1, sky=1, npoints=1280, score=0), ("rs32::step_kernel_f32duo<0, false, true, true>", 10, 128, 0)),
+    (row(f32=1, full=1, cpl=GENERAL, npoints=1280), ("rs32::step_kernel_f32_coupled", 5, 256, L32(15))),
 ]
 
 

@@ -1332,6 +1332,62 @@ int rs_driver_run_episodes(const RsDriverInput *in, const RsGridSource *const *g
                            const RsDriverOutput *out, const RsDriverSummary *summary, const RsDriverGroups *groups,
                            const RsDriverKept *kept, const RsDriverEpisodes *episodes,
                            int32_t device); /* {grids, summary, groups, kept, episodes} */
+/* The ensemble form of the driver (the ABI number stays: every name here is new, a binding detects the call by its
+ * symbol and checks the struct with rs_driver_ensemble_bytes).  `in` holds the STATIONS and the sources they share;
+ * every station has members - parent[q] is member q's station - that see one further source, `member`
+ * ([n_members][n_times] per field, a time axis shared by all members), put at `position` of the overlay order: in
+ * front of shared source `position`, later sources win.  The DEFINITION is a plain call on replicated input
+ * (roadsurf_amd/driver.py, replicate_sources: every shared source row-gathered by parent as bit copies, the member
+ * source inserted): the members get exactly what rs_driver_run_request returns for that input - status,
+ * missing_index, the decisions in `local` and the six series at the kept rows from first_row on - and the stations
+ * what it returns for the shared sources alone at the kept rows before first_row; later station rows read -9999.0, as
+ * rows never saved do.
+ *   The branch follows from the member source: JsonSource::interpolate writes nothing to a simulation time before a
+ * source's first raw time, so with k_b the smallest 0-based simulation index whose time is at or behind
+ * member.times[0], every index below k_b is shared.  branch_index = B = k_b is the last shared 1-based time index,
+ * first_row = ceil(k_b / step) the first kept row that is a member's own, member_out.n_out = n_out - first_row.
+ *   The call steps the stations over [1, B] ONCE, copies every station's carried state into its members on the device
+ * (rs_hip_state_fanout) and steps the members over [B + 1, SimLen] alone.  A tile is a run of whole stations whose
+ * members fit ROADSURF_HIP_TILE_POINTS; the members are a second tile with a second plan beside the stations': the
+ * member source is uploaded as any per-point source, the shared sources' raw columns are filled on the device from the
+ * stations' columns through parent (bit copies: values, per-point time axes and lengths; a gridded shared source
+ * included, whose columns the stations' tile has gathered), horizons and geometry are the station's.  Every member's
+ * decisions are made from its own columns; a station steps with the decisions of its series before index k_b (a hole
+ * behind the branch that rejects the station does not keep its members from being accepted).
+ *   stats / probs: per-station cells of the members' kept rows first_row .. n_out - 1, [n_tail][n_stations][cols] as
+ * rs_hip_outputs_ens and rs_hip_outputs_prob define them for group = parent (spec.ngroups = n_stations), reduced on the
+ * device from the members' final, blanked result block; with all six series pointers of member_out NULL nothing else
+ * of the members' rows comes home.
+ *   Refused before any device work, rs_last_error naming the reason and the first offending member or station: a
+ * member source with per-point time axes, flagged as observation, carrying tsurfobs or without times; times[0] <=
+ * start_time; B outside [1, SimLen - 1]; a parent row that is not non-decreasing within [0, n_stations); more than
+ * RS_MAX_SOURCES sources in all; position outside [0, n_sources]; device < 0 (no fan-out over the device list);
+ * member_out.n_out other than n_tail; a station with more members than a tile holds; with stats or probs the limits
+ * of rs_ens_member_table, ngroups other than n_stations, and a probs condition that uses the deficit.  Refused per
+ * tile, once its decisions are known and before it steps (nothing of that tile has reached the caller's arrays,
+ * earlier tiles are complete): with coupling a station whose coupling is on and couplingIndexI + 1 > B (a replay
+ * reads the index behind its window, which must be shared), and an accepted member whose InitLenI, couplingIndexI or
+ * couplingTsurf differ from its station's, or whose relaxation targets differ while InitLenI < B.
+ *   ROADSURF_HIP_DRIVER_TIMING=1 also reports the column copies and the fan-outs.  rs_driver_last_tiles counts the
+ * station tiles.  tools/bench_driver_ensemble.py measures the call against the plain one (profiles/driver_ensemble.txt). */
+typedef struct RsDriverEnsemble {
+  int32_t n_members;
+  int32_t position;              /* 0 .. in->n_sources: the member source's place in the overlay order */
+  const int32_t *parent;         /* host [n_members], non-decreasing, in [0, in->n_points) */
+  RsRawSource member;            /* fields host [n_members][n_times]; times_per_point = 0, no tsurfobs */
+  RsDriverOutput member_out;     /* n_out = n_tail; series host [n_members][n_tail] or NULL; status, missing_index
+                                    host [n_members] or NULL */
+  LocalParameters *member_local; /* host [n_members] out (lat, lon, sky_view the station's), or NULL */
+  const RsEnsSpec *stats_spec;   /* or NULL */
+  double *stats;                 /* host [n_tail][n_stations][rs_hip_ens_cols] */
+  const RsProbSpec *probs_spec;  /* or NULL */
+  double *probs;                 /* host [n_tail][n_stations][rs_hip_prob_cols] */
+  int32_t branch_index, first_row; /* out: B and the first kept row of the members (also set by a refusal behind them) */
+} RsDriverEnsemble;
+int64_t rs_driver_ensemble_bytes(void); /* sizeof(RsDriverEnsemble): the binding's size check */
+int rs_driver_run_ensemble(const RsDriverInput *in, const RsGridSource *const *grids /* [n_sources] or NULL */,
+                           const InputSettings *settings, const InputParameters *params, LocalParameters *local,
+                           const RsDriverOutput *out, RsDriverEnsemble *ens, int32_t device);
 /* Tiles: a call steps its points in tiles of ROADSURF_HIP_TILE_POINTS (default 524 288).  With
  * coupling the forcing windows of a tile span [first coupling-window start, last window end + 1]
  * of ITS points; a tile whose windows would exceed ROADSURF_HIP_WINDOW_BUDGET_MB (default 24 576)

@@ -44,6 +44,8 @@
 #include "rs_devutil.hpp"
 #include "rs_state.h"
 #include "rs_devices.hpp"
+#include "rs_driver_ens.hpp"
+#include "rs_ens_table.hpp"
 #include "rs_group_rule.hpp"
 #include "rs_kernels.h"
 #include "rs_raw.hpp"
@@ -415,6 +417,7 @@ struct FinalArgs {
   const int32_t *first_missing, *last_obs, *cpl_i;
   const double *cpl_t;
   int32_t use_relaxation, use_coupling, cplLen, default_initlen;
+  int32_t ignore_from; /* a missing value at this 0-based index or behind it rejects nobody (INT32_MAX: read_input's own rule) */
   /* out, [np_pad] */
   int32_t *status, *missing_index, *initlen, *cpl_index, *cpl_hi;
   double *tair_relax, *vz_relax, *rh_relax, *cpl_tsurf;
@@ -430,7 +433,7 @@ __global__ void __launch_bounds__(RS_BLOCK) finalize_kernel(const FinalArgs A) {
   if (p < A.S.npoints) {
     for (int k = 0; k < 6; ++k) {
       const int32_t fm = A.first_missing[(int64_t)k * A.S.np_pad + p];
-      if (fm < mi) { /* strict: at equal index the earlier test in the reference's order wins */
+      if (fm < mi && fm < A.ignore_from) { /* strict: at equal index the earlier test in the reference's order wins */
         mi = fm;
         status = k + 1;
       }
@@ -706,6 +709,45 @@ __global__ void __launch_bounds__(RS_BLOCK) fill_pad_kernel(double *x, int64_t m
   for (int64_t c = m + threadIdx.x; c < mp; c += RS_BLOCK) row[c] = v;
 }
 
+/* The raw columns of one source of a members' tile from the columns of its stations' tile (rs_driver_run_ensemble):
+ * column p of every array takes column parent[p] of the stations' - 64-bit words copied as they are, so values, the
+ * humidity completion the stations' tile has made, per-point time stamps and their padding arrive bit for bit; the
+ * columns [m, mp) read the missing value (time stamps 0, lengths 0).  One array per blockIdx.y - the NFLD variables,
+ * then the per-point time axis with the lengths -, one member per lane, rows in the loop: the stores are whole lines,
+ * the loads the lines of the (non-decreasing) parents. */
+struct ParentCopyArgs {
+  const uint64_t *src[NFLD + 1]; /* [n_times][src_stride], nullptr = absent */
+  uint64_t *dst[NFLD + 1];       /* [n_times][mp] */
+  const int32_t *src_len;        /* [src_stride] or nullptr: with the time axis */
+  int32_t *dst_len;              /* [mp] */
+  const int32_t *parent;         /* [m], every entry a live column of the stations' tile */
+  int32_t n_times;
+  int64_t src_stride, mp, m;
+};
+__global__ void __launch_bounds__(RS_BLOCK) parent_copy_kernel(const ParentCopyArgs A) {
+  __builtin_amdgcn_s_setprio(3); /* before a block's first time step: all of it is waited for */
+  const int64_t p = (int64_t)blockIdx.x * RS_BLOCK + threadIdx.x;
+  const int y = blockIdx.y;
+  const uint64_t *src = A.src[y];
+  uint64_t *dst = A.dst[y];
+  if (p >= A.mp || !src || !dst) return;
+  const bool live = p < A.m;
+  const int64_t q = live ? (int64_t)A.parent[p] : 0;
+  const uint64_t pad = y < NFLD ? (uint64_t)__double_as_longlong(-9999.9) : 0;
+  src += q;
+  dst += p;
+  for (int32_t t = 0; t < A.n_times; ++t) dst[(int64_t)t * A.mp] = live ? src[(int64_t)t * A.src_stride] : pad;
+  if (y == NFLD && A.src_len) A.dst_len[p] = live ? A.src_len[q] : 0;
+}
+
+/* slot s takes src[order[s]] (a members' tile in plan order: the stations' column of the horizon table per slot) */
+__global__ void __launch_bounds__(RS_BLOCK) gather_i32_kernel(const int32_t *__restrict__ order, int64_t npoints,
+                                                              const int32_t *__restrict__ src, int32_t *dst) {
+  __builtin_amdgcn_s_setprio(3); /* a link of the chain between two step launches of a block: all of it is waited for */
+  const int64_t s = (int64_t)blockIdx.x * RS_BLOCK + threadIdx.x;
+  if (s < npoints) dst[s] = src[order[s]];
+}
+
 void launch_expand_raw(bool any_pp, int64_t mp, const ExpandRawArgs &ea, hipStream_t stream) {
   const dim3 g((unsigned)(mp / RS_BLOCK), NFLD), b(RS_BLOCK);
   if (any_pp)
@@ -904,6 +946,14 @@ struct TileRaw {
   SrcSet S{};
 };
 
+/* A members' tile of rs_driver_run_ensemble: the sources it does not upload, because its stations' tile holds them */
+struct ParentFill {
+  const TileRaw *T;               /* the stations' tile, raw columns final (humidity completed) */
+  const int32_t *parent;          /* device [m]: the column of T behind member p */
+  int src_of[RS_MAX_SOURCES];     /* the stations' source behind the members' source s; -1: the member source, uploaded */
+  double *copy_ms;                /* ROADSURF_HIP_DRIVER_TIMING: the column copies' time is added here, or nullptr */
+};
+
 /* ROADSURF_HIP_DRIVER_TIMING=1: wall time per phase of rs_driver_run on stderr (synchronises) */
 struct PhaseTimer {
   bool on;
@@ -944,7 +994,7 @@ struct PhaseTimer {
  * worker two blocks' compute streams can land on one queue, their step kernels then take turns (the call
  * 0.64 s instead of 0.58 s; round 5 again: 0.35 -> 0.43 s, profiles/r05_ab_upload_stream.txt). */
 int upload_finish(const RsDriverInput *in, const Common &c, int64_t p0, int m, int64_t mp,
-                  TileRaw &T, hipStream_t stream) {
+                  TileRaw &T, hipStream_t stream, const ParentFill *pf = nullptr) {
   T.S.nsrc = c.nsrc;
   T.S.simlen = c.L;
   T.S.np_pad = mp;
@@ -958,6 +1008,45 @@ int upload_finish(const RsDriverInput *in, const Common &c, int64_t p0, int m, i
     d = SrcDev{};
     d.n_times = rs.n_times;
     d.is_obs = rs.is_observation;
+    if (pf && pf->src_of[s] >= 0) { /* the stations' columns through parent: no landing block, no transpose */
+      const SrcDev &ps = pf->T->S.src[pf->src_of[s]];
+      ParentCopyArgs pa;
+      std::memset(&pa, 0, sizeof(pa));
+      if (ps.ptimes) {
+        HOK(T.ptimes[s].alloc((size_t)rs.n_times * mp * sizeof(int64_t)));
+        HOK(T.plen[s].alloc(mp * sizeof(int32_t)));
+        HOK(T.prp[s].alloc(mp * sizeof(int32_t)));
+        d.ptimes = T.ptimes[s].as<int64_t>();
+        d.plen = T.plen[s].as<int32_t>();
+        d.prp = T.prp[s].as<int32_t>();
+        pa.src[NFLD] = reinterpret_cast<const uint64_t *>(ps.ptimes);
+        pa.dst[NFLD] = reinterpret_cast<uint64_t *>(T.ptimes[s].p);
+        pa.src_len = ps.plen;
+        pa.dst_len = T.plen[s].as<int32_t>();
+        T.any_pp = true;
+      } else {
+        HOK(T.plan[s].alloc((size_t)c.L * sizeof(PlanStep)));
+        HOK(hipMemcpyAsync(T.plan[s].p, c.plans[s].data(), (size_t)c.L * sizeof(PlanStep), hipMemcpyHostToDevice, stream));
+        d.plan = T.plan[s].as<PlanStep>();
+      }
+      for (int f = 0; f < NFLD; ++f) {
+        if (!ps.fld[f] || rs.n_times == 0) continue;
+        HOK(T.fld[s][f].alloc((size_t)rs.n_times * mp * sizeof(double)));
+        d.fld[f] = T.fld[s][f].as<double>();
+        pa.src[f] = reinterpret_cast<const uint64_t *>(ps.fld[f]);
+        pa.dst[f] = reinterpret_cast<uint64_t *>(T.fld[s][f].p);
+      }
+      pa.parent = pf->parent;
+      pa.n_times = rs.n_times;
+      pa.src_stride = pf->T->S.np_pad;
+      pa.mp = mp;
+      pa.m = m;
+      if (rs.n_times > 0) {
+        hipLaunchKernelGGL(parent_copy_kernel, dim3((unsigned)(mp / RS_BLOCK), NFLD + 1), dim3(RS_BLOCK), 0, stream, pa);
+        HOK(hipGetLastError());
+      }
+      continue;
+    }
     if (rs.times_per_point && rs.n_times > 0) {
       /* per-point axes: times [m][n_times] -> [n_times][mp], lengths, walk positions */
       HOK(T.ptimes[s].alloc((size_t)rs.n_times * mp * sizeof(int64_t)));
@@ -1036,14 +1125,14 @@ int upload_finish(const RsDriverInput *in, const Common &c, int64_t p0, int m, i
 
 /* one tile's turn on the link: its series and, where `hzpt` is given, its local horizons */
 int upload_tile(const RsDriverInput *in, const Common &c, int32_t device, int64_t p0, int m, int64_t mp,
-                TileRaw &T, Dev *hzpt, bool timing, hipStream_t stream) {
+                TileRaw &T, Dev *hzpt, bool timing, hipStream_t stream, const ParentFill *pf = nullptr) {
   const double tg0 = PhaseTimer::now();
   std::lock_guard<std::mutex> turn(rsu::copy_gate(device)); /* rs_devices.hpp: uploads take turns */
   const double tg1 = PhaseTimer::now();
   size_t total = 0;
   for (int s = 0; s < c.nsrc; ++s) {
     const RsRawSource &rs = in->sources[s];
-    if (rs.n_times < 1) continue;
+    if (rs.n_times < 1 || (pf && pf->src_of[s] >= 0)) continue; /* (nothing, or its stations' tile has it) */
     const size_t piece = ((size_t)m * rs.n_times * sizeof(double) + 255) & ~(size_t)255;
     if (const RsGridSource *g = c.grid[s]) { /* the fields are on the device already: the tile's slice of the stencils */
       T.off_node[s] = total;
@@ -1065,10 +1154,11 @@ int upload_tile(const RsDriverInput *in, const Common &c, int32_t device, int64_
         total += piece;
       }
   }
-  HOK(T.stage.alloc(total));
+  HOK(T.stage.alloc(total ? total : 256)); /* (a members' tile whose own source has no variable lands nothing) */
   char *base = T.stage.as<char>();
   for (int s = 0; s < c.nsrc; ++s) {
     const RsRawSource &rs = in->sources[s];
+    if (pf && pf->src_of[s] >= 0) continue;
     if (const RsGridSource *g = c.grid[s]) {
       if (rs.n_times < 1) continue;
       HOK(hipMemcpyAsync(base + T.off_node[s], g->node + (size_t)p0 * g->stencil, (size_t)m * g->stencil * sizeof(int32_t),
@@ -1094,9 +1184,11 @@ int upload_tile(const RsDriverInput *in, const Common &c, int32_t device, int64_
                        hipMemcpyHostToDevice, stream));
   }
   HOK(hipStreamSynchronize(stream));
-  if (int rc = upload_finish(in, c, p0, m, mp, T, stream)) return rc;
+  const double tc0 = PhaseTimer::now();
+  if (int rc = upload_finish(in, c, p0, m, mp, T, stream, pf)) return rc;
   const double tg2 = PhaseTimer::now();
   HOK(hipStreamSynchronize(stream)); /* the turn on the link ends when the last byte has landed */
+  if (pf && pf->copy_ms) *pf->copy_ms += 1e3 * (PhaseTimer::now() - tc0); /* (with the member source's transposes) */
   if (timing)
     fprintf(stderr, "rs_driver_run upload: waited %.1f ms for the link, issued the copies in %.1f ms, "
                     "drained in %.1f ms\n", 1e3 * (tg1 - tg0), 1e3 * (tg2 - tg1), 1e3 * (PhaseTimer::now() - tg2));
@@ -1108,6 +1200,36 @@ struct TileDecisions {
   Dev first_missing, last_obs, cpl_i, cpl_t;
   Dev status, missing_index, initlen, cpl_index, cpl_hi, tair_relax, vz_relax, rh_relax, cpl_tsurf;
 };
+
+/* read_input's decisions from the scan's results.  ignore_from < SimLen (the stations of rs_driver_run_ensemble): the
+ * decisions of the series before that index, as if nothing were missing from it on. */
+int finalize_tile(const Common &c, const InputSettings *st, const TileRaw &T, TileDecisions &D, int32_t ignore_from,
+                  hipStream_t stream) {
+  const int64_t mp = T.S.np_pad;
+  FinalArgs fa;
+  fa.S = T.S;
+  fa.first_missing = D.first_missing.as<int32_t>();
+  fa.last_obs = D.last_obs.as<int32_t>();
+  fa.cpl_i = D.cpl_i.as<int32_t>();
+  fa.cpl_t = D.cpl_t.as<double>();
+  fa.ignore_from = ignore_from;
+  fa.use_relaxation = st->use_relaxation;
+  fa.use_coupling = st->use_coupling;
+  fa.cplLen = c.cplLen;
+  fa.default_initlen = c.default_initlen;
+  fa.status = D.status.as<int32_t>();
+  fa.missing_index = D.missing_index.as<int32_t>();
+  fa.initlen = D.initlen.as<int32_t>();
+  fa.cpl_index = D.cpl_index.as<int32_t>();
+  fa.cpl_hi = D.cpl_hi.as<int32_t>();
+  fa.tair_relax = D.tair_relax.as<double>();
+  fa.vz_relax = D.vz_relax.as<double>();
+  fa.rh_relax = D.rh_relax.as<double>();
+  fa.cpl_tsurf = D.cpl_tsurf.as<double>();
+  hipLaunchKernelGGL(finalize_kernel, grid1(mp), dim3(RS_BLOCK), 0, stream, fa);
+  HOK(hipGetLastError());
+  return 0;
+}
 
 int decide_tile(const Common &c, const InputSettings *st, const TileRaw &T, TileDecisions &D,
                 hipStream_t stream) {
@@ -1136,28 +1258,7 @@ int decide_tile(const Common &c, const InputSettings *st, const TileRaw &T, Tile
     hipLaunchKernelGGL(scan_raw_kernel<false>, dim3((unsigned)(mp / RS_BLOCK), 7), dim3(RS_BLOCK), 0,
                        stream, sa);
   HOK(hipGetLastError());
-  FinalArgs fa;
-  fa.S = T.S;
-  fa.first_missing = sa.first_missing;
-  fa.last_obs = sa.last_obs;
-  fa.cpl_i = sa.cpl_i;
-  fa.cpl_t = sa.cpl_t;
-  fa.use_relaxation = st->use_relaxation;
-  fa.use_coupling = st->use_coupling;
-  fa.cplLen = c.cplLen;
-  fa.default_initlen = c.default_initlen;
-  fa.status = D.status.as<int32_t>();
-  fa.missing_index = D.missing_index.as<int32_t>();
-  fa.initlen = D.initlen.as<int32_t>();
-  fa.cpl_index = D.cpl_index.as<int32_t>();
-  fa.cpl_hi = D.cpl_hi.as<int32_t>();
-  fa.tair_relax = D.tair_relax.as<double>();
-  fa.vz_relax = D.vz_relax.as<double>();
-  fa.rh_relax = D.rh_relax.as<double>();
-  fa.cpl_tsurf = D.cpl_tsurf.as<double>();
-  hipLaunchKernelGGL(finalize_kernel, grid1(mp), dim3(RS_BLOCK), 0, stream, fa);
-  HOK(hipGetLastError());
-  return 0;
+  return finalize_tile(c, st, T, D, INT32_MAX, stream);
 }
 
 /* Copy the decisions back into the caller's LocalParameters / status arrays the way
@@ -1287,11 +1388,12 @@ struct TileHead {
 /* Plan, upload, decide, report for points [p0, p0+m).  The decisions are enqueued for the caller's arrays; they
  * are there on return with `report_now` (or with the timer on, whose laps drain the stream anyway), else
  * after the caller's own report_finish. */
-int tile_prologue(const Call &k, int64_t p0, int m, bool horizons, bool report_now, PhaseTimer &pt, TileHead &H) {
+int tile_prologue(const Call &k, int64_t p0, int m, bool horizons, bool report_now, PhaseTimer &pt, TileHead &H,
+                  const ParentFill *pf = nullptr) {
   H.pg.p = rs_hip_plan_create(k.device, m, &k.consts, k.stream);
   if (!H.pg.p) return -11;
   H.mp = rs_hip_plan_npoints_padded(H.pg.p);
-  if (int rc = upload_tile(k.in, k.c, k.device, p0, m, H.mp, H.T, horizons ? &H.d_hzpt : nullptr, pt.on, k.stream))
+  if (int rc = upload_tile(k.in, k.c, k.device, p0, m, H.mp, H.T, horizons ? &H.d_hzpt : nullptr, pt.on, k.stream, pf))
     return rc;
   pt.lap(1);
   if (int rc = decide_tile(k.c, k.st, H.T, H.D, k.stream)) return rc;
@@ -1470,11 +1572,13 @@ struct TilePolicy {
 };
 
 TilePolicy make_tile_policy(const RunPolicy &R, const Common &c, const InputSettings *st,
-                            const LocalParameters *local, int64_t p0, int m, int64_t mp, bool any_pp) {
+                            const LocalParameters *local, int64_t p0, int m, int64_t mp, bool any_pp,
+                            bool no_replay = false) {
   const int L = c.L, TC = R.TC;
   TilePolicy t;
-  /* chunked coupling: where the tile's coupling windows lie */
-  if (R.cpl_chunked) {
+  /* chunked coupling: where the tile's coupling windows lie (no_replay: the members of rs_driver_run_ensemble, whose
+   * windows their stations have closed - lock-step chunks alone, no replay block) */
+  if (R.cpl_chunked && !no_replay) {
     for (int p = 0; p < m; ++p) {
       const LocalParameters &lp = local[p0 + p];
       if (lp.couplingTsurf < -100 || lp.couplingIndexI < 1) continue; /* src/InputOutput.f90:34-36 */
@@ -1582,6 +1686,13 @@ struct Tile : TileHead {
   rs::RawForcing rf;
   int walk_at = 0;                /* 0-based index the per-point raw walks are positioned at */
   size_t seg = 0;                 /* segment of the index the raw-series kernels start at (seek_seg) */
+  /* rs_driver_run_ensemble.  A members' tile: its stations' horizon table [stations][360] and every member's column of
+   * it, device [m] - and that row in slot order.  A stations' tile: the status read_input gives, where the tile steps
+   * with the decisions of the series before the branch (finalize_tile) - what the result is blanked by */
+  const double *hz_table = nullptr;
+  const int32_t *hz_col = nullptr;
+  Dev d_hzcol_s, d_status_rep;
+  Dev d_etable, d_einv, d_eacc, d_ever, d_words; /* the members' reducers: table, identity row, cells, carry, words */
 
   Tile(Run &run, int64_t p0_, int m_) : r(run), R(run.R), c(run.c), stream(run.stream), p0(p0_), m(m_) {}
   const RsPointParams &ppx() const { return tp.cluster ? pps : pp; }
@@ -1622,6 +1733,10 @@ struct Tile : TileHead {
        * at all where the caller has none (the kernels read a missing table as 0) */
       pp.horizons = r.in->horizons ? d_hzpt.as<double>() : nullptr; /* (uploaded with the series, tile_prologue) */
       pp.horizons_by_point = 1;
+      if (hz_table) { /* a member reads its station's row */
+        pp.horizons = hz_table;
+        pp.horizon_index = hz_col;
+      }
     }
     return 0;
   }
@@ -1728,6 +1843,13 @@ struct Tile : TileHead {
                        skyview ? pp.sky_view : nullptr, skyview ? d_geo_s.as<double>() : nullptr, (int64_t)mp);
     HOK(hipGetLastError());
     if (skyview) pps.horizon_index = ea.order; /* slot -> column of the horizon table */
+    if (skyview && hz_table) {
+      if (!d_hzcol_s.p) HOK(d_hzcol_s.alloc(mp * sizeof(int32_t)));
+      hipLaunchKernelGGL(gather_i32_kernel, grid1(m), dim3(RS_BLOCK), 0, stream, ea.order, (int64_t)m, hz_col,
+                         d_hzcol_s.as<int32_t>());
+      HOK(hipGetLastError());
+      pps.horizon_index = d_hzcol_s.as<int32_t>();
+    }
     return 0;
   }
   /* The sources that can supply a value somewhere in [i0, i0+n): a shared-axis source whose plan is
@@ -1908,8 +2030,8 @@ struct Tile : TileHead {
    * window end (points whose window ends later wait there: they step only the index they
    * are due for).  Plan order: the slots are re-sorted after every lock-step chunk; windows and per-point
    * parameters are produced in slot order, outputs go to their point's column. */
-  int loop_cpl_chunked() {
-    const int L = c.L, TC = R.TC;
+  int loop_cpl_chunked(int last) { /* `last`: the last index stepped (SimLen; B for the stations of an ensemble call) */
+    const int L = last, TC = R.TC;
     RsForcing fo;
     if (tp.cluster && rs_hip_set_output_by_point(pg.p, 1) != 0) return -14;
     const int s1_hi = tp.any_on ? std::min(tp.ce_max, L) : L;
@@ -1942,10 +2064,23 @@ struct Tile : TileHead {
     }
     return 0;
   }
-  /* no windows: the step kernel's ground wave reads the raw series (rs_step_raw) */
-  int loop_raw() {
+  /* the members of an ensemble call with coupling: lock-step chunks over [first, SimLen] - every window is closed */
+  int loop_lockstep(int first) {
     const int L = c.L, TC = R.TC;
-    for (int t0 = 1; t0 <= L; t0 += TC) {
+    RsForcing fo;
+    if (tp.cluster && rs_hip_set_output_by_point(pg.p, 1) != 0) return -14;
+    for (int t0 = first; t0 <= L; t0 += TC) {
+      const int len = std::min(TC, L - t0 + 1);
+      if (int rc = lockstep(t0, len, fo)) return rc;
+      if (t0 + len <= L)
+        if (int rc = resort(t0 + len)) return rc;
+    }
+    return 0;
+  }
+  /* no windows: the step kernel's ground wave reads the raw series (rs_step_raw) */
+  int loop_raw(int first, int last) {
+    const int L = last, TC = R.TC;
+    for (int t0 = first; t0 <= L; t0 += TC) {
       const int len = std::min(TC, L - t0 + 1);
       if (int rc = step_raw(t0, len)) return rc;
       if (t0 + len <= L)
@@ -1954,9 +2089,9 @@ struct Tile : TileHead {
     return 0;
   }
   /* forcing windows for the one-point-per-lane kernels (rs_hip_step) */
-  int loop_windows() {
-    const int L = c.L, TC = R.TC, step = R.step;
-    for (int t0 = 1; t0 <= L; t0 += TC) {
+  int loop_windows(int first, int last) {
+    const int L = last, TC = R.TC, step = R.step;
+    for (int t0 = first; t0 <= L; t0 += TC) {
       const int len = std::min(TC, L - t0 + 1);
       RsForcing fo;
       if (int rc = expand_window(t0, len, fo)) return rc;
@@ -2080,11 +2215,84 @@ struct Tile : TileHead {
     HOK(rs_cluster_episodes_finish(d_epi.as<double>(), m, mp, q.spec, stream));
     return block_home(d_epi.as<double>(), d_epipt.as<double>(), cols, q.episodes);
   }
+  /* The members of an ensemble call (rs_driver_run_ensemble), stations [s0, s0 + ms) of n_stations: blank what
+   * read_input rejected, reduce the kept rows from first_row on per station - the member table of the tile's members,
+   * the cells of the tile's stations into their columns of the caller's [n_tail][n_stations][cols] - and bring the
+   * wanted series' rows from first_row on home. */
+  int members_home(const RsDriverEnsemble &e, int first_row, const int32_t *parent_local, int64_t s0, int ms,
+                   int64_t n_stations) {
+    double *ob = d_out.as<double>();
+    hipLaunchKernelGGL(blank_rejected_kernel, grid1(m), dim3(RS_BLOCK), 0, stream, ob, (int64_t)mp,
+                       (int32_t)R.n_out, (int64_t)m, (const int32_t *)D.status.as<int32_t>());
+    HOK(hipGetLastError());
+    const int n_tail = R.n_out - first_row;
+    std::vector<int32_t> table; /* (alive until the stream has drained) */
+    std::vector<double> cells;
+    if (n_tail > 0 && (e.stats_spec || e.probs_spec)) {
+      const void *in[6];
+      result_rows(in, first_row);
+      HOK(d_einv.alloc(mp * sizeof(int32_t)));
+      HOK(rs_cluster_identity(d_einv.as<int32_t>(), mp, stream)); /* the result block is in point order */
+      RsEnsSpec ts;
+      std::memset(&ts, 0, sizeof(ts));
+      ts.ngroups = ms;
+      char err[300];
+      for (int pass = 0; pass < 2; ++pass) {
+        if (pass == 0 ? !e.stats_spec : !e.probs_spec) continue;
+        const int32_t mm = pass == 0 ? e.stats_spec->max_members : e.probs_spec->max_members;
+        if (table.empty() || ts.max_members != mm) { /* one table serves both reducers under one max_members */
+          HOK(hipStreamSynchronize(stream)); /* (the upload of the last one) */
+          ts.max_members = mm;
+          table.assign((size_t)ms + 1 + m, 0);
+          if (rs_ens::member_table(m, parent_local, &ts, table.data(), err, sizeof(err)) != 0) return fail_msg(err, -1);
+          HOK(d_etable.alloc(table.size() * sizeof(int32_t)));
+          HOK(hipMemcpyAsync(d_etable.p, table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+        }
+        int cols;
+        double *host;
+        if (pass == 0) {
+          RsEnsSpec sp = *e.stats_spec;
+          sp.ngroups = ms;
+          cols = rs_ens::cols(&sp);
+          HOK(d_eacc.alloc((size_t)n_tail * ms * cols * sizeof(double)));
+          HOK(rs_cluster_outputs_ens(in, false, d_etable.as<int32_t>(), d_einv.as<int32_t>(), m, mp, n_tail, sp,
+                                     d_eacc.as<double>(), stream));
+          host = e.stats;
+        } else {
+          RsProbSpec sp = *e.probs_spec;
+          sp.ngroups = ms;
+          cols = rs_cluster_prob_cols(&sp);
+          HOK(d_ever.alloc(mp * sizeof(int32_t)));
+          HOK(hipMemsetAsync(d_ever.p, 0, mp * sizeof(int32_t), stream)); /* one carry per tile, reset once */
+          HOK(d_words.alloc((size_t)n_tail * mp * sizeof(uint32_t)));
+          HOK(d_eacc.alloc((size_t)n_tail * ms * cols * sizeof(double)));
+          HOK(rs_cluster_outputs_prob(in, nullptr, false, nullptr, d_etable.as<int32_t>(), d_einv.as<int32_t>(), m, mp, n_tail,
+                                      sp, d_ever.as<int32_t>(), d_words.as<uint32_t>(), mp, d_eacc.as<double>(), stream));
+          host = e.probs;
+        }
+        cells.resize((size_t)n_tail * ms * cols);
+        HOK(hipMemcpyAsync(cells.data(), d_eacc.p, cells.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+        HOK(hipStreamSynchronize(stream)); /* (d_eacc is the next pass's too) */
+        for (int r = 0; r < n_tail; ++r) /* the tile's stations' columns of every row */
+          std::memcpy(host + ((size_t)r * n_stations + s0) * cols, cells.data() + (size_t)r * ms * cols,
+                      (size_t)ms * cols * sizeof(double));
+      }
+    }
+    const RsDriverOutput &o = e.member_out;
+    double *dst[6] = {o.tsurf, o.snow, o.water, o.ice, o.deposit, o.ice2};
+    for (int f = 0; f < 6 && n_tail > 0; ++f)
+      if (dst[f])
+        if (int rc = block_home(ob + (size_t)f * os + (size_t)first_row * mp, d_outpt.as<double>(), n_tail, dst[f])) return rc;
+    HOK(hipStreamSynchronize(stream));
+    r.pt.lap(5);
+    return 0;
+  }
   /* blank what read_input rejected, then [row][point] -> [point][row] -> the caller's arrays */
   int outputs_home() {
     double *ob = d_out.as<double>();
     hipLaunchKernelGGL(blank_rejected_kernel, grid1(m), dim3(RS_BLOCK), 0, stream, ob, (int64_t)mp,
-                       (int32_t)R.n_out, (int64_t)m, (const int32_t *)D.status.as<int32_t>());
+                       (int32_t)R.n_out, (int64_t)m,
+                       (const int32_t *)(d_status_rep.p ? d_status_rep.as<int32_t>() : D.status.as<int32_t>()));
     HOK(hipGetLastError());
     if (r.q.summary)
       if (int rc = summaries_home()) return rc;
@@ -2393,7 +2601,7 @@ int driver_run_range(const RsDriverInput *in, const InputSettings *st, const Inp
      * t0 = 1, the step, the re-sort for the next chunk - and differ in the rs_* entries they call.  (With the
      * forecast key nobody reads the step kernels' history score: the instances run without it.) */
     if (rs_hip_set_history_score(X.pg.p, (X.tp.cluster && X.tp.forecast_key && !R.cpl_chunked) ? 0 : 1) != 0) return -14;
-    if (int rc = R.cpl_chunked ? X.loop_cpl_chunked() : R.use_raw ? X.loop_raw() : X.loop_windows()) return rc;
+    if (int rc = R.cpl_chunked ? X.loop_cpl_chunked(c.L) : R.use_raw ? X.loop_raw(1, c.L) : X.loop_windows(1, c.L)) return rc;
     X.d_row1.release();
     /* everything is enqueued: the decisions go to the caller's arrays while the device works */
     if (int rc = report_finish(c, st, X.rep, local, out->status, out->missing_index)) return rc;
@@ -2519,9 +2727,328 @@ int driver_run(const RsDriverInput *in, const InputSettings *st, const InputPara
   });
 }
 
+/* ---- the ensemble form (include/roadsurf.h, rs_driver_run_ensemble; the host rules: rs_driver_ens.hpp) */
+
+/* the decisions report_finish writes, of the points [p0, p0 + m), from one array into another */
+void copy_decisions(LocalParameters *dst, const LocalParameters *src, int64_t p0, int m) {
+  for (int64_t p = p0; p < p0 + m; ++p) dst[p] = src[p];
+}
+
+bool same_bits(double a, double b) { return std::memcmp(&a, &b, sizeof(a)) == 0; }
+
+int driver_run_ensemble(const RsDriverInput *in, const RsGridSource *const *grids, const InputSettings *st,
+                        const InputParameters *params, LocalParameters *local, const RsDriverOutput *out,
+                        RsDriverEnsemble *ens, int32_t device) {
+  char b[400];
+  if (!in || !st || !ens || !in->sources || in->n_points < 1 || in->n_sources < 1)
+    return fail_msg("rs_driver_run_ensemble: bad arguments (the stations' input, settings and the ensemble struct are required)", -1);
+  if (device < 0)
+    return fail_msg("rs_driver_run_ensemble: device < 0: the ensemble form has no fan-out over the device list", -1);
+  const int nsh = in->n_sources, S = in->n_points, nmem = ens->n_members;
+  if (nsh + 1 > RS_MAX_SOURCES) {
+    snprintf(b, sizeof(b), "rs_driver_run_ensemble: %d shared sources and the member source are more than RS_MAX_SOURCES = %d", nsh,
+             RS_MAX_SOURCES);
+    return fail_msg(b, -1);
+  }
+  if (ens->position < 0 || ens->position > nsh) {
+    snprintf(b, sizeof(b), "rs_driver_run_ensemble: position = %d outside [0, n_sources = %d]", (int)ens->position, nsh);
+    return fail_msg(b, -1);
+  }
+  const RsRawSource &msrc = ens->member;
+  if (msrc.times_per_point || msrc.lengths)
+    return fail_msg("rs_driver_run_ensemble: the member source needs a time axis shared by all members (times_per_point = 0, lengths NULL)", -1);
+  if (msrc.is_observation)
+    return fail_msg("rs_driver_run_ensemble: the member source must not be an observation source (is_observation = 0): the "
+                    "relaxation index would be a member's own", -1);
+  if (msrc.tsurfobs)
+    return fail_msg("rs_driver_run_ensemble: the member source must carry no tsurfobs: the coupling decisions would be a member's own", -1);
+  if (msrc.n_times < 1 || !msrc.times)
+    return fail_msg("rs_driver_run_ensemble: the member source needs a time axis (n_times >= 1): the branch follows from times[0]", -1);
+  Common chk; /* (SimLen, DTSecs and the shared sources' axes; the call's own Common follows the grids' upload) */
+  if (int rc = prepare(in, st, chk)) return rc;
+  const int L = chk.L;
+  const int step0 = (int)((double)(st->outputStep * 60) / st->DTSecs);
+  if (step0 < 1) return fail_msg("rs_driver_run: outputStep*60/DTSecs < 1", -1);
+  int32_t B = 0, first_row = 0;
+  if (rs_dens::branch(in->start_time, chk.DT, L, step0, msrc.times[0], &B, &first_row, b, sizeof(b)) != 0) return fail_msg(b, -1);
+  ens->branch_index = B;
+  ens->first_row = first_row;
+  std::vector<int32_t> starts;
+  if (rs_dens::check_parent(nmem, ens->parent, S, starts, b, sizeof(b)) != 0) return fail_msg(b, -1);
+  const bool gridded = any_grid(in, grids);
+  if (gridded)
+    if (int rc = check_grids(in, grids)) return rc;
+
+  /* the members' input: the shared sources' axes (their rows come from the stations' tile), the member source in its place */
+  RsRawSource msources[RS_MAX_SOURCES];
+  ParentFill pf{};
+  for (int s = 0, k = 0; s <= nsh; ++s) {
+    if (s == ens->position) {
+      msources[s] = msrc;
+      pf.src_of[s] = -1;
+    } else {
+      msources[s] = in->sources[k];
+      msources[s].lengths = nullptr; /* (the stations': copied on the device) */
+      pf.src_of[s] = k++;
+    }
+  }
+  for (int s = nsh + 1; s < RS_MAX_SOURCES; ++s) pf.src_of[s] = -1;
+  RsDriverInput min = *in;
+  min.n_points = nmem;
+  min.n_sources = nsh + 1;
+  min.sources = msources;
+  min.horizons = nullptr; /* (the stations' table, read through parent) */
+  Common cM;
+  if (int rc = prepare(&min, st, cM)) return rc;
+  /* private decisions: what a tile steps with, and what reaches the caller once the tile's checks have passed */
+  if (!local) return fail_msg("rs_driver_run: params, local and out are required", -1);
+  std::vector<LocalParameters> slocal(local, local + S), rlocal(local, local + S), mlocal((size_t)nmem), mlocal0;
+  for (int q = 0; q < nmem; ++q) mlocal[q] = local[ens->parent[q]];
+  mlocal0 = mlocal;
+  std::vector<int32_t> sstatus(S), smi(S), rstatus(S), rmi(S), mstatus(nmem), mmi(nmem);
+  RunPolicy RS, RM;
+  RsConstants consts;
+  if (int rc = check_run_arguments(in, st, params, slocal.data(), out, chk, RS, consts)) return rc;
+  RM.step = RS.step;
+  RM.n_out = RS.n_out;
+  const int n_tail = RS.n_out - first_row;
+  if (ens->member_out.n_out != n_tail) {
+    snprintf(b, sizeof(b), "rs_driver_run_ensemble: member_out.n_out must be n_out - first_row = %d (B = %d, first_row = %d)", n_tail,
+             (int)B, (int)first_row);
+    return fail_msg(b, -1);
+  }
+  if (ens->stats_spec) {
+    const RsEnsSpec &sp = *ens->stats_spec;
+    if (rs_ens::cols(&sp) < 0 || !ens->stats || sp.ngroups != S) {
+      snprintf(b, sizeof(b), "rs_driver_run_ensemble: stats: a good spec with ngroups = n_stations = %d and the stats array are required", S);
+      return fail_msg(b, -1);
+    }
+    std::vector<int32_t> table((size_t)S + 1 + nmem);
+    if (rs_ens::member_table(nmem, ens->parent, &sp, table.data(), b, sizeof(b)) != 0) return fail_msg(b, -1);
+  }
+  if (ens->probs_spec) {
+    const RsProbSpec &sp = *ens->probs_spec;
+    if (rs_cluster_prob_cols(&sp) < 0 || !ens->probs || sp.ngroups != S) {
+      snprintf(b, sizeof(b), "rs_driver_run_ensemble: probs: a good spec with ngroups = n_stations = %d and the probs array are required", S);
+      return fail_msg(b, -1);
+    }
+    if (rs_cluster_prob_needs_deficit(&sp) == 1)
+      return fail_msg("rs_driver_run_ensemble: probs: a condition uses the deficit, and the call has no deficit rows for the members", -1);
+    RsEnsSpec ts;
+    std::memset(&ts, 0, sizeof(ts));
+    ts.ngroups = S;
+    ts.max_members = sp.max_members;
+    std::vector<int32_t> table((size_t)S + 1 + nmem);
+    if (rs_ens::member_table(nmem, ens->parent, &ts, table.data(), b, sizeof(b)) != 0) return fail_msg(b, -1);
+  }
+  make_run_policy(st, consts, chk, slocal.data(), 0, S, RS);
+  make_run_policy(st, consts, cM, mlocal.data(), 0, nmem, RM);
+  if (RS.coupled && !RS.cpl_chunked)
+    return fail_msg("rs_driver_run_ensemble: coupling over the whole series (ROADSURF_HIP_CPL_WHOLE) cannot stop at the branch", -1);
+  if (const int32_t crowded = rs_dens::first_crowded(starts, RM.P); crowded >= 0) {
+    snprintf(b, sizeof(b), "rs_driver_run_ensemble: station %d has %d members, more than a tile of %d points holds", (int)crowded,
+             (int)(starts[crowded + 1] - starts[crowded]), RM.P);
+    return fail_msg(b, -1);
+  }
+
+  /* ---- device work from here on */
+  if (int rc = check_device(device)) return rc;
+  HOK(hipSetDevice(device));
+  GridUploads G; /* (declared before the stream: freed when it is gone) */
+  GridView gv{grids, nullptr};
+  if (gridded) {
+    if (int rc = upload_grids(in, grids, std::vector<int>{device}, G)) return rc;
+    gv.dev = G.find(device);
+  }
+  Common cS;
+  if (int rc = prepare(in, st, cS, gridded ? &gv : nullptr)) return rc;
+  StreamGuard sg;
+  HOK(hipStreamCreate(&sg.s));
+  const hipStream_t stream = sg.s;
+  const Call callS{in, st, cS, consts, device, stream, slocal.data(), sstatus.data(), smi.data()};
+  const Call callM{&min, st, cM, consts, device, stream, mlocal.data(), mstatus.data(), mmi.data()};
+  WindowLease arena_lease; /* (declared behind the stream guard: WindowLease::release) */
+  arena_lease.stream = stream;
+  arena_lease.cache = g_arenacache;
+  rsu::Arena arena;
+  const size_t arena_bytes = arena_estimate(in, cS, RS) + arena_estimate(&min, cM, RM);
+  if (arena_lease.acquire(arena_bytes, device) == hipSuccess) {
+    arena.base = static_cast<char *>(arena_lease.p);
+    arena.cap = arena_bytes;
+  }
+  ArenaScope arena_scope(arena.base ? &arena : nullptr);
+  SharedAxes axS, axM;
+  if (int rc = upload_shared_axes(callS, RS, 0, S, axS)) return rc;
+  if (int rc = upload_shared_axes(callM, RM, 0, nmem, axM)) return rc;
+  PhaseTimer pt(stream, RS.timing);
+  pt.lap(0);
+  WindowLease winS, winM;
+  winS.stream = winM.stream = stream;
+  const RsDriverRequest none{};
+  const double tbottom = rs_bottom_temperature(params, &consts, in->year[0], in->month[0], in->day[0]);
+  Run runS{callS, params, out, RS, 0, S, tbottom, axS, pt, winS, 0, none, nullptr};
+  Run runM{callM, params, &ens->member_out, RM, 0, nmem, tbottom, axM, pt, winM, 0, none, nullptr};
+  pt.lap(6);
+
+  double copy_ms = 0.0, fanout_ms = 0.0;
+  pf.copy_ms = RS.timing ? &copy_ms : nullptr;
+  int64_t Scap = RS.P;
+  g_last_tiles = 0;
+  g_last_raw_launches = 0;
+  const size_t arena_mark = arena.off;
+  for (int32_t s0 = 0; s0 < S;) {
+    arena.rewind(arena_mark);
+    const int ms = rs_dens::tile_stations(starts, s0, Scap, RM.P);
+    if (ms < 1) return fail_msg("rs_driver_run_ensemble: a station's members do not fit a tile", -1); /* (first_crowded has passed) */
+    const int64_t q0 = starts[s0];
+    const int mm = starts[(size_t)s0 + ms] - starts[s0];
+    /* the stations: an ordinary tile, its decisions at once */
+    Tile XS(runS, s0, ms);
+    copy_decisions(slocal.data(), local, s0, ms);
+    if (int rc = tile_prologue(runS, s0, ms, RS.skyview && in->horizons, true, pt, XS)) return rc;
+    copy_decisions(rlocal.data(), slocal.data(), s0, ms);
+    bool behind = false; /* some station is rejected by a hole at or behind the branch alone */
+    for (int p = s0; p < s0 + ms; ++p) {
+      rstatus[p] = sstatus[p];
+      rmi[p] = smi[p];
+      behind = behind || (sstatus[p] >= 1 && sstatus[p] <= 6 && smi[p] >= B);
+    }
+    if (behind) { /* ... and steps, with the decisions of the series before the branch: its members may be accepted */
+      HOK(XS.d_status_rep.alloc(XS.mp * sizeof(int32_t)));
+      HOK(hipMemcpyAsync(XS.d_status_rep.p, XS.D.status.p, XS.mp * sizeof(int32_t), hipMemcpyDeviceToDevice, stream));
+      if (int rc = finalize_tile(cS, st, XS.T, XS.D, B, stream)) return rc;
+      copy_decisions(slocal.data(), local, s0, ms);
+      if (int rc = report_issue(XS.D, s0, ms, XS.rep, stream)) return rc;
+      if (int rc = report_finish(cS, st, XS.rep, slocal.data(), sstatus.data(), smi.data())) return rc;
+    }
+    if (RS.coupled)
+      for (int p = s0; p < s0 + ms; ++p) {
+        const LocalParameters &l = slocal[p];
+        const bool on = sstatus[p] == 0 && !(l.couplingTsurf < -100 || l.couplingIndexI < 1);
+        if (on && l.couplingIndexI + 1 > B) {
+          snprintf(b, sizeof(b), "rs_driver_run_ensemble: station %d: couplingIndexI + 1 = %d > B = %d: a coupling replay reads the "
+                                 "index behind its window, which must be shared", p, l.couplingIndexI + 1, (int)B);
+          return fail_msg(b, -1);
+        }
+      }
+    if (int rc = XS.point_params()) return rc;
+    XS.tp = make_tile_policy(RS, cS, st, slocal.data(), s0, ms, XS.mp, XS.T.any_pp);
+    if (XS.tp.halve_to) { /* started again at the same station */
+      Scap = XS.tp.halve_to;
+      continue;
+    }
+    /* the members: a second tile, a second plan */
+    Tile XM(runM, q0, std::max(mm, 1));
+    Dev d_parent;
+    std::vector<int32_t> parent_local((size_t)std::max(mm, 1));
+    if (mm > 0) {
+      for (int q = 0; q < mm; ++q) parent_local[q] = ens->parent[q0 + q] - s0;
+      HOK(d_parent.alloc((size_t)mm * sizeof(int32_t)));
+      HOK(hipMemcpyAsync(d_parent.p, parent_local.data(), (size_t)mm * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+      pf.T = &XS.T;
+      pf.parent = d_parent.as<int32_t>();
+      copy_decisions(mlocal.data(), mlocal0.data(), q0, mm);
+      if (int rc = tile_prologue(runM, q0, mm, false, true, pt, XM, &pf)) return rc;
+      /* the sharing argument, held to the decisions themselves */
+      for (int q = (int)q0; q < q0 + mm; ++q) {
+        if (mstatus[q] != 0) continue;
+        const int p = ens->parent[q];
+        const LocalParameters &a = mlocal[q], &l = slocal[p];
+        const char *what = nullptr;
+        if (sstatus[p] != 0) what = "status";
+        else if (a.InitLenI != l.InitLenI) what = "InitLenI";
+        else if (RS.coupled && a.couplingIndexI != l.couplingIndexI) what = "couplingIndexI";
+        else if (RS.coupled && !same_bits(a.couplingTsurf, l.couplingTsurf)) what = "couplingTsurf";
+        else if (st->use_relaxation == 1 && l.InitLenI < B &&
+                 !(same_bits(a.tair_relax, l.tair_relax) && same_bits(a.VZ_relax, l.VZ_relax) && same_bits(a.RH_relax, l.RH_relax)))
+          what = "relaxation targets (with InitLenI < B)";
+        if (what) {
+          snprintf(b, sizeof(b), "rs_driver_run_ensemble: member %d differs from its station %d in %s: the analysis would not be shared "
+                                 "(B = %d)", q, p, what, (int)B);
+          return fail_msg(b, -1);
+        }
+      }
+      if (RM.skyview && in->horizons && XS.d_hzpt.p) {
+        XM.hz_table = XS.d_hzpt.as<double>();
+        XM.hz_col = d_parent.as<int32_t>();
+      }
+      if (int rc = XM.point_params()) return rc;
+      XM.tp = make_tile_policy(RM, cM, st, mlocal.data(), q0, mm, XM.mp, XM.T.any_pp, true);
+    }
+    /* the tile's checks have passed: its decisions reach the caller */
+    for (int p = s0; p < s0 + ms; ++p) {
+      local[p] = rlocal[p];
+      if (out->status) out->status[p] = rstatus[p];
+      if (out->missing_index) out->missing_index[p] = rmi[p];
+    }
+    for (int64_t q = q0; q < q0 + mm; ++q) {
+      if (ens->member_local) ens->member_local[q] = mlocal[q];
+      if (ens->member_out.status) ens->member_out.status[q] = mstatus[q];
+      if (ens->member_out.missing_index) ens->member_out.missing_index[q] = mmi[q];
+    }
+    if (int rc = XS.buffers()) return rc;
+    if (mm > 0)
+      if (int rc = XM.buffers()) return rc;
+    pt.lap(3);
+    /* the stations' leg: [1, B] */
+    if (rs_hip_set_history_score(XS.pg.p, (XS.tp.cluster && XS.tp.forecast_key && !RS.cpl_chunked) ? 0 : 1) != 0) return -14;
+    if (int rc = RS.cpl_chunked ? XS.loop_cpl_chunked(B) : RS.use_raw ? XS.loop_raw(1, B) : XS.loop_windows(1, B)) return rc;
+    XS.d_row1.release();
+    if (RS.cpl_chunked && rs_hip_coupling_windows_closed(XS.pg.p, 1) != 0) return -14;
+    if (mm > 0) {
+      /* the members' leg: the stations' carried state, then [B + 1, SimLen] */
+      if (RS.timing) HOK(hipStreamSynchronize(stream));
+      const double tf0 = PhaseTimer::now();
+      if (rs_hip_state_fanout(XM.pg.p, XS.pg.p, parent_local.data()) != 0) return -15;
+      if (RS.timing) {
+        HOK(hipStreamSynchronize(stream));
+        fanout_ms += 1e3 * (PhaseTimer::now() - tf0);
+      }
+      if (rs_hip_set_history_score(XM.pg.p, (XM.tp.cluster && XM.tp.forecast_key && !RM.cpl_chunked) ? 0 : 1) != 0) return -14;
+      if (int rc = RM.cpl_chunked ? XM.loop_lockstep(B + 1) : RM.use_raw ? XM.loop_raw(B + 1, L) : XM.loop_windows(B + 1, L))
+        return rc;
+    }
+    pt.lap(4);
+    if (int rc = XS.outputs_home()) return rc;
+    if (mm > 0) {
+      if (int rc = XM.members_home(*ens, first_row, parent_local.data(), s0, ms, S)) return rc;
+    } else if (n_tail > 0) { /* stations without a member: the empty cells */
+      for (int r = 0; r < n_tail; ++r)
+        for (int p = s0; p < s0 + ms; ++p) {
+          if (ens->stats_spec) {
+            const int cols = rs_ens::cols(ens->stats_spec);
+            double *cell = ens->stats + ((size_t)r * S + p) * cols;
+            for (int k = 0; k < cols; ++k) cell[k] = k < 2 ? 0.0 : -9999.0;
+          }
+          if (ens->probs_spec) {
+            const int cols = rs_cluster_prob_cols(ens->probs_spec);
+            double *cell = ens->probs + ((size_t)r * S + p) * cols;
+            for (int k = 0; k < cols; ++k) cell[k] = 0.0;
+          }
+        }
+    }
+    s0 += ms;
+    ++g_last_tiles;
+    Scap = RS.P;
+  }
+  if (RS.timing)
+    fprintf(stderr, "rs_driver_run_ensemble: B = %d, first_row = %d, %d tiles: column copies %.3f ms, fan-outs %.3f ms\n", (int)B,
+            (int)first_row, g_last_tiles, copy_ms, fanout_ms);
+  pt.report();
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
+
+int64_t rs_driver_ensemble_bytes(void) { return (int64_t)sizeof(RsDriverEnsemble); }
+
+int rs_driver_run_ensemble(const RsDriverInput *in, const RsGridSource *const *grids, const InputSettings *st,
+                           const InputParameters *params, LocalParameters *local, const RsDriverOutput *out,
+                           RsDriverEnsemble *ens, int32_t device) {
+  return driver_run_ensemble(in, grids, st, params, local, out, ens, device);
+}
 
 int rs_driver_expand(const RsDriverInput *in, const InputSettings *st, LocalParameters *local,
                      double *merged, int32_t *status, int32_t *missing_index, int32_t device) {

@@ -89,6 +89,14 @@ class RsDriverRequest(C.Structure):
                 ("episodes", C.POINTER(RsDriverEpisodes))]
 
 
+class RsDriverEnsemble(C.Structure):
+    _fields_ = [("n_members", C.c_int32), ("position", C.c_int32), ("parent", abi.c_int32_p), ("member", RsRawSource),
+                ("member_out", RsDriverOutput), ("member_local", C.POINTER(abi.LocalParameters)),
+                ("stats_spec", C.POINTER(rslib.RsEnsSpec)), ("stats", abi.c_double_p),
+                ("probs_spec", C.POINTER(rslib.RsProbSpec)), ("probs", abi.c_double_p),
+                ("branch_index", C.c_int32), ("first_row", C.c_int32)]
+
+
 @dataclasses.dataclass
 class RawSource:
     """One data source: ``fields`` name -> [n_points][n_times] float64 (absent name = variable
@@ -403,6 +411,192 @@ def run(sources, settings: abi.InputSettings, params: abi.InputParameters, start
     res["local"] = larr
     res["step"] = step
     return res
+
+
+# ---- the ensemble form: one analysis per station, members over the forecast alone --------
+
+def branch_index(start_time: int, dtsecs: int, simlen: int, member_time0: int) -> int:
+    """``B``, the last 1-based time index the members share with their station, for a member source whose first raw
+    time is ``member_time0``: ``JsonSource::interpolate`` writes nothing to a simulation time before a source's first
+    raw time, so with ``k_b`` the smallest 0-based simulation index with ``start_time + k*dtsecs >= member_time0`` the
+    indices ``k < k_b`` do not see the source, and ``B = k_b``.  ValueError where the member source starts at or
+    before ``start_time`` (index 1 is the stations') or ``B`` leaves ``[1, simlen - 1]``."""
+    start_time, dtsecs, simlen, member_time0 = int(start_time), int(dtsecs), int(simlen), int(member_time0)
+    if dtsecs < 1 or simlen < 1:
+        raise ValueError("branch_index: DTSecs >= 1 and SimLen >= 1 are required")
+    if member_time0 <= start_time:
+        raise ValueError(f"branch_index: the member source starts at {member_time0}, at or before start_time = "
+                         f"{start_time}: times[0] > start_time is required")
+    k = -(-(member_time0 - start_time) // dtsecs)
+    if not 1 <= k <= simlen - 1:
+        raise ValueError(f"branch_index: B = {k} outside [1, SimLen - 1 = {simlen - 1}]: both the stations and the "
+                         "members need an index")
+    return k
+
+
+def member_rows(settings: abi.InputSettings, start_time: int, member_time0: int) -> tuple[int, int, int]:
+    """(B, first_row, n_tail) of an ensemble call: kept row r is the 0-based index ``r*step`` (roadrunner.cpp:303),
+    so ``first_row = ceil(B / step)`` is the first kept row that is a member's own and ``n_tail = n_out - first_row``
+    the rows a member has."""
+    step, n_out = output_rows(settings)
+    B = branch_index(start_time, int(settings.DTSecs), settings.SimLen, member_time0)
+    first_row = -(-B // step)
+    return B, first_row, n_out - first_row
+
+
+def check_parent(parent, n_stations: int) -> np.ndarray:
+    """``parent`` as int32 [n_members]: non-decreasing - the members of a station side by side, a station may have
+    none - with every entry in ``[0, n_stations)``; ValueError names the first member that is not."""
+    parent = np.ascontiguousarray(parent, dtype=np.int32)
+    if parent.ndim != 1 or len(parent) < 1:
+        raise ValueError("parent: one station per member, at least one member")
+    for q, s in enumerate(parent):
+        if not 0 <= s < n_stations:
+            raise ValueError(f"member {q}: parent {int(s)} outside [0, n_stations = {n_stations})")
+        if q and s < parent[q - 1]:
+            raise ValueError(f"member {q}: parent {int(s)} below member {q - 1}'s parent {int(parent[q - 1])}: parent "
+                             "must be non-decreasing")
+    return parent
+
+
+def default_position(shared_sources) -> int:
+    """Where the member source goes by default: directly behind the non-observation shared sources that lead the
+    list, before the first observation one."""
+    k = 0
+    while k < len(shared_sources) and not shared_sources[k].is_observation:
+        k += 1
+    return k
+
+
+def replicate_sources(shared_sources, member_source: RawSource, parent, position: int | None = None) -> list:
+    """The input of the plain run an ensemble call is defined by: every shared source row-gathered by ``parent`` as
+    bit copies (``a[parent]``: fields, per-point time axes and lengths; of a ``grid.GridSource`` the stencils - its
+    fields are shared as they are), and the member source inserted at ``position`` of the overlay order, where later
+    sources win.  Pure numpy."""
+    parent = np.asarray(parent, np.int64)
+    position = default_position(shared_sources) if position is None else int(position)
+    if not 0 <= position <= len(shared_sources):
+        raise ValueError(f"position = {position} outside [0, {len(shared_sources)}]")
+    out = []
+    for s in shared_sources:
+        if isinstance(s, rsgrid.GridSource):
+            out.append(rsgrid.GridSource(s.times, s.fields, np.ascontiguousarray(s.node[parent]),
+                                         np.ascontiguousarray(s.weight[parent]), s.is_observation))
+            continue
+        t = np.asarray(s.times)
+        out.append(RawSource(np.ascontiguousarray(t[parent]) if t.ndim == 2 else t,
+                             {k: np.ascontiguousarray(np.asarray(a)[parent]) for k, a in s.fields.items()},
+                             s.is_observation,
+                             None if s.lengths is None else np.ascontiguousarray(np.asarray(s.lengths)[parent])))
+    out.insert(position, member_source)
+    return out
+
+
+def _bind_ensemble(L):
+    if not hasattr(L, "rs_driver_run_ensemble"):
+        raise RuntimeError("this libroadsurf_hip.so has no ensemble form of the driver (rs_driver_run_ensemble)")
+    L.rs_driver_ensemble_bytes.restype = C.c_int64
+    if L.rs_driver_ensemble_bytes() != C.sizeof(RsDriverEnsemble):
+        raise RuntimeError("RsDriverEnsemble: the library's struct and the binding's differ in size")
+    P = C.POINTER
+    L.rs_driver_run_ensemble.argtypes = [P(RsDriverInput), P(P(RsGridSource)), P(abi.InputSettings),
+                                         P(abi.InputParameters), P(abi.LocalParameters), P(RsDriverOutput),
+                                         P(RsDriverEnsemble), C.c_int32]
+    return L
+
+
+def run_ensemble(shared_sources, member_source: RawSource, parent, settings: abi.InputSettings,
+                 params: abi.InputParameters, start_time: int, forecast_time: int, position: int | None = None,
+                 local=None, horizons: np.ndarray | None = None, device: int = 0, series: bool = True,
+                 stats=None, probs=None, out: dict | None = None) -> dict:
+    """The ensemble form of ``run`` (rs_driver_run_ensemble): ``shared_sources`` hold the stations - per-point or
+    gridded, as ``run`` takes them - and ``member_source`` [n_members][n_times] on one shared time axis is what the
+    members of a station see in addition, at ``position`` of the overlay order (default ``default_position``);
+    ``parent`` [n_members] names every member's station, non-decreasing.  The analysis is stepped once per station, the
+    carried state fanned out on the device, the members stepped over the forecast alone.  By definition the members get
+    what ``run(replicate_sources(...), ...)`` returns - status, missing_index, the decisions in ``local`` and the six
+    series at the kept rows from ``first_row`` on - and the stations what ``run(shared_sources, ...)`` returns at the
+    kept rows before ``first_row`` (later rows read -9999.0).
+
+    Returns a dict: ``stations`` like ``run``'s result (arrays [n_stations][n_out]), ``members`` likewise with arrays
+    [n_members][n_tail] (``series=False``: no series in it, and none downloaded), ``branch_index``, ``first_row``,
+    and with ``stats`` = an ``ensstats.EnsSpec`` / ``probs`` = an ``ensprob.ProbSpec`` (``ngroups`` = the stations) the
+    cells ``stats[n_tail][n_stations][cols]`` / ``probs[n_tail][n_stations][cols]`` of ``ensstats.reduce_members`` /
+    ``ensprob.reduce_members_prob`` over the members' rows, group = parent.  ``local``: the stations' parameters (in:
+    lat, lon, sky_view; out: the decisions); a member has its station's.  ``out``: the result of an earlier call of
+    the same shapes, whose arrays are written again.  The library refuses - RuntimeError with its reason - what would
+    not keep the analysis shared (include/roadsurf.h lists the refusals)."""
+    L = _bind_ensemble(_bind(rslib.load()))
+    cal = calendar(start_time, settings.SimLen, int(settings.DTSecs))
+    inp, grids, keep = make_grid_input(shared_sources, start_time, forecast_time, cal, horizons)
+    if grids is not None:
+        _need_grids(L)
+    S = inp.n_points
+    step, n_out = output_rows(settings)
+    position = default_position(shared_sources) if position is None else int(position)
+    parent = np.ascontiguousarray(parent, dtype=np.int32)
+    if parent.ndim != 1 or len(parent) < 1:
+        raise ValueError("parent: one station per member, at least one member")
+    nmem = len(parent)
+    mt = np.ascontiguousarray(member_source.times, np.int64)
+    # the rows a member has; where the library will refuse the branch, any shape does (the call names the reason)
+    try:
+        _, _, n_tail = member_rows(settings, start_time, int(mt.flat[0]) if mt.size else start_time)
+    except ValueError:
+        n_tail = 0
+    minp, mkeep = make_input([member_source], start_time, forecast_time, n_points=nmem)
+    earlier = out or {}
+    est, eme = earlier.get("stations", {}), earlier.get("members", {})
+
+    def rows(old, n, w):
+        ok = old is not None and old.shape == (n, w) and old.dtype == np.float64 and old.flags.c_contiguous
+        return old if ok else np.full((n, w), np.nan)
+
+    def ints(old, n):
+        ok = old is not None and old.shape == (n,) and old.dtype == np.int32
+        return old if ok else np.empty(n, np.int32)
+    st_res = {k: rows(est.get(k), S, n_out) for k in OUT_FIELDS}
+    me_res = {k: rows(eme.get(k), nmem, n_tail) for k in OUT_FIELDS} if series else {}
+    for res, e, n in ((st_res, est, S), (me_res, eme, nmem)):
+        res["status"] = ints(e.get("status"), n)
+        res["missing_index"] = ints(e.get("missing_index"), n)
+    sout = RsDriverOutput()
+    sout.n_out = n_out
+    ens = RsDriverEnsemble()
+    ens.member_out.n_out = n_tail
+    for o, res in ((sout, st_res), (ens.member_out, me_res)):
+        for k in OUT_FIELDS:
+            if k in res:
+                setattr(o, k, res[k].ctypes.data_as(abi.c_double_p))
+        o.status = res["status"].ctypes.data_as(abi.c_int32_p)
+        o.missing_index = res["missing_index"].ctypes.data_as(abi.c_int32_p)
+    larr = _locals(S, local)
+    marr = (abi.LocalParameters * nmem)()
+    ens.n_members = nmem
+    ens.position = position
+    ens.parent = parent.ctypes.data_as(abi.c_int32_p)
+    ens.member = minp.sources[0]
+    ens.member_local = marr
+    result = {"stations": st_res, "members": me_res}
+    if stats is not None:
+        sp = rslib.ens_spec(stats)
+        cols = L.rs_hip_ens_cols(C.byref(sp))
+        result["stats"] = np.full((n_tail, S, max(cols, 1)), np.nan)
+        ens.stats_spec = C.pointer(sp)
+        ens.stats = result["stats"].ctypes.data_as(abi.c_double_p)
+    if probs is not None:
+        pp = rslib.prob_spec(probs)
+        cols = L.rs_hip_prob_cols(C.byref(pp))
+        result["probs"] = np.full((n_tail, S, max(cols, 1)), np.nan)
+        ens.probs_spec = C.pointer(pp)
+        ens.probs = result["probs"].ctypes.data_as(abi.c_double_p)
+    rslib.check(L.rs_driver_run_ensemble(C.byref(inp), grids, C.byref(settings), C.byref(params), larr, C.byref(sout),
+                                         C.byref(ens), device), "rs_driver_run_ensemble")
+    del keep, mkeep
+    st_res.update(local=larr, step=step)
+    me_res.update(local=marr, step=step)
+    result.update(branch_index=int(ens.branch_index), first_row=int(ens.first_row))
+    return result
 
 
 # ---- file formats (host only) ------------------------------------------------------------

@@ -159,7 +159,7 @@ EXPORTS = (
     "rs_hip_init_state", "rs_hip_step", "rs_hip_step_cpl", "rs_hip_cpl_replay", "rs_hip_set_output_by_point", "rs_hip_state_download", "rs_hip_state_upload", "rs_hip_state_fanout",
     "rs_hip_failed_count", "rs_hip_clock_probe", "rs_hip_first_failed_index", "rs_hip_set_diagnostics", "rs_hip_diagnostics", "rs_hip_sync", "rs_hip_synth_knots", "rs_hip_expand_forcing", "rs_hip_expand_forcing_ordered", "rs_hip_step_knots", "rs_hip_expand_forcing_on",
     "rs_hip_plan_order", "rs_hip_recluster", "rs_hip_recluster_forecast", "rs_hip_set_history_score", "rs_hip_coupling_windows_closed", "rs_hip_set_writeback", "rs_hip_plan_order_copy", "rs_hip_outputs_by_point", "rs_hip_summary_cols", "rs_hip_summary_reset", "rs_hip_outputs_summary", "rs_hip_group_cols", "rs_hip_group_path", "rs_hip_group_reset", "rs_hip_outputs_groups", "rs_hip_ens_cols", "rs_ens_table_ints", "rs_ens_member_table", "rs_hip_outputs_ens", "rs_hip_episode_cols", "rs_hip_episodes_reset", "rs_hip_outputs_episodes", "rs_hip_episodes_finish", "rs_hip_prob_cols", "rs_hip_prob_needs_deficit", "rs_hip_prob_spec_bytes", "rs_hip_prob_work_ints", "rs_hip_prob_reset", "rs_hip_outputs_prob", "rs_hip_period_cols", "rs_hip_period_spec_bytes", "rs_hip_period_check", "rs_hip_periods_reset", "rs_hip_outputs_periods", "rs_hip_grid_max_stencil", "rs_hip_gather_nodes", "rs_hip_plan_reset_order", "rs_hip_set_variant", "rs_hip_set_precision", "rs_hip_test_math", "rs_hip_division_mode", "rs_hip_div_mismatch_count", "rs_hip_div_special_count", "rs_hip_div_samples", "rs_hip_timing_reset", "rs_hip_timing_step_ms", "rs_hip_timing_intervals",
-    "rs_host_run_batch", "rs_last_fanout", "rs_driver_run_request", "rs_driver_run", "rs_driver_run_summary", "rs_driver_run_groups", "rs_driver_run_grid", "rs_driver_expand_grid", "rs_driver_run_kept", "rs_driver_kept_fields", "rs_driver_run_episodes", "rs_driver_last_tiles", "rs_driver_last_raw_launches", "rs_hip_bl_stats", "rs_compat_begin", "rs_compat_step", "rs_compat_replay", "rs_compat_failed_index", "rs_compat_last_state", "rs_compat_outputs", "rs_compat_end", "rs_driver_expand", "rs_driver_release_cache", "rs_abi_version", "rs_abi_sizeof", "rs_fortran_sizeof",
+    "rs_host_run_batch", "rs_last_fanout", "rs_driver_run_request", "rs_driver_run", "rs_driver_run_summary", "rs_driver_run_groups", "rs_driver_run_grid", "rs_driver_expand_grid", "rs_driver_run_kept", "rs_driver_kept_fields", "rs_driver_run_episodes", "rs_driver_ensemble_bytes", "rs_driver_run_ensemble", "rs_driver_last_tiles", "rs_driver_last_raw_launches", "rs_hip_bl_stats", "rs_compat_begin", "rs_compat_step", "rs_compat_replay", "rs_compat_failed_index", "rs_compat_last_state", "rs_compat_outputs", "rs_compat_end", "rs_driver_expand", "rs_driver_release_cache", "rs_abi_version", "rs_abi_sizeof", "rs_fortran_sizeof",
 )
 
 _lib = None
